@@ -67,7 +67,12 @@ def parse():
                                                               "stream) -- the single-rank twin of a multi-rank run")
     ap.add_argument("--init-f32", action="store_true", help="fp64 run starting from the fp32-rounded factors (so that one CPU "
                                                             "reference fit serves both precisions)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (factors W_T, H, d and the loss; c5 also theta) as "
+                         "DIR/<name>.npy in the run's precision (the loss in float64), at most 64 MB in all (dump_outputs())")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # c3: the movielens fixture (tests/golden/movielens.npz, extracted from the reference's data/movielens.rda), k = 32,
     # L1 = c(0, 0.1), mask = "zeros" (a fit-time no-op in the reference); c5: NB counts, IRLS half-updates
     # c1: the hawaiibirds fixture (tests/golden/hawaiibirds.npz, extracted from the reference's data/hawaiibirds.rda), k = 10: the whole fit
@@ -162,6 +167,33 @@ def cpu_baseline(A_loc, At_loc, W_T, H, G_h, G_w, cfg_k, dtype, seconds, cd_maxi
                            out["H"][0], n, out["H"][1], out["H"][2], out["W"][0], m, out["W"][1], out["W"][2],
                            "-O3 -march=native" if native else "-O2"),
                 dtype=dtype)
+
+
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, headers included at most DUMP_BYTES in all.  Inputs are seeded, so two
+    builds given the same arguments can be compared file for file.  When the arrays are larger, one-dimensional ones are kept
+    whole and every two-dimensional one keeps the same share of its rows, drawn by a fixed-seed generator (sorted); their indices
+    go beside it as <name>_rows.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: np.ascontiguousarray(a) for name, a in arrays.items()}
+    header = 128                                            # bytes of one .npy header (format 1.0, these shapes)
+    total = sum(a.nbytes + header for a in arrays.values())
+    big = {name: a for name, a in arrays.items() if a.ndim == 2}
+    frac = 1.0
+    if total > DUMP_BYTES:
+        room = DUMP_BYTES - sum(a.nbytes + header for name, a in arrays.items() if name not in big) - 2 * header * len(big)
+        frac = room / float(sum(a.shape[0] * (a.strides[0] + 8) for a in big.values()))
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError("dump_outputs: %s is %s, not float32 / float64" % (name, a.dtype))
+        if name in big and frac < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def collectives_model(world, m, k, sv, w_solve):
@@ -326,6 +358,9 @@ def main():
         dt = time.perf_counter() - t0
         ops.record = False
         final_loss_t = loss.clone()
+        outputs = None
+        if args.dump_outputs and rank == 0:            # host copies before anything below moves the state (rank 0: its H shard)
+            outputs = dict(W_T=st.W_T.cpu().numpy(), H=st.H.cpu().numpy(), d=st.d.cpu().numpy(), loss=final_loss_t[:1].cpu().numpy())
         work = ops.ctx.stats()
         eager_ms_per_step = None
         if graph is not None:
@@ -604,6 +639,8 @@ def main():
                 out["fp64"] = fp64_leg(args, ref_loss)
             except Exception as e:
                 out["fp64"] = {"error": repr(e)}
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
     if world > 1 or force_dist:
         dist.barrier()
@@ -663,6 +700,9 @@ def bench_c1(args):
               "what": "workgroup 0's wall-clock ticks inside the timed launch, per iteration: fused rhs + solve of both sides | waiting at the four "
                       "barriers for the slowest workgroup | scaling, Gram partials, fixed-order sums, loss"}
     state = (W.clone(), H.clone(), d.clone())
+    outputs = None
+    if args.dump_outputs:
+        outputs = dict(W_T=state[0].cpu().numpy(), H=state[1].cpu().numpy(), d=state[2].cpu().numpy(), loss=res[2:3].cpu().numpy())
     reps = []
     for _ in range(15):                                 # the same region again (fresh start + warm-up each time): spread of a 0.5 ms measurement
         reset(); launch(max(args.warmup, 1), 0)
@@ -780,6 +820,8 @@ def bench_c1(args):
             line["speedup_vs_cpu_baseline_what"] = "fit_from_start (the same K iterations from the same start as the CPU fit) over the best CPU thread count"
         except Exception as e:
             line["cpu_baseline"] = {"value": None, "unit": "cols/s", "cores": os.cpu_count(), "kind": "port", "sample": "failed: %r" % (e,)}
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     print(json.dumps(line))
 
 
@@ -833,6 +875,9 @@ def bench_c5(args):
     dt = time.perf_counter() - t0
     ops.record = False
     final_loss = float(out4[0].item())
+    outputs = None
+    if args.dump_outputs:                        # (the counting iteration below moves the factors)
+        outputs = dict(W_T=W.cpu().numpy(), H=H.cpu().numpy(), d=d.cpu().numpy(), theta=theta.cpu().numpy(), loss=out4[:1].cpu().numpy())
     ev = ops.event_ms()
     phases = {name: round(ms / args.steps, 4) for name, (c, ms) in sorted(ev.items())}
     # ---- work of one more iteration, counted by the kernels themselves (outside the timed region; two atomics per column)
@@ -894,6 +939,8 @@ def bench_c5(args):
             line["speedup_vs_cpu_baseline"] = line["value"] / line["cpu_baseline"]["value"]
         except Exception as e:
             line["cpu_baseline"] = {"value": None, "unit": "cols/s", "cores": os.cpu_count(), "kind": "port", "sample": "failed: %r" % (e,)}
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     print(json.dumps(line))
 
 

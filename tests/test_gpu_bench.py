@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -63,6 +64,25 @@ def test_bench_line_graph_and_eager_modes_agree():
     # same iterations, same kernels: the modes differ in how launches are issued, not in what is computed
     assert g["final_loss"] == e["final_loss"]
     assert g["roofline"]["mean_sweeps_per_column"] == e["roofline"]["mean_sweeps_per_column"]
+
+
+def test_bench_dump_outputs_follow_the_timed_steps(tmp_path):
+    """--dump-outputs writes what the last timed step computed: the factors and loss after warm-up + steps iterations from the seeded
+    start -- the same however the iterations are split between warm-up and timed steps, and whether the timed ones are graph replays or
+    the eager loop; one timed step fewer gives other factors."""
+    def dump(name, *extra):
+        d = _run("--dump-outputs", str(tmp_path / name), *extra)
+        got = {f[:-4]: np.load(str(tmp_path / name / f)) for f in os.listdir(str(tmp_path / name))}
+        assert got["loss"][0] == d["final_loss"]
+        return got
+    a = dump("a")
+    assert sorted(a) == ["H", "W_T", "d", "loss"]
+    assert a["W_T"].shape == (3000, 64) and a["H"].shape == (24000, 64) and a["d"].shape == (64,) and a["loss"].shape == (1,)
+    assert a["W_T"].dtype == a["H"].dtype == a["d"].dtype == np.float32 and a["loss"].dtype == np.float64
+    for other in (dump("b", "--warmup", "4", "--steps", "3"), dump("c", "--no-graph")):
+        for name in a:
+            assert np.array_equal(a[name], other[name]), name
+    assert not np.array_equal(a["H"], dump("e", "--steps", "3")["H"])
 
 
 def test_bench_line_carries_cpu_reference_deviation_and_fp64_leg():
