@@ -237,6 +237,48 @@ RCPPML_GPU_API void rcppml_gpu_nmf_profile_double(const int* col_ptr, const int*
                                                   int* cd_maxit, int* seed, double* out_phase_ms_total,
                                                   double* out_phase_ms_per_iter, int* out_n_iters, int* out_status);
 
+/* Clustering (rcppml_amd/csrc/ops_cluster.hip): bipartition() and dclust() with the reference's CPU semantics
+ * (inst/include/FactorNet/clustering/bipartition.hpp, dclust.hpp) -- SplitMix64(seed) start (seed 0 -> 12345), the same seed for
+ * every split, closed-form rank-2 ALS, 1 - Pearson(w, w_prev) tolerance -- in fp64, all splits of one tree level batched.
+ * Refused with *out_status = -1 (rcppml_gpu_last_error), outputs untouched: no device, a malformed CSC, *max_iter < 1 (the CPU
+ * reads an uninitialised h), *tol >= 1 or NaN (the CPU runs no iteration), *min_samples < 1 (the CPU never terminates), a seed
+ * outside [0, 2^32).  Env RCPPML_GPU_CLUSTER_BUDGET (bytes, default 2 GiB): per-cluster device memory (32 m bytes a split) of one
+ * launch batch; a level over it runs in chunks, with the same result.
+ *
+ * rcppml_gpu_bipartition_double: the reference plugin's 15 pointers (src/gpu_bridge_cluster.cu:57-62) with the buffers R allocates
+ * (R/bipartition.R:105-108): partition n ints (0 = samples1, i.e. v > 0; 1 = samples2), v m doubles (the first min(m, n) sample
+ * scores are written, nothing past m), center 2 m doubles (center1 then center2), dist 1.  All columns, calc_dist on. */
+RCPPML_GPU_API void rcppml_gpu_bipartition_double(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n,
+                                                  int* nnz, int* max_iter, double* tol, int* nonneg, double* seed, int* partition,
+                                                  double* v, double* center, double* dist, int* out_status);
+/* rcppml_gpu_dclust_double: the reference plugin's 16 pointers (src/gpu_bridge_cluster.cu:105-110).  assignments (n ints): the
+ * sample's cluster as its index in the CPU's emission order; *max_clusters > 0 keeps the first *max_clusters clusters and gives
+ * the samples of the others -1.  *out_num_clusters: clusters reported. */
+RCPPML_GPU_API void rcppml_gpu_dclust_double(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n,
+                                             int* nnz, int* max_clusters, int* min_samples, double* min_dist, int* max_iter,
+                                             double* tol, int* nonneg, double* seed, int* assignments, int* out_num_clusters,
+                                             int* out_status);
+/* Build-defined forms (the Python surface).  Every *_len / *_cap is the buffer's capacity on input and the count written on
+ * output; a capacity below what the call needs is refused (status -1) with the size needed in it, nothing else written.
+ * rcppml_gpu_bipartition_ex: samples (0-based, any order, duplicates allowed; NULL or *n_samples = 0: all columns), calc_dist
+ * switch.  partition / v: one entry per sample (*partition_len, *v_len >= n_samples); center: 2 m (zeros without calc_dist);
+ * out_dist -1 without calc_dist; out_iter = ALS iterations run. */
+RCPPML_GPU_API void rcppml_gpu_bipartition_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+                                              const int* samples, int* n_samples, int* max_iter, double* tol, int* nonneg, double* seed,
+                                              int* calc_dist, int* partition, int* partition_len, double* v, int* v_len, double* center,
+                                              int* center_len, int* out_size1, int* out_size2, double* out_dist, int* out_iter,
+                                              int* out_status);
+/* rcppml_gpu_dclust_ex: assignments (n ints, emission-order cluster index); per cluster (capacity *cluster_cap): out_size,
+ * out_radius (the rejected split's dist with min_dist > 0, else 0), out_node (its node in the split tree), out_center (m doubles
+ * per cluster, may be NULL: then not computed).  The split tree (capacity *node_cap): node 0 is the root (parent -1, bit -1),
+ * every accepted split adds its two children (bit 0 = samples1, 1 = samples2); node_iter = ALS iterations of the node's
+ * bipartition (-1: none was attempted).  A cluster's id is the bits on its path from the root -- any depth. */
+RCPPML_GPU_API void rcppml_gpu_dclust_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+                                         int* min_samples, double* min_dist, int* max_iter, double* tol, int* nonneg, double* seed,
+                                         int* assignments, int* cluster_cap, int* out_size, double* out_radius, int* out_node,
+                                         double* out_center, int* node_cap, int* node_parent, int* node_bit, int* node_iter,
+                                         int* out_status);
+
 /* Last error text of the calling thread ("" if none). */
 RCPPML_GPU_API const char* rcppml_gpu_last_error(void);
 

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_nmf_target", "rcppml_hip_axpy", "rcppml_hip_add_diag", "rcppml_hip_clip_upper",
     "rcppml_hip_scale_order", "rcppml_hip_gram_loss_mse", "rcppml_hip_tail_scale_gram", "rcppml_hip_tail_scale_gram_loss",
     "rcppml_hip_als_small_eligible", "rcppml_hip_als_small_fit",
+    "rcppml_gpu_bipartition_double", "rcppml_gpu_dclust_double", "rcppml_gpu_bipartition_ex", "rcppml_gpu_dclust_ex",
 ]
 
 
@@ -725,3 +726,94 @@ def nmf_dense(A, k, W_T, H, *, entry="float", max_iter=100, tol=1e-4, L1_H=0.0, 
     getattr(L, "rcppml_gpu_nmf_dense_unified_" + entry)(*args)
     return dict(d=d, iter=out_iter.value, converged=bool(out_conv.value), loss=out_loss.value, tol=out_tol.value,
                 theta=theta[:out_theta_len.value].copy(), status=out_status.value, error=last_error() if out_status.value != 0 else "")
+
+
+# ----------------------------------------------------------------------------- clustering (ops_cluster.hip)
+def _csc_args(p, i, x):
+    return (np.ascontiguousarray(p, np.int32), np.ascontiguousarray(i, np.int32), np.ascontiguousarray(x, np.float64))
+
+
+def bipartition_double(p, i, x, m, n, *, max_iter=100, tol=1e-5, nonneg=True, seed=0.0, partition=None, v=None, center=None):
+    """The R-shaped 15-pointer entry (reference src/gpu_bridge_cluster.cu:57-62), with R's buffer sizes by default: partition n
+    ints, v m doubles, center 2 m doubles (tests hand in larger buffers to watch what lies past them).  Returns dict(status,
+    error, partition, v, center, dist)."""
+    p, i, x = _csc_args(p, i, x)
+    partition = np.zeros(n, np.int32) if partition is None else partition
+    v = np.zeros(m, np.float64) if v is None else v
+    center = np.zeros(2 * m, np.float64) if center is None else center
+    dist, st = C.c_double(0.0), C.c_int(-99)
+    lib().rcppml_gpu_bipartition_double(_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0]), _ci(max_iter),
+                                        _cd(tol), _ci(1 if nonneg else 0), _cd(seed), _np_ptr(partition), _np_ptr(v),
+                                        _np_ptr(center), C.byref(dist), C.byref(st))
+    return dict(status=st.value, error=last_error() if st.value else "", partition=partition, v=v, center=center, dist=dist.value)
+
+
+def dclust_double(p, i, x, m, n, *, min_samples, min_dist=0.0, max_iter=100, tol=1e-5, nonneg=True, seed=0.0, max_clusters=0,
+                  assignments=None):
+    """The R-shaped 16-pointer entry (reference src/gpu_bridge_cluster.cu:105-110).  Returns dict(status, error, assignments,
+    num_clusters)."""
+    p, i, x = _csc_args(p, i, x)
+    assignments = np.zeros(n, np.int32) if assignments is None else assignments
+    nc, st = C.c_int(0), C.c_int(-99)
+    lib().rcppml_gpu_dclust_double(_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0]), _ci(max_clusters),
+                                   _ci(min_samples), _cd(min_dist), _ci(max_iter), _cd(tol), _ci(1 if nonneg else 0), _cd(seed),
+                                   _np_ptr(assignments), C.byref(nc), C.byref(st))
+    return dict(status=st.value, error=last_error() if st.value else "", assignments=assignments, num_clusters=nc.value)
+
+
+def bipartition_ex(p, i, x, m, n, samples=None, *, max_iter=100, tol=1e-5, nonneg=True, seed=0.0, calc_dist=True, capacity=None):
+    """Build-defined bipartition of a sample subset (0-based, duplicates allowed).  capacity: (partition, v, center) buffer
+    sizes to hand in (tests of the capacity check); default: what the call needs.  Returns dict(status, error, partition, v,
+    center, size1, size2, dist, iter, needed)."""
+    p, i, x = _csc_args(p, i, x)
+    smp = None if samples is None else np.ascontiguousarray(samples, np.int32)
+    ns = n if smp is None else smp.shape[0]
+    caps = list(capacity) if capacity is not None else [ns, ns, 2 * m]
+    part = np.zeros(max(caps[0], 1), np.int32)
+    v = np.zeros(max(caps[1], 1), np.float64)
+    center = np.zeros(max(caps[2], 1), np.float64)
+    lens = [C.c_int(int(c)) for c in caps]
+    s1, s2, it, st, dist = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(-99), C.c_double(0.0)
+    lib().rcppml_gpu_bipartition_ex(_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0]),
+                                    _np_ptr(smp) if smp is not None else None, _ci(0 if smp is None else ns), _ci(max_iter), _cd(tol),
+                                    _ci(1 if nonneg else 0), _cd(seed), _ci(1 if calc_dist else 0), _np_ptr(part), C.byref(lens[0]),
+                                    _np_ptr(v), C.byref(lens[1]), _np_ptr(center), C.byref(lens[2]), C.byref(s1), C.byref(s2),
+                                    C.byref(dist), C.byref(it), C.byref(st))
+    return dict(status=st.value, error=last_error() if st.value else "", partition=part[:ns], v=v[:ns], center=center[:2 * m],
+                size1=s1.value, size2=s2.value, dist=dist.value, iter=it.value, needed=[l.value for l in lens])
+
+
+def dclust_ex(p, i, x, m, n, *, min_samples, min_dist=0.0, max_iter=100, tol=1e-5, nonneg=True, seed=0.0, centers=True,
+              cluster_cap=None, node_cap=None):
+    """Build-defined dclust.  Without capacities the call is made with room for every tree the parameters allow: each cluster but
+    a lone root holds at least min_samples samples, so there are at most max(1, n // min_samples) clusters and twice as many
+    nodes.  Returns dict(status, error, assignments, size, radius, node, center (clusters x m or
+    None), parent, bit, iter (per node), ids (binary path strings), clusters, nodes)."""
+    p, i, x = _csc_args(p, i, x)
+    bound = max(1, n // max(int(min_samples), 1))
+    ccap = bound if cluster_cap is None else int(cluster_cap)
+    ncap = 2 * bound if node_cap is None else int(node_cap)
+    asg = np.zeros(n, np.int32)
+    size = np.zeros(max(ccap, 1), np.int32)
+    radius = np.zeros(max(ccap, 1), np.float64)
+    node = np.zeros(max(ccap, 1), np.int32)
+    center = np.zeros((max(ccap, 1), m), np.float64) if centers else None
+    parent = np.zeros(max(ncap, 1), np.int32)
+    bit = np.zeros(max(ncap, 1), np.int32)
+    niter = np.zeros(max(ncap, 1), np.int32)
+    cc, nc, st = C.c_int(ccap), C.c_int(ncap), C.c_int(-99)
+    lib().rcppml_gpu_dclust_ex(_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0]), _ci(min_samples), _cd(min_dist),
+                               _ci(max_iter), _cd(tol), _ci(1 if nonneg else 0), _cd(seed), _np_ptr(asg), C.byref(cc), _np_ptr(size),
+                               _np_ptr(radius), _np_ptr(node), _np_ptr(center) if centers else None, C.byref(nc), _np_ptr(parent),
+                               _np_ptr(bit), _np_ptr(niter), C.byref(st))
+    out = dict(status=st.value, error=last_error() if st.value else "", clusters=cc.value, nodes=nc.value, assignments=asg)
+    if st.value != 0:
+        return out
+    L, N = cc.value, nc.value
+    parent, bit = parent[:N], bit[:N]
+    paths = [""] * N
+    for k in range(1, N):                 # children are appended after their parent: one pass in node order
+        paths[k] = paths[parent[k]] + str(int(bit[k]))
+    out.update(size=size[:L], radius=radius[:L], node=node[:L], center=center[:L] if centers else None, parent=parent, bit=bit,
+               iter=niter[:N], ids=[paths[node[c]] for c in range(L)])
+    return out
