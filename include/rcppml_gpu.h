@@ -279,6 +279,63 @@ RCPPML_GPU_API void rcppml_gpu_dclust_ex(const int* col_ptr, const int* row_idx,
                                          double* out_center, int* node_cap, int* node_parent, int* node_bit, int* node_iter,
                                          int* out_status);
 
+/* Truncated SVD / PCA (rcppml_amd/csrc/ops_svd.hip): the reference plugin's four entries with its pointer lists
+ * (src/gpu_bridge_svd.cu:53, 220, 392, 555) -- 61 pointers for the sparse CSC forms, 58 for the column-major dense forms.  The
+ * _float forms take doubles, compute in fp32 on the device and write doubles back.  Outputs in the R wrapper's layout
+ * (R/gpu_backend.R:295-420): U m x k_max and V n x k_max column-major with the first *out_k_selected columns written, d, out_iters_per_
+ * factor (deflation: one count per factor; Lanczos: the number of steps in entry 0), out_frobenius_norm_sq (of the centered matrix
+ * when *center), out_row_means (m, when *center), out_wall_time_ms.  out_test_loss is not written.
+ *   *algorithm 0: deflation, the reference's CPU deflation_svd (svd/deflation.hpp:600-915) restated.
+ *   *algorithm 1-4 (irlba, lanczos, randomized, krylov) without element constraints: Golub-Kahan-Lanczos with full two-pass
+ *     reorthogonalisation (svd/lanczos.hpp); with *k_max = min(m, n) it may take min(m, n) steps instead of min(m, n) - 1.
+ * Refused with *out_status = -1 (rcppml_gpu_last_error), outputs untouched: *test_fraction > 0, an obs_mask, a graph with lambda > 0,
+ * L21, angular, *robust_delta > 0, element constraints (L1 / L2 / nonneg / upper bound) with *algorithm != 0, *k_max outside
+ * [1, min(m, n)], *algorithm outside [0, 4], deflation with *max_iter < 1, a malformed CSC, no device. */
+RCPPML_GPU_API void rcppml_gpu_svd_pca_double(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+        int* k_max, double* U, double* d, double* V, double* tol, int* max_iter,
+        int* center, int* verbose, int* seed, int* threads, double* L1_u, double* L1_v, double* L2_u, double* L2_v, int* nonneg_u,
+        int* nonneg_v, double* ub_u, double* ub_v, double* L21_u, double* L21_v, double* angular_u, double* angular_v,
+        double* test_fraction, int* cv_seed, int* patience, int* mask_zeros, int* algorithm, const int* graph_u_p,
+        const int* graph_u_i, const double* graph_u_x, int* graph_u_dim, int* graph_u_nnz, double* graph_u_lambda_val,
+        const int* graph_v_p, const int* graph_v_i, const double* graph_v_x, int* graph_v_dim, int* graph_v_nnz,
+        double* graph_v_lambda_val, const int* obs_mask_p, const int* obs_mask_i, const double* obs_mask_x, int* obs_mask_rows,
+        int* obs_mask_cols, int* obs_mask_nnz, int* out_k_selected, double* out_wall_time_ms, double* out_test_loss,
+        int* out_iters_per_factor, double* out_frobenius_norm_sq, double* out_row_means, double* robust_delta, int* irls_max_iter,
+        double* irls_tol, int* out_status);
+RCPPML_GPU_API void rcppml_gpu_svd_pca_float(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+        int* k_max, double* U, double* d, double* V, double* tol, int* max_iter,
+        int* center, int* verbose, int* seed, int* threads, double* L1_u, double* L1_v, double* L2_u, double* L2_v, int* nonneg_u,
+        int* nonneg_v, double* ub_u, double* ub_v, double* L21_u, double* L21_v, double* angular_u, double* angular_v,
+        double* test_fraction, int* cv_seed, int* patience, int* mask_zeros, int* algorithm, const int* graph_u_p,
+        const int* graph_u_i, const double* graph_u_x, int* graph_u_dim, int* graph_u_nnz, double* graph_u_lambda_val,
+        const int* graph_v_p, const int* graph_v_i, const double* graph_v_x, int* graph_v_dim, int* graph_v_nnz,
+        double* graph_v_lambda_val, const int* obs_mask_p, const int* obs_mask_i, const double* obs_mask_x, int* obs_mask_rows,
+        int* obs_mask_cols, int* obs_mask_nnz, int* out_k_selected, double* out_wall_time_ms, double* out_test_loss,
+        int* out_iters_per_factor, double* out_frobenius_norm_sq, double* out_row_means, double* robust_delta, int* irls_max_iter,
+        double* irls_tol, int* out_status);
+RCPPML_GPU_API void rcppml_gpu_svd_pca_dense_double(const double* A_data, int* m, int* n,
+        int* k_max, double* U, double* d, double* V, double* tol, int* max_iter,
+        int* center, int* verbose, int* seed, int* threads, double* L1_u, double* L1_v, double* L2_u, double* L2_v, int* nonneg_u,
+        int* nonneg_v, double* ub_u, double* ub_v, double* L21_u, double* L21_v, double* angular_u, double* angular_v,
+        double* test_fraction, int* cv_seed, int* patience, int* mask_zeros, int* algorithm, const int* graph_u_p,
+        const int* graph_u_i, const double* graph_u_x, int* graph_u_dim, int* graph_u_nnz, double* graph_u_lambda_val,
+        const int* graph_v_p, const int* graph_v_i, const double* graph_v_x, int* graph_v_dim, int* graph_v_nnz,
+        double* graph_v_lambda_val, const int* obs_mask_p, const int* obs_mask_i, const double* obs_mask_x, int* obs_mask_rows,
+        int* obs_mask_cols, int* obs_mask_nnz, int* out_k_selected, double* out_wall_time_ms, double* out_test_loss,
+        int* out_iters_per_factor, double* out_frobenius_norm_sq, double* out_row_means, double* robust_delta, int* irls_max_iter,
+        double* irls_tol, int* out_status);
+RCPPML_GPU_API void rcppml_gpu_svd_pca_dense_float(const double* A_data, int* m, int* n,
+        int* k_max, double* U, double* d, double* V, double* tol, int* max_iter,
+        int* center, int* verbose, int* seed, int* threads, double* L1_u, double* L1_v, double* L2_u, double* L2_v, int* nonneg_u,
+        int* nonneg_v, double* ub_u, double* ub_v, double* L21_u, double* L21_v, double* angular_u, double* angular_v,
+        double* test_fraction, int* cv_seed, int* patience, int* mask_zeros, int* algorithm, const int* graph_u_p,
+        const int* graph_u_i, const double* graph_u_x, int* graph_u_dim, int* graph_u_nnz, double* graph_u_lambda_val,
+        const int* graph_v_p, const int* graph_v_i, const double* graph_v_x, int* graph_v_dim, int* graph_v_nnz,
+        double* graph_v_lambda_val, const int* obs_mask_p, const int* obs_mask_i, const double* obs_mask_x, int* obs_mask_rows,
+        int* obs_mask_cols, int* obs_mask_nnz, int* out_k_selected, double* out_wall_time_ms, double* out_test_loss,
+        int* out_iters_per_factor, double* out_frobenius_norm_sq, double* out_row_means, double* robust_delta, int* irls_max_iter,
+        double* irls_tol, int* out_status);
+
 /* Last error text of the calling thread ("" if none). */
 RCPPML_GPU_API const char* rcppml_gpu_last_error(void);
 

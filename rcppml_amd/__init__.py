@@ -5,6 +5,7 @@ Layout (only what the path needs):
   _abi.py    ctypes binding of that C-ABI (no CPU fallback: fails loudly if the library is missing)
   nmf.py     host-side mirror of the reference R surface: nmf() / nnls() / predict() / evaluate()
   cluster.py bipartition() / dclust(): mirror of the R surface on the HIP clustering path (csrc/ops_cluster.hip)
+  svd.py     svd() / pca(): mirror of the R surface on the HIP truncated-SVD path (csrc/ops_svd.hip)
   als.py     one-process-per-GPU column-sharded ALS loop over torch.distributed (RCCL): Comm, ShardedALS, HipOps
   data.py    synthetic inputs (restatement of R/simulateNMF.R) and CSC helpers
 """

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_hip_scale_order", "rcppml_hip_gram_loss_mse", "rcppml_hip_tail_scale_gram", "rcppml_hip_tail_scale_gram_loss",
     "rcppml_hip_als_small_eligible", "rcppml_hip_als_small_fit",
     "rcppml_gpu_bipartition_double", "rcppml_gpu_dclust_double", "rcppml_gpu_bipartition_ex", "rcppml_gpu_dclust_ex",
+    "rcppml_gpu_svd_pca_double", "rcppml_gpu_svd_pca_float", "rcppml_gpu_svd_pca_dense_double", "rcppml_gpu_svd_pca_dense_float",
 ]
 
 
@@ -817,3 +818,60 @@ def dclust_ex(p, i, x, m, n, *, min_samples, min_dist=0.0, max_iter=100, tol=1e-
     out.update(size=size[:L], radius=radius[:L], node=node[:L], center=center[:L] if centers else None, parent=parent, bit=bit,
                iter=niter[:N], ids=[paths[node[c]] for c in range(L)])
     return out
+
+
+# ----------------------------------------------------------------------------- truncated SVD / PCA (ops_svd.hip)
+SVD_ALGORITHMS = {"deflation": 0, "irlba": 1, "lanczos": 2, "randomized": 3, "krylov": 4}
+
+
+def svd_pca(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=200, center=False, seed=0, L1=(0.0, 0.0),
+            L2=(0.0, 0.0), nonneg=(False, False), upper_bound=(0.0, 0.0), L21=(0.0, 0.0), angular=(0.0, 0.0), test_fraction=0.0,
+            algorithm=0, graph_u=None, graph_v=None, obs_mask=None, robust_delta=0.0, buffers=None):
+    """One of the four R-shaped entries (reference src/gpu_bridge_svd.cu), with the arguments laid out as R's .gpu_svd_pca /
+    .gpu_svd_pca_dense pass them (R/gpu_backend.R:295-420).  A: (p, i, x, m, n) CSC parts, or a column-major (m, n) array with
+    dense=True.  graph_u / graph_v: (p, i, x, dim, lambda); obs_mask: (p, i, x, rows, cols).  buffers: dict of preallocated outputs
+    (tests watch what is left untouched).  Returns dict(status, error, U (m x k_max), d, V (n x k_max), k, iters, frob, row_means,
+    wall_ms, test_loss)."""
+    if dense:
+        Ad = np.asfortranarray(np.asarray(A, np.float64))
+        m, n = Ad.shape
+        head = [_np_ptr(Ad.ravel(order="F")), _ci(m), _ci(n)]
+        keep = [Ad]
+    else:
+        p, i, x, m, n = A
+        p, i, x = _csc_args(p, i, x)
+        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0])]
+        keep = [p, i, x]
+    b = dict(U=np.zeros(m * k_max), d=np.zeros(k_max), V=np.zeros(n * k_max), test_loss=np.zeros(k_max),
+             iters=np.zeros(k_max, np.int32), row_means=np.zeros(m))
+    if buffers:
+        b.update(buffers)
+
+    def graph(g):
+        if g is None:
+            return [_np_ptr(np.zeros(1, np.int32)), _np_ptr(np.zeros(1, np.int32)), _np_ptr(np.zeros(1)), _ci(0), _ci(0), _cd(0.0)]
+        gp, gi, gx, dim, lam = g
+        gp, gi, gx = _csc_args(gp, gi, gx)
+        keep.extend([gp, gi, gx])
+        return [_np_ptr(gp), _np_ptr(gi), _np_ptr(gx), _ci(dim), _ci(gx.shape[0]), _cd(lam)]
+
+    if obs_mask is None:
+        om = [_np_ptr(np.zeros(1, np.int32)), _np_ptr(np.zeros(1, np.int32)), _np_ptr(np.zeros(1)), _ci(0), _ci(0), _ci(0)]
+    else:
+        op_, oi, ox, rows, cols = obs_mask
+        op_, oi, ox = _csc_args(op_, oi, ox)
+        keep.extend([op_, oi, ox])
+        om = [_np_ptr(op_), _np_ptr(oi), _np_ptr(ox), _ci(rows), _ci(cols), _ci(ox.shape[0])]
+    ksel, wall, frob, st = C.c_int(0), C.c_double(0.0), C.c_double(0.0), C.c_int(-99)
+    args = head + [_ci(k_max), _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]), _cd(tol), _ci(max_iter), _ci(int(bool(center))),
+                   _ci(0), _ci(seed), _ci(0), _cd(L1[0]), _cd(L1[1]), _cd(L2[0]), _cd(L2[1]), _ci(int(bool(nonneg[0]))),
+                   _ci(int(bool(nonneg[1]))), _cd(upper_bound[0]), _cd(upper_bound[1]), _cd(L21[0]), _cd(L21[1]), _cd(angular[0]),
+                   _cd(angular[1]), _cd(test_fraction), _ci(0), _ci(5), _ci(0), _ci(algorithm)] + graph(graph_u) + graph(graph_v) + om + [
+                   C.byref(ksel), C.byref(wall), _np_ptr(b["test_loss"]), _np_ptr(b["iters"]), C.byref(frob), _np_ptr(b["row_means"]),
+                   _cd(robust_delta), _ci(5), _cd(1e-4), C.byref(st)]
+    assert len(args) == (58 if dense else 61)
+    name = "rcppml_gpu_svd_pca_" + ("dense_" if dense else "") + ("float" if precision == "float" else "double")
+    getattr(lib(), name)(*args)
+    return dict(status=st.value, error=last_error() if st.value else "", U=b["U"][:m * k_max].reshape(max(k_max, 0), m).T,
+                V=b["V"][:n * k_max].reshape(max(k_max, 0), n).T, d=b["d"], k=ksel.value, iters=b["iters"], frob=frob.value, row_means=b["row_means"],
+                wall_ms=wall.value, test_loss=b["test_loss"], buffers=b)

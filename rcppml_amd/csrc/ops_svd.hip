@@ -1,0 +1,595 @@
+// ops_svd.hip -- truncated SVD / PCA on the device (kernels: kernels_svd.hip.h) and the reference plugin's four entries
+// rcppml_gpu_svd_pca_{double,float} (sparse CSC) and rcppml_gpu_svd_pca_dense_{double,float} (column-major dense), with the
+// reference's pointer lists (src/gpu_bridge_svd.cu:53, 220, 392, 555) and the buffers R allocates (R/gpu_backend.R:295-420).
+//
+// algorithm 0: deflation, the reference's CPU deflation_svd (inst/include/FactorNet/svd/deflation.hpp:600-915) restated: SplitMix64
+//   start (seed 0 -> 42), power-step warm start of later factors, Nesterov momentum, adaptive tol_k, L2 -> L1 -> nonneg -> upper
+//   bound, two-pass Gram-Schmidt after each factor and a Rayleigh-quotient sigma, early stop when sigma ~ 0.  One iteration is five
+//   launches (A'u, the v epilogue, A v, the u epilogue, the finish) with no host synchronisation; a converged factor freezes on the
+//   device at the CPU's iteration and the host polls one flag every kPoll iterations.
+// algorithms 1-4 without element constraints: Golub-Kahan-Lanczos with full two-pass reorthogonalisation (svd/lanczos.hpp); the
+//   small bidiagonal problem is solved on the host in fp64.
+// Anything else is refused (status -1, reason in rcppml_gpu_last_error, no output written).
+//
+// Centering never densifies: A'u - (mu . u) 1 and A v - mu sum(v) are scalar corrections inside the epilogues.
+#include "plugin_common.hip.h"
+#include "kernels_svd.hip.h"
+
+#include <chrono>
+#include <climits>
+#include <limits>
+
+namespace {
+using namespace rcppml_plugin;
+using namespace rsv;
+
+constexpr int kPoll = 8;
+
+int nblk(long len) { return (int)((len + CH - 1) / CH); }
+int wblk(long len) { return (int)((len + NW - 1) / NW); }
+
+template <class T> T* grow(DevBuf& b, size_t count) {
+    if (b.bytes < count * sizeof(T) || !b.p) b.alloc(count * sizeof(T));
+    return b.as<T>();
+}
+
+// SplitMix64 uniform<S>() draws (rng/rng.hpp:89-104): draw `off` .. off + count - 1 of the stream of `seed`
+template <class S> std::vector<S> splitmix(uint64_t seed, uint64_t off, size_t count) {
+    std::vector<S> out(count);
+    uint64_t state = seed + off * 0x9e3779b97f4a7c15ull;
+    for (auto& x : out) {
+        state += 0x9e3779b97f4a7c15ull;
+        uint64_t z = state;
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        z = z ^ (z >> 31);
+        x = static_cast<S>(z) / static_cast<S>(UINT64_MAX);
+    }
+    return out;
+}
+
+struct Opts {
+    int m, n, k;
+    int64_t nnz;
+    const int* p = nullptr; const int* i = nullptr; const double* x = nullptr;   // sparse CSC
+    const double* dense = nullptr;                                              // or column-major dense
+    double tol; int max_iter; int center; unsigned seed; int algorithm;
+    double L1_u, L1_v, L2_u, L2_v, ub_u, ub_v; int nonneg_u, nonneg_v;
+};
+
+struct Result {
+    std::vector<double> U, V, d, row_means;
+    std::vector<int> iters;
+    int k_sel = 0;
+    double frob = 0;
+};
+
+bool has_constraints(const Opts& o) {
+    return o.L1_u != 0 || o.L1_v != 0 || o.L2_u != 0 || o.L2_v != 0 || o.nonneg_u || o.nonneg_v || o.ub_u != 0 || o.ub_v != 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ host eigen
+// Eigenvalues (d, ascending after sorting by the caller) and eigenvector rows of a symmetric tridiagonal matrix (diagonal d[0..n),
+// off-diagonal e[1..n)) by implicit QL with shifts.  Z: zr rows x n, row-major, initialised by the caller (rows of the identity);
+// every rotation is applied to those rows only, so tracking one row costs O(n^2) and all rows O(n^3).
+void tql(std::vector<double>& d, std::vector<double> e, int n, std::vector<double>& Z, int zr) {
+    for (int i = 1; i < n; ++i) e[i - 1] = e[i];
+    if (n > 0) e[n - 1] = 0.0;
+    for (int l = 0; l < n; ++l) {
+        int iter = 0, mm;
+        do {
+            for (mm = l; mm < n - 1; ++mm) {
+                const double dd = std::fabs(d[mm]) + std::fabs(d[mm + 1]);
+                if (std::fabs(e[mm]) <= std::numeric_limits<double>::epsilon() * dd) break;
+            }
+            if (mm != l) {
+                if (++iter > 60) throw std::runtime_error("tridiagonal eigensolver did not converge");
+                double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
+                double r = std::hypot(g, 1.0);
+                g = d[mm] - d[l] + e[l] / (g + (g >= 0 ? std::fabs(r) : -std::fabs(r)));
+                double s = 1.0, c = 1.0, p = 0.0;
+                int i;
+                for (i = mm - 1; i >= l; --i) {
+                    double f = s * e[i], b = c * e[i];
+                    e[i + 1] = (r = std::hypot(f, g));
+                    if (r == 0.0) { d[i + 1] -= p; e[mm] = 0.0; break; }
+                    s = f / r; c = g / r;
+                    g = d[i + 1] - p;
+                    r = (d[i] - g) * s + 2.0 * c * b;
+                    d[i + 1] = g + (p = s * r);
+                    g = c * r - b;
+                    for (int z = 0; z < zr; ++z) {
+                        double* row = &Z[(size_t)z * n];
+                        f = row[i + 1];
+                        row[i + 1] = s * row[i] + c * f;
+                        row[i] = c * row[i] - s * f;
+                    }
+                }
+                if (r == 0.0 && i >= l) continue;
+                d[l] -= p; e[l] = g; e[mm] = 0.0;
+            }
+        } while (mm != l);
+    }
+}
+
+// SVD of the upper bidiagonal B (alpha on the diagonal, beta[1..ja) above it) through the eigenproblem of B'B:
+// sigma descending, right vectors Vb (ja x ja, column-major), left vectors Ub = B Vb / sigma (zero columns for sigma = 0).
+// rows_only: only the last row of Ub is wanted (the Ritz residual check): Vb is tracked in its last row only.
+void bidiag_svd(const std::vector<double>& a, const std::vector<double>& b, int ja, std::vector<double>& sig, std::vector<double>& Ub,
+                std::vector<double>& Vb, bool last_row_only) {
+    std::vector<double> dd(ja), ee(ja, 0.0);
+    for (int l = 0; l < ja; ++l) {
+        dd[l] = a[l] * a[l] + (l > 0 ? b[l] * b[l] : 0.0);
+        if (l > 0) ee[l] = a[l - 1] * b[l];
+    }
+    const int zr = last_row_only ? 1 : ja;
+    std::vector<double> Z((size_t)zr * ja, 0.0);
+    for (int z = 0; z < zr; ++z) Z[(size_t)z * ja + (last_row_only ? ja - 1 : z)] = 1.0;
+    tql(dd, ee, ja, Z, zr);
+    std::vector<int> ord(ja);
+    std::iota(ord.begin(), ord.end(), 0);
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return dd[x] > dd[y]; });
+    sig.assign(ja, 0.0);
+    for (int c = 0; c < ja; ++c) sig[c] = std::sqrt(std::max(dd[ord[c]], 0.0));
+    if (last_row_only) {                 // Ub(ja-1, c) = alpha_{ja-1} Vb(ja-1, c) / sigma_c  (the last row of B holds alpha only)
+        Ub.assign(ja, 0.0);
+        for (int c = 0; c < ja; ++c) Ub[c] = sig[c] > 0 ? a[ja - 1] * Z[ord[c]] / sig[c] : 0.0;
+        return;
+    }
+    Vb.assign((size_t)ja * ja, 0.0);
+    Ub.assign((size_t)ja * ja, 0.0);
+    for (int c = 0; c < ja; ++c)
+        for (int l = 0; l < ja; ++l) Vb[(size_t)c * ja + l] = Z[(size_t)l * ja + ord[c]];
+    for (int c = 0; c < ja; ++c) {
+        if (!(sig[c] > 0)) continue;
+        const double* v = &Vb[(size_t)c * ja];
+        for (int l = 0; l < ja; ++l) Ub[(size_t)c * ja + l] = (a[l] * v[l] + (l + 1 < ja ? b[l + 1] * v[l + 1] : 0.0)) / sig[c];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ engine
+template <class T> struct Engine {
+    const Opts& o;
+    CtxGuard g;
+    hipStream_t s;
+    int m, n;
+    DevBuf Ap, Ai, Ax, Tp, Ti, Tx, Ad, mu;
+    std::vector<double> mu_h;
+
+    Engine(const Opts& o_) : o(o_), g(env_device()), s(g.s), m(o_.m), n(o_.n) {
+        mu_h.assign(m, 0.0);
+        if (o.dense) {
+            upload_cast<T>(g.c, o.dense, (size_t)m * n, Ad, s);
+            for (int j = 0; j < n; ++j)
+                for (int i = 0; i < m; ++i) mu_h[i] += o.dense[(size_t)j * m + i];
+        } else {
+            const size_t nz = (size_t)std::max<int64_t>(o.nnz, 1);
+            upload_ints(o.p, (size_t)n + 1, Ap, s);
+            upload_ints(o.i, nz, Ai, s);
+            upload_cast<T>(g.c, o.x, nz, Ax, s);
+            grow<int>(Tp, (size_t)m + 1);
+            grow<int>(Ti, nz);
+            grow<T>(Tx, nz);
+            OPCHK(rcppml_hip_transpose_csc(g.c, DT<T>::id, m, n, Ap.as<int>(), Ai.as<int>(), Ax.p, Tp.as<int>(), Ti.as<int>(), Tx.p));
+            for (int64_t e = 0; e < o.nnz; ++e) mu_h[o.i[e]] += o.x[e];
+        }
+        for (auto& v : mu_h) v /= (double)n;
+        if (o.center) {
+            std::vector<double> tmp(mu_h);
+            upload_cast<T>(g.c, tmp.data(), (size_t)m, mu, s);
+        }
+    }
+    const T* mup() const { return o.center ? mu.as<T>() : nullptr; }
+    // y = A' x (n);  brk: a state word that skips the launch when set (0: none)
+    void at(const T* x, T* y, const int* st, int it, int brk) {
+        if (o.dense)
+            hipLaunchKernelGGL(spmv_t_dense<T>, dim3(wblk(n)), dim3(WG), 0, s, Ad.as<T>(), m, n, x, y, st, it, brk);
+        else
+            hipLaunchKernelGGL(spmv_t_csc<T>, dim3(wblk(n)), dim3(WG), 0, s, Ap.as<int>(), Ai.as<int>(), Ax.as<T>(), n, x, y, st, it, brk);
+    }
+    // y = A x (m)
+    void ax(const T* x, T* y, const int* st, int it, int brk) {
+        if (o.dense)
+            hipLaunchKernelGGL(spmv_dense<T>, dim3((m + WG - 1) / WG), dim3(WG), 0, s, Ad.as<T>(), m, n, x, y, st, it, brk);
+        else
+            hipLaunchKernelGGL(spmv_csr<T>, dim3(wblk(m)), dim3(WG), 0, s, Tp.as<int>(), Ti.as<int>(), Tx.as<T>(), m, x, y, st, it, brk);
+    }
+    void dots(const T* x, long len, const Cols<T>& C, T* P) {
+        hipLaunchKernelGGL(dots_kernel<T>, dim3(nblk(len)), dim3(WG), 0, s, x, len, C, P);
+    }
+    template <class X> std::vector<X> read(const void* src, size_t count) {
+        std::vector<X> h(count);
+        HIPCHK(hipMemcpyAsync(h.data(), src, count * sizeof(X), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return h;
+    }
+
+    // -------------------------------------------------------------------------------------------------------- deflation
+    void deflation(Result& R) {
+        const int K = o.k, nbm = nblk(m), nbn = nblk(n);
+        const T eps100 = std::numeric_limits<T>::epsilon() * T(100);
+        const T l1u = (T)o.L1_u, l1v = (T)o.L1_v, l2u = (T)o.L2_u, l2v = (T)o.L2_v, ubu = (T)o.ub_u, ubv = (T)o.ub_v;
+        DevBuf dU, dV, dd, uraw, uhat, vraw, y, t, Pm, Pn, Pu, st, nrm;
+        T* U = grow<T>(dU, (size_t)m * K);
+        T* V = grow<T>(dV, (size_t)n * K);
+        T* d = grow<T>(dd, K);
+        grow<T>(uraw, m); grow<T>(uhat, m); grow<T>(vraw, n); grow<T>(y, n); grow<T>(t, m);
+        grow<T>(Pm, (size_t)nbm * (K + 2)); grow<T>(Pn, (size_t)nbn * (K + 2)); grow<T>(Pu, (size_t)nbm * 2);
+        int* S = grow<int>(st, S_WORDS);
+        T* dn = grow<T>(nrm, 1);
+        HIPCHK(hipMemsetAsync(U, 0, (size_t)m * K * sizeof(T), s));
+        HIPCHK(hipMemsetAsync(V, 0, (size_t)n * K * sizeof(T), s));
+        HIPCHK(hipMemsetAsync(d, 0, (size_t)K * sizeof(T), s));
+        const uint64_t seed = o.seed == 0 ? 42ull : (uint64_t)o.seed;
+        uint64_t drawn = 0;
+        std::vector<T> dh(K, T(0));
+        const int init[S_WORDS] = {INT_MAX, 0, 0, 0, 0, 0, 0, 0};
+        auto random_u = [&](T* u) {        // the next m uniform<double>() draws, cast to the working precision
+            const std::vector<double> r = splitmix<double>(seed, drawn, (size_t)m);
+            drawn += m;
+            std::vector<T> rt(r.begin(), r.end());
+            HIPCHK(hipMemcpyAsync(u, rt.data(), (size_t)m * sizeof(T), hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));
+        };
+        R.iters.clear();
+        int k = 0;
+        for (; k < K; ++k) {
+            T* u = U + (size_t)k * m;
+            T* v = V + (size_t)k * n;
+            Cols<T> Cm;                                         // m side: [U_k' x, mu . x (or sum), |x|^2]
+            Cm.X = U; Cm.ld = m; Cm.nx = k; Cm.e[0] = mup(); Cm.ne = 2;
+            Cols<T> Cn;                                         // n side: [V_k' x, sum x, |x|^2]
+            Cn.X = V; Cn.ld = n; Cn.nx = k; Cn.e[0] = nullptr; Cn.ne = 2;
+            // ---- start vector
+            bool rnd = k == 0;
+            if (k > 0) {
+                HIPCHK(hipMemcpyAsync(u, U + (size_t)(k - 1) * m, (size_t)m * sizeof(T), hipMemcpyDeviceToDevice, s));
+                hipLaunchKernelGGL(gs_kernel<T>, dim3(1), dim3(WG), 0, s, u, (long)m, (const T*)U, k, 1, eps100, dn);
+                const T ni = read<T>(dn, 1)[0];
+                if (ni > eps100) {                              // power step: v = normalise(R' u), u = R v, MGS
+                    Cm.e[1] = u;
+                    dots(u, m, Cm, Pm.as<T>());
+                    at(u, y.as<T>(), nullptr, 0, 0);
+                    hipLaunchKernelGGL(defl_v_kernel<T>, dim3(nbn), dim3(WG), 0, s, (const T*)y.as<T>(), n, (const T*)V, k, (const T*)d,
+                                       (const T*)Pm.as<T>(), nbm, o.center, T(0), T(0), 0, T(0), (int)M_WARM, vraw.as<T>(),
+                                       Pn.as<T>(), (int*)nullptr, 0);
+                    ax(vraw.as<T>(), t.as<T>(), nullptr, 0, 0);
+                    hipLaunchKernelGGL(defl_u_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)t.as<T>(), m, (const T*)U, k, (const T*)d,
+                                       (const T*)Pn.as<T>(), nbn, mup(), T(0), T(0), 0, T(0), (int)M_WARM, (const T*)vraw.as<T>(), v, n,
+                                       u, (const T*)nullptr, Pu.as<T>(), (int*)nullptr, 0);
+                    hipLaunchKernelGGL(gs_kernel<T>, dim3(1), dim3(WG), 0, s, u, (long)m, (const T*)U, k, 1, T(0), (T*)nullptr);
+                } else {
+                    rnd = true;
+                }
+            }
+            if (rnd) {
+                random_u(u);
+                hipLaunchKernelGGL(gs_kernel<T>, dim3(1), dim3(WG), 0, s, u, (long)m, (const T*)nullptr, 0, 1, T(0), (T*)nullptr);
+            }
+            // ---- adaptive tolerance
+            T tol_k = (T)o.tol;
+            if (k > 0 && dh[0] > 0 && dh[k - 1] > 0) tol_k = std::min((T)o.tol * dh[0] / dh[k - 1], (T)o.tol * T(100));
+            // ---- ALS iterations
+            HIPCHK(hipMemcpyAsync(uhat.p, u, (size_t)m * sizeof(T), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(S, init, sizeof(init), hipMemcpyHostToDevice, s));
+            Cm.e[1] = uhat.as<T>();
+            dots(uhat.as<T>(), m, Cm, Pm.as<T>());
+            for (int done = 0; done < o.max_iter;) {
+                const int P = std::min(kPoll, o.max_iter - done);
+                for (int q = 0; q < P; ++q) {
+                    const int it = done + q;
+                    at(uhat.as<T>(), y.as<T>(), S, it, 0);
+                    hipLaunchKernelGGL(defl_v_kernel<T>, dim3(nbn), dim3(WG), 0, s, (const T*)y.as<T>(), n, (const T*)V, k, (const T*)d,
+                                       (const T*)Pm.as<T>(), nbm, o.center, l1v, l2v, o.nonneg_v, ubv, (int)M_LOOP, vraw.as<T>(),
+                                       Pn.as<T>(), S, it);
+                    ax(vraw.as<T>(), t.as<T>(), S, it, S_BRKV);
+                    hipLaunchKernelGGL(defl_u_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)t.as<T>(), m, (const T*)U, k, (const T*)d,
+                                       (const T*)Pn.as<T>(), nbn, mup(), l1u, l2u, o.nonneg_u, ubu, (int)M_LOOP, (const T*)vraw.as<T>(),
+                                       v, n, uraw.as<T>(), (const T*)u, Pu.as<T>(), S, it);
+                    hipLaunchKernelGGL(defl_finish_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)uraw.as<T>(), u, uhat.as<T>(), m,
+                                       (const T*)Pu.as<T>(), nbm, (const T*)U, k, mup(), Pm.as<T>(), tol_k, S, it);
+                }
+                HIPCHK(hipGetLastError());
+                done += P;
+                if (read<int>(S + S_STOP, 1)[0] <= done) break;
+            }
+            const int iters = read<int>(S + S_ITERS, 1)[0];
+            R.iters.push_back(iters);
+            // ---- two-pass Gram-Schmidt against the earlier factors, then the Rayleigh quotient
+            if (k > 0) {
+                hipLaunchKernelGGL(gs_kernel<T>, dim3(1), dim3(WG), 0, s, u, (long)m, (const T*)U, k, 0, eps100, (T*)nullptr);
+                hipLaunchKernelGGL(gs_kernel<T>, dim3(1), dim3(WG), 0, s, v, (long)n, (const T*)V, k, 0, eps100, (T*)nullptr);
+            }
+            Cn.e[1] = v;
+            dots(v, n, Cn, Pn.as<T>());
+            ax(v, t.as<T>(), nullptr, 0, 0);
+            hipLaunchKernelGGL(defl_u_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)t.as<T>(), m, (const T*)U, k, (const T*)d,
+                               (const T*)Pn.as<T>(), nbn, mup(), T(0), T(0), 0, T(0), (int)M_PLAIN, (const T*)v, (T*)nullptr, n,
+                               uraw.as<T>(), (const T*)u, Pu.as<T>(), (int*)nullptr, 0);
+            HIPCHK(hipGetLastError());
+            const std::vector<T> pu = read<T>(Pu.p, (size_t)nbm * 2);
+            T sg = 0;
+            for (int b = 0; b < nbm; ++b) sg += pu[(size_t)b * 2 + 1];
+            if (sg < 0) sg = -sg;
+            dh[k] = sg;
+            HIPCHK(hipMemcpyAsync(d + k, &dh[k], sizeof(T), hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (sg < eps100) { ++k; break; }
+        }
+        R.k_sel = std::min(k, K);
+        R.U.resize((size_t)m * R.k_sel);
+        R.V.resize((size_t)n * R.k_sel);
+        download_cast<T>(g.c, dU, (size_t)m * R.k_sel, R.U.data(), s);
+        download_cast<T>(g.c, dV, (size_t)n * R.k_sel, R.V.data(), s);
+        R.d.assign(dh.begin(), dh.begin() + R.k_sel);
+    }
+
+    // -------------------------------------------------------------------------------------------------------- Lanczos
+    void lanczos(Result& R) {
+        const int K = o.k, mn = std::min(m, n);
+        // svd/lanczos.hpp: jmax = min(min(m, n) - 1, max(3k, k + 50, max_iter)); k = min(m, n) may use all min(m, n) steps
+        const int cap = K >= mn ? mn : mn - 1;
+        const int jmax = std::min(cap, std::max(std::max(3 * K, K + 50), o.max_iter > 0 ? o.max_iter : 0));
+        if (jmax + 1 > NPMAX) throw std::invalid_argument("Lanczos would need more than " + std::to_string(NPMAX - 1) + " steps");
+        const int nbm = nblk(m), nbn = nblk(n);
+        const T eps = std::numeric_limits<T>::epsilon() * T(100);
+        const double conv_tol = o.tol > 0 ? o.tol : 1e-10;
+        DevBuf dP, dQ, dal, dbe, r, sv, y, t, Pa, Pb, Pc, st;
+        T* Pm = grow<T>(dP, (size_t)n * (jmax + 1));
+        T* Q = grow<T>(dQ, (size_t)m * std::max(jmax, 1));
+        T* al = grow<T>(dal, (size_t)jmax + 1);
+        T* be = grow<T>(dbe, (size_t)jmax + 1);
+        grow<T>(r, m); grow<T>(sv, n); grow<T>(y, n); grow<T>(t, m);
+        const size_t pcap = (size_t)std::max(nbm, nbn) * (jmax + 2);
+        grow<T>(Pa, pcap); grow<T>(Pb, pcap); grow<T>(Pc, pcap);
+        int* S = grow<int>(st, S_WORDS);
+        const int init[S_WORDS] = {INT_MAX, 0, 0, 0, 0, 0, 0, 0};
+        HIPCHK(hipMemcpyAsync(S, init, sizeof(init), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(be, 0, ((size_t)jmax + 1) * sizeof(T), s));
+        {   // p0 = normalise(uniform<Scalar>() - 0.5)
+            std::vector<T> p0 = splitmix<T>(o.seed == 0 ? 42ull : (uint64_t)o.seed, 0, (size_t)n);
+            T nn = 0;
+            for (auto& v : p0) { v -= T(0.5); nn += v * v; }
+            nn = std::sqrt(nn);
+            if (nn > 0) for (auto& v : p0) v /= nn;
+            HIPCHK(hipMemcpyAsync(Pm, p0.data(), (size_t)n * sizeof(T), hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        Cols<T> Csum;
+        Csum.e[0] = nullptr; Csum.ne = 1;
+        if (o.center) dots(Pm, n, Csum, Pc.as<T>());
+        T* Psum = Pc.as<T>();                 // partials of sum(p_j), consumed by lz_r of step j
+        DevBuf Pc2; T* Psum_next = grow<T>(Pc2, pcap);
+        auto host_ab = [&](int ja, std::vector<double>& a, std::vector<double>& b) {
+            const std::vector<T> ah = read<T>(al, (size_t)std::max(ja, 1)), bh = read<T>(be, (size_t)ja + 1);
+            a.assign(ah.begin(), ah.begin() + ja);
+            b.assign(bh.begin(), bh.begin() + ja + 1);
+        };
+        int j = 0;
+        for (; j < jmax; ++j) {
+            ax(Pm + (size_t)j * n, t.as<T>(), S, j, 0);
+            hipLaunchKernelGGL(lz_r_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)t.as<T>(), m, mup(), (const T*)Psum, nbn, (const T*)be,
+                               (const T*)Q, j, r.as<T>(), Pa.as<T>(), (const int*)S);
+            const T* Pr = Pa.as<T>();
+            if (j > 0) {
+                hipLaunchKernelGGL(cgs_kernel<T>, dim3(nbm), dim3(WG), 0, s, r.as<T>(), (long)m, (const T*)Q, j, Pr, nbm, 0, Pb.as<T>(),
+                                   (const int*)S, j, 0);
+                hipLaunchKernelGGL(cgs_kernel<T>, dim3(nbm), dim3(WG), 0, s, r.as<T>(), (long)m, (const T*)Q, j, (const T*)Pb.as<T>(), nbm,
+                                   1, Pa.as<T>(), (const int*)S, j, 0);
+            }
+            hipLaunchKernelGGL(lz_norm_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)r.as<T>(), (long)m, Pr, nbm, eps, (const T*)al, Q + (size_t)j * m,
+                               al, j, 0, o.center, mup(), Pb.as<T>(), S, j);
+            at(Q + (size_t)j * m, y.as<T>(), S, j, S_BRKV);
+            hipLaunchKernelGGL(lz_s_kernel<T>, dim3(nbn), dim3(WG), 0, s, (const T*)y.as<T>(), n, (const T*)Pb.as<T>(), nbm, o.center,
+                               (const T*)al, (const T*)Pm, j, sv.as<T>(), Pa.as<T>(), (const int*)S);
+            hipLaunchKernelGGL(cgs_kernel<T>, dim3(nbn), dim3(WG), 0, s, sv.as<T>(), (long)n, (const T*)Pm, j + 1, (const T*)Pa.as<T>(), nbn,
+                               0, Pb.as<T>(), (const int*)S, j, 1);
+            hipLaunchKernelGGL(cgs_kernel<T>, dim3(nbn), dim3(WG), 0, s, sv.as<T>(), (long)n, (const T*)Pm, j + 1, (const T*)Pb.as<T>(), nbn,
+                               1, Pa.as<T>(), (const int*)S, j, 1);
+            hipLaunchKernelGGL(lz_norm_kernel<T>, dim3(nbn), dim3(WG), 0, s, (const T*)sv.as<T>(), (long)n, (const T*)Pa.as<T>(), nbn, eps, (const T*)al,
+                               Pm + (size_t)(j + 1) * n, be, j + 1, 1, o.center, (const T*)nullptr, Psum_next, S, j);
+            HIPCHK(hipGetLastError());
+            std::swap(Psum, Psum_next);
+            const int ja = j + 1;
+            const bool check = ja >= K + 2 && ja % 5 == 0 && ja < jmax;
+            if (!check && ja % kPoll != 0) continue;
+            if (read<int>(S + S_STOP, 1)[0] <= ja) break;               // lucky breakdown
+            if (!check) continue;
+            std::vector<double> a, b, sig, ub, vb;
+            host_ab(ja, a, b);
+            bidiag_svd(a, b, ja, sig, ub, vb, true);
+            const int kc = std::min(K, ja);
+            const double bl = std::fabs(b[ja]);
+            bool all = true;
+            for (int c = 0; c < kc && all; ++c)
+                if (bl * std::fabs(ub[c]) > conv_tol * sig[0]) all = false;
+            if (all) break;
+        }
+        const int ja = read<int>(S + S_ITERS, 1)[0];
+        const bool abrk = read<int>(S + S_BRKV, 1)[0] != 0;
+        R.iters.assign(1, ja);
+        const int kc = std::min(K, ja);
+        R.k_sel = kc;
+        R.d.clear(); R.U.clear(); R.V.clear();
+        if (kc == 0) return;
+        // An alpha breakdown at step ja (A p_ja in span Q) leaves beta_ja coupling p_ja: A [P_ja p_ja] = Q_ja [B_ja | beta_ja e],
+        // so the small problem is the (ja + 1)-column bidiagonal with a trailing alpha = 0 (its extra singular value is 0 and the
+        // last row of its left vectors vanishes).  svd/lanczos.hpp drops beta_ja there, which is wrong on low-rank input.
+        const int nbd = abrk ? ja + 1 : ja;
+        std::vector<double> a, b, sig, Ub, Vb;
+        host_ab(ja, a, b);
+        if (abrk) { a.push_back(0.0); b.push_back(0.0); }
+        bidiag_svd(a, b, nbd, sig, Ub, Vb, false);
+        R.d.assign(sig.begin(), sig.begin() + kc);
+        std::vector<T> wu((size_t)ja * kc), wv((size_t)nbd * kc);
+        for (int c = 0; c < kc; ++c) {
+            for (int l = 0; l < ja; ++l) wu[(size_t)c * ja + l] = (T)Ub[(size_t)c * nbd + l];
+            for (int l = 0; l < nbd; ++l) wv[(size_t)c * nbd + l] = (T)Vb[(size_t)c * nbd + l];
+        }
+        DevBuf dwu, dwv, ou, ov;
+        upload_vec(wu, dwu);
+        upload_vec(wv, dwv);
+        grow<T>(ou, (size_t)m * kc); grow<T>(ov, (size_t)n * kc);
+        hipLaunchKernelGGL(ritz_kernel<T>, dim3((m + WG - 1) / WG, kc), dim3(WG), 0, s, (const T*)Q, (long)m, ja, (const T*)dwu.as<T>(), kc,
+                           ou.as<T>());
+        hipLaunchKernelGGL(ritz_kernel<T>, dim3((n + WG - 1) / WG, kc), dim3(WG), 0, s, (const T*)Pm, (long)n, nbd, (const T*)dwv.as<T>(), kc,
+                           ov.as<T>());
+        HIPCHK(hipGetLastError());
+        R.U.resize((size_t)m * kc);
+        R.V.resize((size_t)n * kc);
+        download_cast<T>(g.c, ou, (size_t)m * kc, R.U.data(), s);
+        download_cast<T>(g.c, ov, (size_t)n * kc, R.V.data(), s);
+    }
+    void upload_vec(const std::vector<T>& h, DevBuf& b) {
+        grow<T>(b, h.size());
+        HIPCHK(hipMemcpyAsync(b.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+
+    void run(Result& R) {
+        R.row_means = mu_h;
+        double f = 0;
+        if (o.dense) for (size_t e = 0; e < (size_t)m * n; ++e) f += o.dense[e] * o.dense[e];
+        else for (int64_t e = 0; e < o.nnz; ++e) f += o.x[e] * o.x[e];
+        if (o.center) {
+            double q = 0;
+            for (double v : mu_h) q += v * v;
+            f -= (double)n * q;
+        }
+        R.frob = f;
+        if (o.algorithm == 0) deflation(R);
+        else lanczos(R);
+    }
+};
+
+// ------------------------------------------------------------------------------------------------------------ boundary
+struct Raw {   // the scalar pointers every entry shares, after the matrix arguments
+    int* k_max; double *U, *d, *V, *tol; int* max_iter; int *center, *verbose, *seed, *threads;
+    double *L1_u, *L1_v, *L2_u, *L2_v; int *nonneg_u, *nonneg_v; double *ub_u, *ub_v, *L21_u, *L21_v, *angular_u, *angular_v;
+    double* test_fraction; int *cv_seed, *patience, *mask_zeros, *algorithm;
+    int *graph_u_nnz; double* graph_u_lambda; int* graph_v_nnz; double* graph_v_lambda; int* obs_mask_nnz;
+    int* out_k_selected; double* out_wall_time_ms; int* out_iters_per_factor; double *out_frobenius_norm_sq, *out_row_means;
+    double* robust_delta;
+};
+
+Opts make_opts(const Raw& a, int m, int n) {
+    Opts o;
+    o.m = m; o.n = n; o.k = *a.k_max;
+    o.tol = *a.tol; o.max_iter = *a.max_iter; o.center = *a.center != 0; o.seed = (unsigned)(uint32_t)*a.seed;
+    o.algorithm = a.algorithm ? *a.algorithm : 0;
+    o.L1_u = *a.L1_u; o.L1_v = *a.L1_v; o.L2_u = *a.L2_u; o.L2_v = *a.L2_v; o.ub_u = *a.ub_u; o.ub_v = *a.ub_v;
+    o.nonneg_u = *a.nonneg_u != 0; o.nonneg_v = *a.nonneg_v != 0;
+    if (m < 1 || n < 1) throw std::invalid_argument("the matrix must have at least one row and one column");
+    if (o.k < 1 || o.k > std::min(m, n)) throw std::invalid_argument("k_max must be in [1, min(m, n)]");
+    if (o.k + 2 > NPMAX) throw std::invalid_argument("k_max above " + std::to_string(NPMAX - 2) + " is not supported");
+    if (o.algorithm < 0 || o.algorithm > 4) throw std::invalid_argument("algorithm must be 0 (deflation) .. 4 (krylov)");
+    if (*a.test_fraction > 0) throw std::invalid_argument("test_fraction > 0 (cross-validation / auto-rank) is not supported on the GPU");
+    if (a.obs_mask_nnz && *a.obs_mask_nnz > 0) throw std::invalid_argument("obs_mask is not supported on the GPU");
+    if ((a.graph_u_nnz && *a.graph_u_nnz > 0 && *a.graph_u_lambda > 0) || (a.graph_v_nnz && *a.graph_v_nnz > 0 && *a.graph_v_lambda > 0))
+        throw std::invalid_argument("graph regularization is not supported on the GPU");
+    if ((a.L21_u && *a.L21_u != 0) || (a.L21_v && *a.L21_v != 0)) throw std::invalid_argument("L21 is not supported on the GPU");
+    if ((a.angular_u && *a.angular_u != 0) || (a.angular_v && *a.angular_v != 0))
+        throw std::invalid_argument("angular is not supported on the GPU");
+    if (a.robust_delta && *a.robust_delta > 0) throw std::invalid_argument("robust SVD (robust_delta > 0) is not supported on the GPU");
+    if (o.algorithm != 0 && has_constraints(o))
+        throw std::invalid_argument("element constraints (L1 / L2 / nonneg / upper bound) need algorithm 0 (deflation) on the GPU");
+    if (o.algorithm == 0 && o.max_iter < 1) throw std::invalid_argument("deflation needs max_iter >= 1");
+    if (!(o.tol >= 0)) throw std::invalid_argument("tol must be non-negative");
+    return o;
+}
+
+void write_out(const Raw& a, const Opts& o, const Result& R, double ms) {
+    const int K = o.k;
+    std::copy(R.U.begin(), R.U.end(), a.U);           // U: m x k_max, the first k_selected columns written
+    std::copy(R.V.begin(), R.V.end(), a.V);
+    std::copy(R.d.begin(), R.d.end(), a.d);
+    for (int c = 0; c < (int)R.iters.size() && c < K; ++c) a.out_iters_per_factor[c] = R.iters[c];
+    *a.out_k_selected = R.k_sel;
+    *a.out_frobenius_norm_sq = R.frob;
+    if (o.center) std::copy(R.row_means.begin(), R.row_means.end(), a.out_row_means);
+    *a.out_wall_time_ms = ms;
+}
+
+template <class T> void run_entry(const Raw& a, Opts o) {
+    const auto t0 = std::chrono::steady_clock::now();
+    Result R;
+    {
+        Engine<T> E(o);
+        E.run(R);
+    }
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    write_out(a, o, R, ms);
+}
+
+void check_csc(const Opts& o) {
+    if (o.nnz < 0 || o.nnz >= INT_MAX) throw std::invalid_argument("nnz out of range");
+    if (!o.p || (o.nnz > 0 && (!o.i || !o.x))) throw std::invalid_argument("null CSC array");
+    if (o.p[0] != 0 || (int64_t)o.p[o.n] != o.nnz) throw std::invalid_argument("col_ptr must start at 0 and end at nnz");
+    for (int j = 0; j < o.n; ++j)
+        if (o.p[j + 1] < o.p[j]) throw std::invalid_argument("col_ptr must be non-decreasing");
+    for (int64_t e = 0; e < o.nnz; ++e)
+        if (o.i[e] < 0 || o.i[e] >= o.m) throw std::invalid_argument("row index out of range");
+}
+
+}  // namespace
+
+#define RCPPML_SVD_PARAMS                                                                                                         \
+    int *k_max, double *U, double *d, double *V, double *tol, int *max_iter, int *center, int *verbose, int *seed, int *threads,     \
+        double *L1_u, double *L1_v, double *L2_u, double *L2_v, int *nonneg_u, int *nonneg_v, double *ub_u, double *ub_v,          \
+        double *L21_u, double *L21_v, double *angular_u, double *angular_v, double *test_fraction, int *cv_seed, int *patience,     \
+        int *mask_zeros, int *algorithm, const int *graph_u_p, const int *graph_u_i, const double *graph_u_x, int *graph_u_dim,     \
+        int *graph_u_nnz, double *graph_u_lambda_val, const int *graph_v_p, const int *graph_v_i, const double *graph_v_x,          \
+        int *graph_v_dim, int *graph_v_nnz, double *graph_v_lambda_val, const int *obs_mask_p, const int *obs_mask_i,               \
+        const double *obs_mask_x, int *obs_mask_rows, int *obs_mask_cols, int *obs_mask_nnz, int *out_k_selected,                   \
+        double *out_wall_time_ms, double *out_test_loss, int *out_iters_per_factor, double *out_frobenius_norm_sq,                  \
+        double *out_row_means, double *robust_delta, int *irls_max_iter, double *irls_tol, int *out_status
+#define RCPPML_SVD_RAW                                                                                                            \
+    Raw{k_max, U, d, V, tol, max_iter, center, verbose, seed, threads, L1_u, L1_v, L2_u, L2_v, nonneg_u, nonneg_v, ub_u, ub_v,    \
+        L21_u, L21_v, angular_u, angular_v, test_fraction, cv_seed, patience, mask_zeros, algorithm, graph_u_nnz,                 \
+        graph_u_lambda_val, graph_v_nnz, graph_v_lambda_val, obs_mask_nnz, out_k_selected, out_wall_time_ms,                      \
+        out_iters_per_factor, out_frobenius_norm_sq, out_row_means, robust_delta}
+#define RCPPML_SVD_TRY  try { rcppml_err().clear(); *out_status = -1;
+#define RCPPML_SVD_CATCH                                                            \
+    } catch (const std::exception& e) { rcppml_err() = e.what(); *out_status = -1; } \
+    catch (...) { rcppml_err() = "unknown error"; *out_status = -1; }
+
+template <class T>
+static void svd_sparse(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz, const Raw& a,
+                       int* out_status) {
+    RCPPML_SVD_TRY
+        Opts o = make_opts(a, *m, *n);
+        o.nnz = *nnz; o.p = col_ptr; o.i = row_idx; o.x = values;
+        check_csc(o);
+        run_entry<T>(a, o);
+        *out_status = 0;
+    RCPPML_SVD_CATCH
+}
+template <class T>
+static void svd_dense(const double* A, int* m, int* n, const Raw& a, int* out_status) {
+    RCPPML_SVD_TRY
+        Opts o = make_opts(a, *m, *n);
+        if (!A) throw std::invalid_argument("null matrix");
+        o.nnz = (int64_t)*m * *n; o.dense = A;
+        run_entry<T>(a, o);
+        *out_status = 0;
+    RCPPML_SVD_CATCH
+}
+
+extern "C" void rcppml_gpu_svd_pca_double(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+                                          RCPPML_SVD_PARAMS) {
+    (void)out_test_loss; (void)irls_max_iter; (void)irls_tol;
+    svd_sparse<double>(col_ptr, row_idx, values, m, n, nnz, RCPPML_SVD_RAW, out_status);
+}
+extern "C" void rcppml_gpu_svd_pca_float(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+                                         RCPPML_SVD_PARAMS) {
+    (void)out_test_loss; (void)irls_max_iter; (void)irls_tol;
+    svd_sparse<float>(col_ptr, row_idx, values, m, n, nnz, RCPPML_SVD_RAW, out_status);
+}
+extern "C" void rcppml_gpu_svd_pca_dense_double(const double* A_data, int* m, int* n, RCPPML_SVD_PARAMS) {
+    (void)out_test_loss; (void)irls_max_iter; (void)irls_tol;
+    svd_dense<double>(A_data, m, n, RCPPML_SVD_RAW, out_status);
+}
+extern "C" void rcppml_gpu_svd_pca_dense_float(const double* A_data, int* m, int* n, RCPPML_SVD_PARAMS) {
+    (void)out_test_loss; (void)irls_max_iter; (void)irls_tol;
+    svd_dense<float>(A_data, m, n, RCPPML_SVD_RAW, out_status);
+}

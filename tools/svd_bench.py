@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""tools/svd_bench.py -- truncated SVD / PCA on the GPU path (rcppml_gpu_svd_pca_{float,double}, csrc/ops_svd.hip).
+
+Workloads, all of pbmc3k (tests/golden/pbmc3k.spz, 13714 x 2700, 2.28 M nonzeros):
+  pca(k = 10) with Lanczos (R's GPU default below k = 32; maxit 0: the 3k / k + 50 step cap, tol 1e-5)
+  svd(k = 5, nonneg) with deflation (R's choice for constrained k < 8; maxit 200, tol 1e-5)
+each in fp32 and fp64.  Per workload, after one warm-up call: the best and all of three wall times of the whole entry call (host CSC
+checks, upload, device transpose, the solve, the download), iterations (deflation: per factor; Lanczos: steps), and the entry's own
+out_wall_time_ms.  --cpu also times the numpy restatement of the reference's CPU deflation (tests/svd_ref.py, dense numpy on the
+machine's BLAS threads -- not the reference's C++) and, for Lanczos, numpy's dense LAPACK SVD of the centered matrix; both are
+labelled as such.  Prints one JSON line per workload."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+from rcppml_amd import _abi, data  # noqa: E402
+
+
+def pbmc3k():
+    from oracle import oracle as O
+    buf = np.fromfile(os.path.join(ROOT, "tests", "golden", "pbmc3k.spz"), dtype=np.uint8)
+    st, m, n, nnz, vt = O.spz_info(buf)
+    p, i, x = O.spz_decode(buf)
+    return data.CSC((m, n), np.asarray(p, np.int32), np.asarray(i, np.int32), np.asarray(x, np.float64))
+
+
+def timed(fn, reps=3):
+    fn()
+    out, ts = None, []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        ts.append(time.perf_counter() - t0)
+    return out, ts
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cpu", action="store_true", help="also time the numpy restatements (slow)")
+    args = ap.parse_args()
+    A = pbmc3k()
+    parts = (A.p, A.i, A.x, A.rows, A.cols)
+    work = [("pca k=10 lanczos", dict(k=10, center=True, algorithm=2, max_iter=0)),
+            ("svd k=5 nonneg deflation", dict(k=5, center=False, algorithm=0, max_iter=200, nonneg=(True, True)))]
+    dense = None
+    for name, w in work:
+        for prec in ("float", "double"):
+            kw = dict(w)
+            k = kw.pop("k")
+            r, ts = timed(lambda: _abi.svd_pca(parts, k, precision=prec, tol=1e-5, seed=0, **kw))
+            assert r["status"] == 0, r["error"]
+            rec = dict(workload=name, precision=prec, m=A.rows, n=A.cols, nnz=int(A.x.shape[0]), wall_s=min(ts), wall_s_all=ts,
+                       entry_wall_ms=r["wall_ms"], iterations=r["iters"][:r["k"]].tolist() if kw["algorithm"] == 0 else int(r["iters"][0]),
+                       d=r["d"][:r["k"]].tolist())
+            if args.cpu and prec == "double":
+                import svd_ref
+                if dense is None:
+                    import scipy.sparse as sp
+                    dense = sp.csc_matrix((A.x, A.i, A.p), shape=(A.rows, A.cols)).toarray()
+                if kw["algorithm"] == 0:
+                    t0 = time.perf_counter()
+                    ref = svd_ref.deflation_svd(dense, k, tol=1e-5, maxit=200, nonneg=(True, True))
+                    rec["cpu_s"] = time.perf_counter() - t0
+                    rec["cpu_label"] = "numpy restatement of the reference CPU deflation (tests/svd_ref.py), not the reference's C++"
+                    rec["cpu_same_iterations"] = ref["iters"].tolist() == rec["iterations"]
+                    rec["cpu_max_rel_d"] = float(np.max(np.abs(ref["d"] - r["d"][:k]) / ref["d"]))
+                else:
+                    t0 = time.perf_counter()
+                    sv = np.linalg.svd(dense - dense.mean(axis=1, keepdims=True), compute_uv=False)
+                    rec["cpu_s"] = time.perf_counter() - t0
+                    rec["cpu_label"] = "numpy dense LAPACK SVD of the centered matrix (all singular values), not the reference's C++"
+                    rec["cpu_max_rel_d"] = float(np.max(np.abs(sv[:k] - r["d"][:k]) / sv[:k]))
+            print(json.dumps(rec), flush=True)
+
+
+if __name__ == "__main__":
+    main()
