@@ -336,6 +336,54 @@ RCPPML_GPU_API void rcppml_gpu_svd_pca_dense_float(const double* A_data, int* m,
         int* out_iters_per_factor, double* out_frobenius_norm_sq, double* out_row_means, double* robust_delta, int* irls_max_iter,
         double* irls_tol, int* out_status);
 
+/* Embedding assessment (rcppml_amd/csrc/ops_assess.hip): the reference plugin's rcppml_gpu_assess (src/gpu_bridge_assess.cu:358-753)
+ * with its 26 pointers, called by R's assess() (R/assess.R:708-769).  embedding: n x dim row-major doubles, cast to fp32.  Seeds are
+ * (unsigned)*seed plus an offset (restart r: + r; silhouette: + 100; folds: + 200), each driving std::mt19937 + std::shuffle.
+ *   do_clustering: *kmeans_nstart restarts of exactly *kmeans_maxiter assign / accumulate / divide steps from the points
+ *     idx[c % n] of the restart's shuffle, n_centers = *n_classes; ARI and NMI of the best restart by ARI (strict >).  nstart < 1:
+ *     both -1.  Deviation: the centroid sums are fp64 in a fixed order, rounded to fp32 and divided in fp32 (the reference adds fp32
+ *     atomics, which has no fixed answer).
+ *   do_silhouette: min(spc, class size) shuffled samples per class; mean silhouette over the points.
+ *   do_classify: stratified *knn_folds-fold kNN vote (k = min(knn_k, n_train)); mean accuracy and macro F1 over all classes.
+ *   do_batch && n_batch > 1: the min(batch_knn_k, n - 1) nearest non-self neighbours; mean normalised batch entropy and kNN
+ *     batch silhouette.
+ * Exact fp32 kNN: the k smallest candidates in (d, index) order, d >= 1e30 or NaN never chosen.  Outputs of metrics not asked for
+ * are untouched.  Refused (*out_status = -1, nothing else written, reason in rcppml_gpu_last_error): n < 1, dim < 1; clustering
+ * with kmeans_maxiter < 1 or n_classes < 1; classification with knn_k < 1 or knn_folds < 1; batch with batch_knn_k < 1; a label
+ * outside [0, n_classes) when clustering, silhouette or classification is asked; a batch label outside [0, n_batch) when batch
+ * mixing is asked; no device. */
+RCPPML_GPU_API void rcppml_gpu_assess(const double* embedding, int* n, int* dim, const int* labels, int* n_classes,
+        const int* batch_labels, int* n_batch, int* do_clustering, int* do_silhouette, int* do_classify, int* do_batch,
+        int* kmeans_nstart, int* kmeans_maxiter, int* sil_samples_per_class, int* knn_k, int* knn_folds, int* batch_knn_k,
+        int* seed, double* out_ari, double* out_nmi, double* out_silhouette, double* out_knn_accuracy, double* out_knn_f1,
+        double* out_batch_sil, double* out_batch_entropy, int* out_status);
+/* rcppml_gpu_assess plus the per-item results.  Each extra output may be NULL (not written); the others are written when their
+ * metric runs: out_assignments (n, the best restart's), out_restart_ari / out_restart_nmi (nstart), out_sil_point (n, fp32),
+ * out_fold_ids (n), out_fold_accuracy / out_fold_f1 (knn_folds, NaN for a fold without training or test points),
+ * out_batch_entropy_point / out_batch_sil_point (n).  *point_capacity, *restart_capacity, *fold_capacity: the lengths of those
+ * buffers; a buffer that is written and too short is refused like the inputs above. */
+RCPPML_GPU_API void rcppml_gpu_assess_ex(const double* embedding, int* n, int* dim, const int* labels, int* n_classes,
+        const int* batch_labels, int* n_batch, int* do_clustering, int* do_silhouette, int* do_classify, int* do_batch,
+        int* kmeans_nstart, int* kmeans_maxiter, int* sil_samples_per_class, int* knn_k, int* knn_folds, int* batch_knn_k,
+        int* seed, double* out_ari, double* out_nmi, double* out_silhouette, double* out_knn_accuracy, double* out_knn_f1,
+        double* out_batch_sil, double* out_batch_entropy, int* out_assignments, double* out_restart_ari, double* out_restart_nmi,
+        float* out_sil_point, int* out_fold_ids, double* out_fold_accuracy, double* out_fold_f1, double* out_batch_entropy_point,
+        double* out_batch_sil_point, int* point_capacity, int* restart_capacity, int* fold_capacity, int* out_status);
+/* Exact fp32 brute-force kNN.  query: n_query x dim row-major; train: n_train x dim, or NULL for the query matrix itself (required by
+ * mask modes 1 and 2).  mask_mode 0: every train point; 1: not the query's own index; 2: not the points of the query's group
+ * (group: n_query ints in [0, n_groups)).  group_k (mode 2, may be NULL): n_groups ints in [0, k], the k of a query of that group.
+ * out_idx / out_dist: n_query x k (capacity *out_capacity), the k smallest candidates in (d, index) order; empty slots -1 / 1e30. */
+RCPPML_GPU_API void rcppml_gpu_knn_float(const float* query, int* n_query, const float* train, int* n_train, int* dim, int* k,
+        int* mask_mode, const int* group, const int* group_k, int* n_groups, int* out_idx, float* out_dist, int* out_capacity,
+        int* out_status);
+/* Host only, no device work: the random plan rcppml_gpu_assess draws.  Each output may be NULL (not drawn).  out_init_idx:
+ * kmeans_nstart x n_classes initial centroid points (capacity *init_capacity); out_sil_samples: the silhouette samples, class by
+ * class (capacity *sil_capacity), out_sil_counts: n_classes counts min(spc, class size); out_fold_ids: n fold ids (capacity
+ * *fold_capacity).  Refused: n < 1, n_classes < 1, a label outside [0, n_classes), knn_folds < 1 with out_fold_ids, a short buffer. */
+RCPPML_GPU_API void rcppml_gpu_assess_plan(const int* labels, int* n, int* n_classes, int* kmeans_nstart, int* sil_samples_per_class,
+        int* knn_folds, int* seed, int* out_init_idx, int* init_capacity, int* out_sil_samples, int* out_sil_counts,
+        int* sil_capacity, int* out_fold_ids, int* fold_capacity, int* out_status);
+
 /* Last error text of the calling thread ("" if none). */
 RCPPML_GPU_API const char* rcppml_gpu_last_error(void);
 

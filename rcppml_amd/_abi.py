@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_hip_als_small_eligible", "rcppml_hip_als_small_fit",
     "rcppml_gpu_bipartition_double", "rcppml_gpu_dclust_double", "rcppml_gpu_bipartition_ex", "rcppml_gpu_dclust_ex",
     "rcppml_gpu_svd_pca_double", "rcppml_gpu_svd_pca_float", "rcppml_gpu_svd_pca_dense_double", "rcppml_gpu_svd_pca_dense_float",
+    "rcppml_gpu_assess", "rcppml_gpu_assess_ex", "rcppml_gpu_knn_float", "rcppml_gpu_assess_plan",
 ]
 
 
@@ -875,3 +876,114 @@ def svd_pca(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=200
     return dict(status=st.value, error=last_error() if st.value else "", U=b["U"][:m * k_max].reshape(max(k_max, 0), m).T,
                 V=b["V"][:n * k_max].reshape(max(k_max, 0), n).T, d=b["d"], k=ksel.value, iters=b["iters"], frob=frob.value, row_means=b["row_means"],
                 wall_ms=wall.value, test_loss=b["test_loss"], buffers=b)
+
+
+# ----------------------------------------------------------------------------- embedding assessment (ops_assess.hip)
+KNN_MASK = {"none": 0, "self": 1, "group": 2}
+_ASSESS_OUT = ("ari", "nmi", "silhouette", "knn_accuracy", "knn_f1", "batch_sil", "batch_entropy")
+
+
+def _assess_head(emb, labels, n_classes, batch, n_batch, flags, nstart, maxiter, spc, knn_k, folds, batch_k, seed, outs):
+    e = np.ascontiguousarray(emb, np.float64)
+    n, dim = (e.shape if e.ndim == 2 else (int(e.shape[0]), 1))
+    lab = np.ascontiguousarray(np.zeros(n) if labels is None else labels, np.int32)
+    bat = np.ascontiguousarray(np.full(n, -1) if batch is None else batch, np.int32)
+    args = [_np_ptr(e), _ci(n), _ci(dim), _np_ptr(lab), _ci(n_classes), _np_ptr(bat), _ci(n_batch)] + [_ci(int(bool(f))) for f in flags] + [
+        _ci(nstart), _ci(maxiter), _ci(spc), _ci(knn_k), _ci(folds), _ci(batch_k), _ci(seed)] + [C.byref(o) for o in outs]
+    return args, (e, lab, bat), n
+
+
+def assess_raw(emb, labels, n_classes, batch=None, n_batch=0, *, clustering=True, silhouette=True, classify=True, batch_mixing=True,
+               nstart=10, maxiter=100, spc=200, knn_k=15, folds=5, batch_k=50, seed=42, init=0.0):
+    """The R-shaped 26-pointer entry (reference src/gpu_bridge_assess.cu:358-376), laid out as R's .assess_gpu passes it
+    (R/assess.R:708-769).  emb: n x dim (row-major doubles are handed over).  The seven outputs start at `init` (what is not computed
+    stays so).  Returns dict(status, error, ari, nmi, silhouette, knn_accuracy, knn_f1, batch_sil, batch_entropy)."""
+    outs = [C.c_double(init) for _ in _ASSESS_OUT]
+    args, keep, n = _assess_head(emb, labels, n_classes, batch, n_batch, (clustering, silhouette, classify, batch_mixing), nstart,
+                                 maxiter, spc, knn_k, folds, batch_k, seed, outs)
+    st = C.c_int(-99)
+    args.append(C.byref(st))
+    assert len(args) == 26
+    lib().rcppml_gpu_assess(*args)
+    r = dict(status=st.value, error=last_error() if st.value else "")
+    r.update({k: o.value for k, o in zip(_ASSESS_OUT, outs)})
+    return r
+
+
+def assess_ex(emb, labels, n_classes, batch=None, n_batch=0, *, clustering=True, silhouette=True, classify=True, batch_mixing=True,
+              nstart=10, maxiter=100, spc=200, knn_k=15, folds=5, batch_k=50, seed=42, init=0.0, capacity=None):
+    """Build-defined rcppml_gpu_assess_ex: the 26-pointer results plus assignments (best restart), restart_ari / restart_nmi,
+    sil_point (fp32), fold_ids, fold_accuracy / fold_f1 (NaN: fold without training or test points), batch_entropy_point,
+    batch_sil_point.  capacity: (point, restart, fold) buffer lengths to hand in; default: what the call needs."""
+    outs = [C.c_double(init) for _ in _ASSESS_OUT]
+    args, keep, n = _assess_head(emb, labels, n_classes, batch, n_batch, (clustering, silhouette, classify, batch_mixing), nstart,
+                                 maxiter, spc, knn_k, folds, batch_k, seed, outs)
+    caps = list(capacity) if capacity is not None else [n, max(nstart, 0), max(folds, 0)]
+    b = dict(assignments=np.full(max(caps[0], 1), -7, np.int32), restart_ari=np.full(max(caps[1], 1), np.nan),
+             restart_nmi=np.full(max(caps[1], 1), np.nan), sil_point=np.full(max(caps[0], 1), np.nan, np.float32),
+             fold_ids=np.full(max(caps[0], 1), -7, np.int32), fold_accuracy=np.full(max(caps[2], 1), -7.0),
+             fold_f1=np.full(max(caps[2], 1), -7.0), batch_entropy_point=np.full(max(caps[0], 1), np.nan),
+             batch_sil_point=np.full(max(caps[0], 1), np.nan))
+    order = ("assignments", "restart_ari", "restart_nmi", "sil_point", "fold_ids", "fold_accuracy", "fold_f1", "batch_entropy_point",
+             "batch_sil_point")
+    st = C.c_int(-99)
+    args += [_np_ptr(b[k]) for k in order] + [_ci(c) for c in caps] + [C.byref(st)]
+    lib().rcppml_gpu_assess_ex(*args)
+    r = dict(status=st.value, error=last_error() if st.value else "")
+    r.update({k: o.value for k, o in zip(_ASSESS_OUT, outs)})
+    lens = dict(assignments=n, restart_ari=max(nstart, 0), restart_nmi=max(nstart, 0), sil_point=n, fold_ids=n,
+                fold_accuracy=max(folds, 0), fold_f1=max(folds, 0), batch_entropy_point=n, batch_sil_point=n)
+    r.update({k: b[k][:lens[k]] for k in order})
+    r["buffers"] = b
+    return r
+
+
+def knn_float(query, train=None, k=15, *, mask="none", group=None, group_k=None, capacity=None):
+    """rcppml_gpu_knn_float: exact fp32 brute-force kNN.  query (nq x dim) / train (nt x dim, None: the query matrix itself, which
+    mask "self" and "group" need).  group: nq ints, group_k: k per group (mask "group").  Returns dict(status, error, idx (nq x k,
+    -1 = empty), dist (nq x k float32, 1e30 = empty))."""
+    q = np.ascontiguousarray(query, np.float32)
+    if q.ndim == 1:
+        q = q[:, None]
+    nq, dim = q.shape
+    t = None if train is None else np.ascontiguousarray(train, np.float32).reshape(-1, dim)
+    g = None if group is None else np.ascontiguousarray(group, np.int32)
+    gk = None if group_k is None else np.ascontiguousarray(group_k, np.int32)
+    ng = 0 if g is None else (int(g.max()) + 1 if g.size else 0)
+    if gk is not None:
+        ng = max(ng, gk.shape[0])
+    cap = nq * k if capacity is None else int(capacity)
+    oi = np.full(max(cap, 1), -7, np.int32)
+    od = np.full(max(cap, 1), np.nan, np.float32)
+    st = C.c_int(-99)
+    lib().rcppml_gpu_knn_float(_np_ptr(q), _ci(nq), _np_ptr(t) if t is not None else None, _ci(0 if t is None else t.shape[0]), _ci(dim),
+                               _ci(k), _ci(KNN_MASK[mask]), _np_ptr(g) if g is not None else None,
+                               _np_ptr(gk) if gk is not None else None, _ci(ng), _np_ptr(oi), _np_ptr(od), _ci(cap), C.byref(st))
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(oi, od))
+    if st.value == 0:
+        r.update(idx=oi[:nq * k].reshape(nq, k), dist=od[:nq * k].reshape(nq, k))
+    return r
+
+
+def assess_plan(labels, n_classes, *, nstart=10, spc=200, folds=5, seed=42, capacity=None):
+    """rcppml_gpu_assess_plan (host only, no device): dict(status, error, init (nstart x n_classes point indices), sil_counts
+    (n_classes, min(spc, size)), sil_samples (class by class), fold_ids (n))."""
+    lab = np.ascontiguousarray(labels, np.int32)
+    n = lab.shape[0]
+    counts_max = int(np.sum(np.minimum(np.maximum(spc, 0), np.bincount(lab[(lab >= 0) & (lab < max(n_classes, 1))],
+                                                                           minlength=max(n_classes, 1)))))
+    caps = list(capacity) if capacity is not None else [max(nstart, 0) * max(n_classes, 0), counts_max, n]
+    init = np.full(max(caps[0], 1), -7, np.int32)
+    samples = np.full(max(caps[1], 1), -7, np.int32)
+    counts = np.full(max(n_classes, 1), -7, np.int32)
+    folds_out = np.full(max(caps[2], 1), -7, np.int32)
+    st = C.c_int(-99)
+    lib().rcppml_gpu_assess_plan(_np_ptr(lab), _ci(n), _ci(n_classes), _ci(nstart), _ci(spc), _ci(folds), _ci(seed), _np_ptr(init),
+                                 _ci(caps[0]), _np_ptr(samples), _np_ptr(counts), _ci(caps[1]), _np_ptr(folds_out), _ci(caps[2]),
+                                 C.byref(st))
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(init, samples, counts, folds_out))
+    if st.value == 0:
+        tot = int(np.sum(np.maximum(counts[:n_classes], 0)))
+        r.update(init=init[:max(nstart, 0) * n_classes].reshape(max(nstart, 0), n_classes), sil_counts=counts[:n_classes].copy(),
+                 sil_samples=samples[:tot].copy(), fold_ids=folds_out[:n].copy())
+    return r
