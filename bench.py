@@ -16,6 +16,10 @@ Launch: at N = 1 the K timed iterations are K replays of one captured hipGraph o
 the same); the per-phase HIP-event durations in the line come from an eager re-run of the same K iterations, checked
 bit-identical (--no-graph times the eager loop; N > 1 always does).
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  Every other figure -- the eager
+re-run behind the per-phase times and the rooflines, `fit_from_start`, the plugin's PCIe-inclusive call, the CPU baseline, the CPU
+reference fit, the fp64 leg, the no-op step counts (and the extra runs of --config c1 / c5) -- needs --full.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -67,6 +71,10 @@ def parse():
                                                               "stream) -- the single-rank twin of a multi-rank run")
     ap.add_argument("--init-f32", action="store_true", help="fp64 run starting from the fp32-rounded factors (so that one CPU "
                                                             "reference fit serves both precisions)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every figure that needs runs of its own: per-phase times and rooflines (eager re-run), "
+                         "fit_from_start, the plugin call, CPU baseline, CPU reference fit, fp64 leg, no-op step counts (the --no-* "
+                         "options skip single ones)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (factors W_T, H, d and the loss; c5 also theta) as "
                          "DIR/<name>.npy in the run's precision (the loss in float64), at most 64 MB in all (dump_outputs())")
@@ -361,9 +369,9 @@ def main():
         outputs = None
         if args.dump_outputs and rank == 0:            # host copies before anything below moves the state (rank 0: its H shard)
             outputs = dict(W_T=st.W_T.cpu().numpy(), H=st.H.cpu().numpy(), d=st.d.cpu().numpy(), loss=final_loss_t[:1].cpu().numpy())
-        work = ops.ctx.stats()
+        work = ops.ctx.stats() if args.full else None
         eager_ms_per_step = None
-        if graph is not None:
+        if graph is not None and args.full:
             # per-phase HIP events cannot sit inside a replayed graph: the SAME K iterations are run once more, eagerly, from the
             # state the timed region started from, with an event pair around every phase (kernel durations do not depend on how
             # the launch was issued; the eager pass's own wall time is reported as `eager_ms_per_step`)
@@ -393,7 +401,7 @@ def main():
         # early), so this is an eager loop -- the steady-state `ms_per_step` above is the contract's timed region, this figure is
         # what a fit from scratch pays per iteration.
         fit_from_start = None
-        if world == 1 and not force_dist:
+        if world == 1 and not force_dist and args.full:
             snap_end = snapshot()                          # (everything below the timed region reads the state it left behind)
             for o in ops._order.values():
                 o["valid"], o["fresh"] = False, False       # no sweep counts yet: iteration 0 and 1 run in natural column order
@@ -420,129 +428,14 @@ def main():
     coll = comm.collective_ms()
 
     if rank == 0:
-        sv = 4 if args.dtype == "f32" else 8
         nnz = A_loc.nnz
-        bytes_h = algorithmic_bytes_rhs(nnz, n_loc, m, k, sv)
-        bytes_w = algorithmic_bytes_rhs(nnz, m, n_loc, k, sv)
-        cnt_h, ms_h = ev.get("rhs_H", (0, 0.0))
-        cnt_w, ms_w = ev.get("rhs_W", (0, 0.0))
-        launches = cnt_h + cnt_w
-        avg_s = (ms_h + ms_w) / max(launches, 1) * 1e-3
-        avg_bytes = (bytes_h * cnt_h + bytes_w * cnt_w) / max(launches, 1)
-        achieved = avg_bytes / max(avg_s, 1e-12) / 1e9
         phases = {name: round(ms / args.steps, 4) for name, (c, ms) in sorted(ev.items())}
-        planned = bool(st.A.get("plans")) and bool(st.At.get("plans"))
-        plan_info = {side: csc["plans"][k].info() for side, csc in (("H", st.A), ("W", st.At)) if csc.get("plans", {}).get(k)}
-        # delivery rate of the gathered k-rows of F (nnz * k * s_v per launch: not compulsory HBM traffic) against
-        # the two on-chip ceilings: vector L1 (64 B/clk/CU) for the gather kernel, LDS (256 B/clk/CU, ds_read_b128) for the
-        # row-tiled kernel
-        gather_bytes = float(nnz) * k * sv
-        deliv = gather_bytes / max(avg_s, 1e-12) / 1e12
-        roof_rhs = {"bound": "hbm",
-                    "kernel": ("rhs_win_kernel + rhs_win_finish_kernel: SpMM-like B = F * A(:,j), F through a ring of LDS row tiles, nonzeros scheduled "
-                               "over a sliding window, partition slabs + overflow summed by the finishing pass; both half-updates"
-                               if planned and all(p.get("kind", "window") == "window" for p in plan_info.values()) else
-                               "rhs_tiled_kernel + spill / reduce kernels (slab plan): SpMM-like B = F * A(:,j), both half-updates"
-                               if planned else "rhs_stage_kernel (gather form; SpMM-like B = F * A(:,j), both half-updates)"),
-                    "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
-                    "traffic": None, "algorithmic_bytes_per_launch": avg_bytes, "avg_launch_ms": avg_s * 1e3,
-                    "rhs_H_ms": ms_h / max(cnt_h, 1), "rhs_W_ms": ms_w / max(cnt_w, 1),
-                    "gathered_row_delivery": {"achieved_TBps": deliv, "bytes_per_launch": gather_bytes,
-                                              "frac_of_L1_39.3TBps": deliv / 39.3, "frac_of_LDS_157TBps": deliv / 157.3},
-                    "plan": plan_info}
-        # NNLS solve: algorithmic flops = 2 k^2 per column and sweep (k coordinate steps, each a k-long residual
-        # update; nnls_batch.hpp:96-121), sweeps counted by the kernels themselves.  fp32 k<=64 runs these updates
-        # as v_mfma_f32_32x32x2_f32 (dense f32 MFMA peak 157.3 TFLOP/s = the f32 vector rate); the phase time
-        # also holds the Gram padding/permutation helper kernel (a few us; the column-ordering kernels ride in the launches of
-        # the scaling pass since round 5: phase "scale").
-        cnt_sh, ms_sh = ev.get("solve_H", (0, 0.0))
-        cnt_sw, ms_sw = ev.get("solve_W", (0, 0.0))
-        cd_launches = cnt_sh + cnt_sw
-        cd_s = (ms_sh + ms_sw) / max(cd_launches, 1) * 1e-3
-        cd_flops = 2.0 * k * k * work["cd_column_sweeps"] / max(cd_launches, 1)
-        cd_peak = 157.3 if args.dtype == "f32" else 78.6
-        roof_cd = None
-        if args.solver == "cd" and work["cd_columns"] > 0:
-            # the two launches run different kernels at the default sizes (32-column MFMA tiles for H, 16-column tiles for
-            # the W side, which has fewer tiles than SIMDs): `roofline` is the H-side kernel, the longer of the two; the
-            # counted column-sweeps are split between the sides in the proportion of the last iteration's per-column sweeps
-            share_h = ms_sh / max(ms_sh + ms_sw, 1e-12)
-            try:
-                sw_h = float(st.ops._order["H"]["sweeps"].sum().item())
-                sw_w = float(st.ops._order["W"]["sweeps"].sum().item())
-                if sw_h + sw_w > 0:
-                    share_h = sw_h / (sw_h + sw_w)
-            except Exception:
-                pass
-            # idle-slot fraction of the MFMA tiles: a wave sweeps until its slowest column has converged, so a tile of T
-            # columns spends T * max(sweeps) column-sweeps for sum(sweeps) useful ones (last iteration's counts, in the
-            # work order the kernel used: sweep-sorted for the H side, natural for the W side)
-            idle = {}
-            try:
-                for side, tile in (("H", 32), ("W", 16 if n_loc >= 0 and m <= 32 * 1024 else 32)):
-                    o = st.ops._order[side]
-                    sw = o["sweeps"].cpu().numpy().astype(np.int64)
-                    use_order = o["valid"] and cfg.cd_tol > 0 and sw.shape[0] >= als.ORDER_MIN_COLUMNS
-                    # (with the fused tail o["order"] already ranks THESE counts for the next solve: the copy the last solve kept)
-                    sq = sw[o.get("order_used", o["order"]).cpu().numpy()] if use_order else sw
-                    pad = (-len(sq)) % tile
-                    tl = np.concatenate([sq, np.zeros(pad, np.int64)]).reshape(-1, tile)
-                    idle[side] = float(1.0 - tl.sum() / max(1, (tl.max(axis=1) * tile).sum()))
-            except Exception:
-                pass
-            # what solve_cd_impl.hip.h launches for variant = auto: fp32 k <= 128 -> 32-column v_mfma_f32_32x32x2 tiles (16-column
-            # v_mfma_f32_16x16x4 tiles on sides with fewer than 4 tiles per CU, k <= 64; lane = column 4x4 blocks for k <= 32 on large
-            # sides); fp64 k <= 128 -> 16-column v_mfma_f64_16x16x4 tiles; above 128: the VALU lane-group kernel
-            mfma = k <= 128 and args.variant == "auto"
-            f32 = args.dtype == "f32"
-            w_small16 = f32 and k <= 64 and (m + 31) // 32 < 4 * 256
-            flops_h = 2.0 * k * k * work["cd_column_sweeps"] * share_h / max(cnt_sh, 1)
-            flops_w = 2.0 * k * k * work["cd_column_sweeps"] * (1.0 - share_h) / max(cnt_sw, 1)
-            s_h, s_w = ms_sh / max(cnt_sh, 1) * 1e-3, ms_sw / max(cnt_sw, 1) * 1e-3
-            tf_h, tf_w = flops_h / max(s_h, 1e-12) / 1e12, flops_w / max(s_w, 1e-12) / 1e12
-            tf = cd_flops / max(cd_s, 1e-12) / 1e12
-            roof_cd = {"bound": "mfma" if mfma else "valu",
-                       "kernel": (("cd_mfma_kernel (coordinate-descent NNLS on 32-column v_mfma_f32_32x32x2 tiles, H half-update)" if f32 else
-                                   "cd_mfma64_kernel<double> (coordinate-descent NNLS on 16-column v_mfma_f64_16x16x4 tiles, H half-update)") if mfma
-                                  else "cd_group_kernel (VALU lane groups; rank above 128 or a forced variant), H half-update"),
-                       "achieved": tf_h, "peak": cd_peak, "unit": "TFLOP/s", "frac": tf_h / cd_peak, "traffic": None,
-                       "algorithmic_flops_per_launch": flops_h, "avg_launch_ms": s_h * 1e3,
-                       "mean_sweeps_per_column": work["cd_column_sweeps"] / work["cd_columns"],
-                       "idle_slot_fraction": idle,
-                       "solve_H_ms": s_h * 1e3, "solve_W_ms": s_w * 1e3,
-                       "w_side": {"kernel": ("cd_mfma64_kernel<float> (16-column v_mfma_f32_16x16x4 tiles)" if (mfma and w_small16) else "same kernel"),
-                                  "achieved": tf_w, "frac": tf_w / cd_peak, "avg_launch_ms": s_w * 1e3,
-                                  "algorithmic_flops_per_launch": flops_w},
-                       "both_sides": {"achieved": tf, "frac": tf / cd_peak, "avg_launch_ms": cd_s * 1e3}}
-            if mfma and f32:
-                # the kernel's own ceiling: per coordinate pair a wave issues ceil(k / 32) f32 MFMAs of 64 cycles each and a
-                # dependent chain of ~100 VALU / LDS cycles that cannot overlap them on gfx950 (profiles/r03_issue_probe.txt); idle slots and
-                # the residency tail come on top
-                mf = 64.0 * ((k + 31) // 32)
-                roof_cd["ceiling_frac"] = mf / (mf + 100.0)
-                roof_cd["ceiling_what"] = ("MFMA-issue share of a coordinate pair's cycles (%d MFMA + ~100 dependent VALU / LDS, mutually exclusive on "
-                                           "the f32 pipes): what `frac` would be with no idle column slot and no residency tail" % int(mf))
-        cd_dominant = roof_cd is not None and (ms_sh + ms_sw) > (ms_h + ms_w)
-        # HBM/fabric bytes per launch from the committed rocprofv3 PMC passes of this same command (FETCH_SIZE x2 per the
-        # gfx950 correction + WRITE_SIZE, profiles/summarize.py); only meaningful for the default workload
-        default_wl = (m, n_loc, k, args.dtype, world) == (20000, 100000, 64, "f32", 1)
-        import glob
-        pmcs = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "r[0-9][0-9]_pmc.json")))
-        pmc_path = pmcs[-1] if pmcs else ""          # the latest round's counter passes
-        pmc_name = "profiles/" + os.path.basename(pmc_path)
-        if default_wl and os.path.exists(pmc_path):
-            try:
-                pmc = json.load(open(pmc_path))
-                if "rhs_per_launch" in pmc:
-                    roof_rhs["traffic"] = pmc["rhs_per_launch"]["hbm_bytes_per_launch"]
-                    roof_rhs["traffic_over_algorithmic"] = roof_rhs["traffic"] / avg_bytes
-                    roof_rhs["traffic_source"] = pmc_name + " (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes; all kernels of one rhs call, mean of both sides)"
-                for name, v in pmc.get("kernels", {}).items():
-                    if roof_cd is not None and "cd_mfma_kernel" in name:
-                        roof_cd["traffic"] = v["hbm_bytes_per_launch"]
-                        roof_cd["traffic_source"] = pmc_name
-            except Exception:
-                pass
+        roof = {}
+        if args.full:
+            roof_cd, roof_rhs, cd_dominant = rooflines(args, st, ops, cfg, ev, work, world, m, n_loc, k, nnz)
+            # `roofline` = the kernel the iteration spends most time in; the other regime of SURVEY 8(d) beside it
+            roof = {"roofline": roof_cd if cd_dominant else roof_rhs,
+                    ("roofline_rhs" if cd_dominant else "roofline_cd"): roof_rhs if cd_dominant else roof_cd}
         out = {
             "metric": "ALS updates/sec (cols solved/s), k=%d sparse NMF" % k,
             "value": args.steps * (m + n_total) / dt,
@@ -560,17 +453,16 @@ def main():
                                       "coordinate-descent" if args.solver == "cd" else "Cholesky+clip", args.cd_maxit),
                        "rows": m, "cols_per_gpu": n_loc, "nnz_per_gpu": nnz, "k": k, "solver": args.solver,
                        "cd_variant": args.variant, "parallelism": "column-shard x%d" % world},
-            # `roofline` = the kernel the iteration spends most time in; the other regime of SURVEY 8(d) beside it
-            "roofline": roof_cd if cd_dominant else roof_rhs,
-            ("roofline_rhs" if cd_dominant else "roofline_cd"): roof_rhs if cd_dominant else roof_cd,
+            **roof,
             "phases_ms_per_step": phases,
             # how the timed iterations were issued; with graph replay the per-phase / per-kernel HIP-event durations above
-            # come from an eager re-run of the same K iterations (checked bit-identical) right after the timed region
+            # come from an eager re-run of the same K iterations (checked bit-identical) right after the timed region: --full only,
+            # a plain run's line has them for the eager loop alone
             "launch": launch_mode,
             "fused_tail": bool(ops.fused_tail),
             "eager_ms_per_step": eager_ms_per_step,
             "final_loss": final_loss,
-            "fit_from_start": fit_from_start,
+            **({"fit_from_start": fit_from_start} if args.full else {}),
             "world_size_seen": world,
             "backend": (dist.get_backend() if (world > 1 or force_dist) else None),
             "forced_one_rank_group": force_dist,
@@ -578,12 +470,12 @@ def main():
                                                    bytes=v["bytes"]) for name, v in sorted(coll.items())},
             "collectives_model": collectives_model(world, m, k, 4 if args.dtype == "f32" else 8, args.w_solve),
         }
-        if world == 1 and not args.no_plugin_figure and args.config == "c2":
+        if args.full and world == 1 and not args.no_plugin_figure and args.config == "c2":
             try:
                 out["plugin_pcie_inclusive"] = plugin_figure(A_loc, m, n_loc, k, args.seed)
             except Exception as e:
                 out["plugin_pcie_inclusive"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 W_T, dvec, H = st.factors()
                 G_h = st.ops.gram(st.W_T, 1e-15, 0.0).cpu().numpy()
@@ -602,7 +494,7 @@ def main():
             except Exception as e:  # the baseline must never take the GPU number down with it
                 out["cpu_baseline"] = {"value": None, "unit": "cols/s", "cores": os.cpu_count(), "kind": "port",
                                        "sample": "failed: %r" % (e,)}
-        if world == 1 and args.solver == "cd" and args.dtype == "f32" and k <= 64 and not args.no_noop_count:
+        if args.full and world == 1 and args.solver == "cd" and args.dtype == "f32" and k <= 64 and not args.no_noop_count:
             try:
                 out["cd_noop_steps"] = cd_noop_fraction(st, ops, cfg, k)
                 zs = out["cd_noop_steps"]
@@ -619,7 +511,7 @@ def main():
         # ---- the metric's second half: deviation of the fit's loss from a CPU reference fit (fp64 oracle restatement of
         # nmf_fit<CPU>, same matrix, same starting factors, same number of iterations, tol = 0; outside the timed region)
         ref_loss = None
-        if world == 1 and not args.no_cpu_ref:
+        if args.full and world == 1 and not args.no_cpu_ref:
             try:
                 from oracle import oracle as O
                 t0 = time.perf_counter()
@@ -634,7 +526,7 @@ def main():
                 out["loss_rel_dev_vs_cpu_ref"] = abs(final_loss - ref.loss) / abs(ref.loss)
             except Exception as e:
                 out["cpu_ref"] = {"error": repr(e)}
-        if world == 1 and not args.no_fp64_leg and args.dtype == "f32":
+        if args.full and world == 1 and not args.no_fp64_leg and args.dtype == "f32":
             try:
                 out["fp64"] = fp64_leg(args, ref_loss)
             except Exception as e:
@@ -647,16 +539,143 @@ def main():
         dist.destroy_process_group()
 
 
+def rooflines(args, st, ops, cfg, ev, work, world, m, n_loc, k, nnz):
+    """--full: the rooflines of the CD solve and of the SpMM-like update, from the per-phase HIP events (the eager re-run after graph
+    replays, or the eager timed loop itself) and the kernels' work counters of the timed steps; returns (roof_cd, roof_rhs, cd_dominant)."""
+    from rcppml_amd import als
+    sv = 4 if args.dtype == "f32" else 8
+    bytes_h = algorithmic_bytes_rhs(nnz, n_loc, m, k, sv)
+    bytes_w = algorithmic_bytes_rhs(nnz, m, n_loc, k, sv)
+    cnt_h, ms_h = ev.get("rhs_H", (0, 0.0))
+    cnt_w, ms_w = ev.get("rhs_W", (0, 0.0))
+    launches = cnt_h + cnt_w
+    avg_s = (ms_h + ms_w) / max(launches, 1) * 1e-3
+    avg_bytes = (bytes_h * cnt_h + bytes_w * cnt_w) / max(launches, 1)
+    achieved = avg_bytes / max(avg_s, 1e-12) / 1e9
+    planned = bool(st.A.get("plans")) and bool(st.At.get("plans"))
+    plan_info = {side: csc["plans"][k].info() for side, csc in (("H", st.A), ("W", st.At)) if csc.get("plans", {}).get(k)}
+    # delivery rate of the gathered k-rows of F (nnz * k * s_v per launch: not compulsory HBM traffic, SURVEY.md 8d) against
+    # the two on-chip ceilings: vector L1 (64 B/clk/CU) for the gather kernel, LDS (256 B/clk/CU, ds_read_b128) for the
+    # row-tiled kernel
+    gather_bytes = float(nnz) * k * sv
+    deliv = gather_bytes / max(avg_s, 1e-12) / 1e12
+    roof_rhs = {"bound": "hbm",
+                "kernel": ("rhs_win_kernel + rhs_win_finish_kernel: SpMM-like B = F * A(:,j), F through a ring of LDS row tiles, nonzeros scheduled "
+                           "over a sliding window, partition slabs + overflow summed by the finishing pass; both half-updates"
+                           if planned and all(p.get("kind", "window") == "window" for p in plan_info.values()) else
+                           "rhs_tiled_kernel + spill / reduce kernels (slab plan): SpMM-like B = F * A(:,j), both half-updates"
+                           if planned else "rhs_stage_kernel (gather form; SpMM-like B = F * A(:,j), both half-updates)"),
+                "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
+                "traffic": None, "algorithmic_bytes_per_launch": avg_bytes, "avg_launch_ms": avg_s * 1e3,
+                "rhs_H_ms": ms_h / max(cnt_h, 1), "rhs_W_ms": ms_w / max(cnt_w, 1),
+                "gathered_row_delivery": {"achieved_TBps": deliv, "bytes_per_launch": gather_bytes,
+                                          "frac_of_L1_39.3TBps": deliv / 39.3, "frac_of_LDS_157TBps": deliv / 157.3},
+                "plan": plan_info}
+    # NNLS solve: algorithmic flops = 2 k^2 per column and sweep (k coordinate steps, each a k-long residual
+    # update; nnls_batch.hpp:96-121), sweeps counted by the kernels themselves.  fp32 k<=64 runs these updates
+    # as v_mfma_f32_32x32x2_f32 (dense f32 MFMA peak 157.3 TFLOP/s = the f32 vector rate); the phase time
+    # also holds the Gram padding/permutation helper kernel (a few us; the column-ordering kernels ride in the launches of
+    # the scaling pass since round 5: phase "scale").
+    cnt_sh, ms_sh = ev.get("solve_H", (0, 0.0))
+    cnt_sw, ms_sw = ev.get("solve_W", (0, 0.0))
+    cd_launches = cnt_sh + cnt_sw
+    cd_s = (ms_sh + ms_sw) / max(cd_launches, 1) * 1e-3
+    cd_flops = 2.0 * k * k * work["cd_column_sweeps"] / max(cd_launches, 1)
+    cd_peak = 157.3 if args.dtype == "f32" else 78.6
+    roof_cd = None
+    if args.solver == "cd" and work["cd_columns"] > 0:
+        # the two launches run different kernels at the default sizes (32-column MFMA tiles for H, 16-column tiles for
+        # the W side, which has fewer tiles than SIMDs): `roofline` is the H-side kernel, the longer of the two; the
+        # counted column-sweeps are split between the sides in the proportion of the last iteration's per-column sweeps
+        share_h = ms_sh / max(ms_sh + ms_sw, 1e-12)
+        try:
+            sw_h = float(st.ops._order["H"]["sweeps"].sum().item())
+            sw_w = float(st.ops._order["W"]["sweeps"].sum().item())
+            if sw_h + sw_w > 0:
+                share_h = sw_h / (sw_h + sw_w)
+        except Exception:
+            pass
+        # idle-slot fraction of the MFMA tiles: a wave sweeps until its slowest column has converged, so a tile of T
+        # columns spends T * max(sweeps) column-sweeps for sum(sweeps) useful ones (last iteration's counts, in the
+        # work order the kernel used: sweep-sorted for the H side, natural for the W side)
+        idle = {}
+        try:
+            for side, tile in (("H", 32), ("W", 16 if n_loc >= 0 and m <= 32 * 1024 else 32)):
+                o = st.ops._order[side]
+                sw = o["sweeps"].cpu().numpy().astype(np.int64)
+                use_order = o["valid"] and cfg.cd_tol > 0 and sw.shape[0] >= als.ORDER_MIN_COLUMNS
+                # (with the fused tail o["order"] already ranks THESE counts for the next solve: the copy the last solve kept)
+                sq = sw[o.get("order_used", o["order"]).cpu().numpy()] if use_order else sw
+                pad = (-len(sq)) % tile
+                tl = np.concatenate([sq, np.zeros(pad, np.int64)]).reshape(-1, tile)
+                idle[side] = float(1.0 - tl.sum() / max(1, (tl.max(axis=1) * tile).sum()))
+        except Exception:
+            pass
+        # what solve_cd_impl.hip.h launches for variant = auto: fp32 k <= 128 -> 32-column v_mfma_f32_32x32x2 tiles (16-column
+        # v_mfma_f32_16x16x4 tiles on sides with fewer than 4 tiles per CU, k <= 64; lane = column 4x4 blocks for k <= 32 on large
+        # sides); fp64 k <= 128 -> 16-column v_mfma_f64_16x16x4 tiles; above 128: the VALU lane-group kernel
+        mfma = k <= 128 and args.variant == "auto"
+        f32 = args.dtype == "f32"
+        w_small16 = f32 and k <= 64 and (m + 31) // 32 < 4 * 256
+        flops_h = 2.0 * k * k * work["cd_column_sweeps"] * share_h / max(cnt_sh, 1)
+        flops_w = 2.0 * k * k * work["cd_column_sweeps"] * (1.0 - share_h) / max(cnt_sw, 1)
+        s_h, s_w = ms_sh / max(cnt_sh, 1) * 1e-3, ms_sw / max(cnt_sw, 1) * 1e-3
+        tf_h, tf_w = flops_h / max(s_h, 1e-12) / 1e12, flops_w / max(s_w, 1e-12) / 1e12
+        tf = cd_flops / max(cd_s, 1e-12) / 1e12
+        roof_cd = {"bound": "mfma" if mfma else "valu",
+                   "kernel": (("cd_mfma_kernel (coordinate-descent NNLS on 32-column v_mfma_f32_32x32x2 tiles, H half-update)" if f32 else
+                               "cd_mfma64_kernel<double> (coordinate-descent NNLS on 16-column v_mfma_f64_16x16x4 tiles, H half-update)") if mfma
+                              else "cd_group_kernel (VALU lane groups; rank above 128 or a forced variant), H half-update"),
+                   "achieved": tf_h, "peak": cd_peak, "unit": "TFLOP/s", "frac": tf_h / cd_peak, "traffic": None,
+                   "algorithmic_flops_per_launch": flops_h, "avg_launch_ms": s_h * 1e3,
+                   "mean_sweeps_per_column": work["cd_column_sweeps"] / work["cd_columns"],
+                   "idle_slot_fraction": idle,
+                   "solve_H_ms": s_h * 1e3, "solve_W_ms": s_w * 1e3,
+                   "w_side": {"kernel": ("cd_mfma64_kernel<float> (16-column v_mfma_f32_16x16x4 tiles)" if (mfma and w_small16) else "same kernel"),
+                              "achieved": tf_w, "frac": tf_w / cd_peak, "avg_launch_ms": s_w * 1e3,
+                              "algorithmic_flops_per_launch": flops_w},
+                   "both_sides": {"achieved": tf, "frac": tf / cd_peak, "avg_launch_ms": cd_s * 1e3}}
+        if mfma and f32:
+            # the kernel's own ceiling (DESIGN 4.1): per coordinate pair a wave issues ceil(k / 32) f32 MFMAs of 64 cycles each and a
+            # dependent chain of ~100 VALU / LDS cycles that cannot overlap them on gfx950 (profiles/r03_issue_probe.txt); idle slots and
+            # the residency tail come on top
+            mf = 64.0 * ((k + 31) // 32)
+            roof_cd["ceiling_frac"] = mf / (mf + 100.0)
+            roof_cd["ceiling_what"] = ("MFMA-issue share of a coordinate pair's cycles (%d MFMA + ~100 dependent VALU / LDS, mutually exclusive on "
+                                       "the f32 pipes): what `frac` would be with no idle column slot and no residency tail" % int(mf))
+    cd_dominant = roof_cd is not None and (ms_sh + ms_sw) > (ms_h + ms_w)
+    # HBM/fabric bytes per launch from the committed rocprofv3 PMC passes of this same command (FETCH_SIZE x2 per the
+    # gfx950 correction + WRITE_SIZE, profiles/summarize.py); only meaningful for the default workload
+    default_wl = (m, n_loc, k, args.dtype, world) == (20000, 100000, 64, "f32", 1)
+    import glob
+    pmcs = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "r[0-9][0-9]_pmc.json")))
+    pmc_path = pmcs[-1] if pmcs else ""          # the latest round's counter passes
+    pmc_name = "profiles/" + os.path.basename(pmc_path)
+    if default_wl and os.path.exists(pmc_path):
+        try:
+            pmc = json.load(open(pmc_path))
+            if "rhs_per_launch" in pmc:
+                roof_rhs["traffic"] = pmc["rhs_per_launch"]["hbm_bytes_per_launch"]
+                roof_rhs["traffic_over_algorithmic"] = roof_rhs["traffic"] / avg_bytes
+                roof_rhs["traffic_source"] = pmc_name + " (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes; all kernels of one rhs call, mean of both sides)"
+            for name, v in pmc.get("kernels", {}).items():
+                if roof_cd is not None and "cd_mfma_kernel" in name:
+                    roof_cd["traffic"] = v["hbm_bytes_per_launch"]
+                    roof_cd["traffic_source"] = pmc_name
+        except Exception:
+            pass
+    return roof_cd, roof_rhs, cd_dominant
+
+
 def bench_c1(args):
     """BASELINE configs[0]: data(hawaiibirds) (183 x 1183, 30 815 nonzeros), k = 10, MSE, fp32.  The whole fit is ONE persistent kernel on
     one XCD (rcppml_amd/csrc/kernels_small.hip.h): a "step" is one ALS iteration inside it -- the warm-up launch runs W iterations from
     the SplitMix64 start, the timed launch the next K (iter0 = W: warm starts, no iteration-0 quirk), each bracketed by a device
-    synchronise.  Beside it: the same K iterations from the start (`fit_from_start`, the reference's protocol), the multi-launch loop
+    synchronise.  Beside it (--full): the same K iterations from the start (`fit_from_start`, the reference's protocol), the multi-launch loop
     on the same input (`multi_launch`), the plugin call end to end with the one-kernel path on and off, and the CPU oracle's whole
     fit at several thread counts (`cpu_baseline` = the best of them; 256 OpenMP threads on 1 366 columns is not it)."""
     import torch
     from rcppml_amd import _abi, als, data
-    from oracle import oracle as O
     fx = np.load(os.path.join(ROOT, "tests", "golden", "hawaiibirds.npz"))
     A = data.CSC(tuple(int(v) for v in fx["shape"]), fx["p"], fx["i"], fx["x"])
     At = A.transpose()
@@ -703,6 +722,32 @@ def bench_c1(args):
     outputs = None
     if args.dump_outputs:
         outputs = dict(W_T=state[0].cpu().numpy(), H=state[1].cpu().numpy(), d=state[2].cpu().numpy(), loss=res[2:3].cpu().numpy())
+    total_iters = max(args.warmup, 1) + args.steps
+    alg_bytes = 2 * (A.nnz * (4 + sv) + (m + n + 2) * 4) + 4 * k * (m + n) * sv        # both sparse passes + factors read and written
+    line = {
+        "metric": "ALS updates/sec (cols solved/s), k=%d sparse NMF" % k,
+        "value": args.steps * (m + n) / dt, "unit": "cols/s", "n_gpus": 1, "steps": args.steps, "warmup": max(args.warmup, 1),
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": args.dtype, "data": "fixture (tests/golden/hawaiibirds.npz = the reference's data/hawaiibirds.rda)",
+        "config": {"workload": "configs[0]: data(hawaiibirds) %dx%d, nnz %d, k=%d, MSE, %s, L1 row normalisation, loss every iteration; the whole "
+                               "fit = one persistent kernel on one XCD" % (m, n, A.nnz, k, "coordinate-descent NNLS (cd_maxit=%d, cd_tol=1e-8)" % args.cd_maxit
+                                                                           if solver == 0 else "Cholesky + clip"),
+                   "rows": m, "cols_per_gpu": n, "nnz_per_gpu": A.nnz, "k": k, "solver": args.solver, "parallelism": "one GPU, one XCD (32 workgroups)"},
+        "roofline": {"bound": "hbm", "kernel": "als_small_kernel (the whole ALS loop; 4 grid barriers per iteration among 32 workgroups of XCD 0)",
+                     "achieved": alg_bytes / (dt / args.steps) / 1e9, "peak": 8000.0, "unit": "GB/s", "frac": alg_bytes / (dt / args.steps) / 1e9 / 8000.0,
+                     "traffic": None, "algorithmic_bytes_per_launch": alg_bytes * args.steps, "avg_launch_ms": dt * 1e3,
+                     "note": "latency-bound by construction: %.0f KB of algorithmic traffic per iteration, all of it L2-resident; the iteration is four "
+                             "barriers (0.8 us each, profiles/r06_grid_barrier.txt) plus the dependent chains of one column's sparse product and "
+                             "solve per phase" % (alg_bytes / 1e3)},
+        "inside_the_kernel": inside,
+        "phases_ms_per_step": {}, "launch": "one persistent kernel for all %d iterations" % args.steps, "final_loss": final_loss, "world_size_seen": 1,
+    }
+    if not args.full:
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
+        print(json.dumps(line))
+        return
+    from oracle import oracle as O
     reps = []
     for _ in range(15):                                 # the same region again (fresh start + warm-up each time): spread of a 0.5 ms measurement
         reset(); launch(max(args.warmup, 1), 0)
@@ -758,30 +803,12 @@ def bench_c1(args):
             os.environ.pop("RCPPML_GPU_NO_SMALL", None)
         else:
             os.environ["RCPPML_GPU_NO_SMALL"] = old
-    total_iters = max(args.warmup, 1) + args.steps
-    alg_bytes = 2 * (A.nnz * (4 + sv) + (m + n + 2) * 4) + 4 * k * (m + n) * sv        # both sparse passes + factors read and written
-    line = {
-        "metric": "ALS updates/sec (cols solved/s), k=%d sparse NMF" % k,
-        "value": args.steps * (m + n) / dt, "unit": "cols/s", "n_gpus": 1, "steps": args.steps, "warmup": max(args.warmup, 1),
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": args.dtype, "data": "fixture (tests/golden/hawaiibirds.npz = the reference's data/hawaiibirds.rda)",
-        "config": {"workload": "configs[0]: data(hawaiibirds) %dx%d, nnz %d, k=%d, MSE, %s, L1 row normalisation, loss every iteration; the whole "
-                               "fit = one persistent kernel on one XCD" % (m, n, A.nnz, k, "coordinate-descent NNLS (cd_maxit=%d, cd_tol=1e-8)" % args.cd_maxit
-                                                                           if solver == 0 else "Cholesky + clip"),
-                   "rows": m, "cols_per_gpu": n, "nnz_per_gpu": A.nnz, "k": k, "solver": args.solver, "parallelism": "one GPU, one XCD (32 workgroups)"},
-        "roofline": {"bound": "hbm", "kernel": "als_small_kernel (the whole ALS loop; 4 grid barriers per iteration among 32 workgroups of XCD 0)",
-                     "achieved": alg_bytes / (dt / args.steps) / 1e9, "peak": 8000.0, "unit": "GB/s", "frac": alg_bytes / (dt / args.steps) / 1e9 / 8000.0,
-                     "traffic": None, "algorithmic_bytes_per_launch": alg_bytes * args.steps, "avg_launch_ms": dt * 1e3,
-                     "note": "latency-bound by construction: %.0f KB of algorithmic traffic per iteration, all of it L2-resident; the iteration is four "
-                             "barriers (0.8 us each, profiles/r06_grid_barrier.txt) plus the dependent chains of one column's sparse product and "
-                             "solve per phase" % (alg_bytes / 1e3)},
+    line.update({
         "repeats_ms_per_step": {"median": float(np.median(reps)), "min": float(np.min(reps)), "max": float(np.max(reps)), "n": len(reps)},
         "fit_from_start": {"iterations": args.steps, "ms_per_step": float(np.median(starts)), "value": (m + n) / (float(np.median(starts)) * 1e-3), "unit": "cols/s",
                            "launch": "one kernel", "final_loss": from_start_loss, "what": "iterations 0 .. %d from the SplitMix64(%d) start, tol = 0, loss every "
                            "iteration, one launch + one synchronise (median of %d)" % (args.steps - 1, args.seed, len(starts))},
-        "inside_the_kernel": inside, "multi_launch": multi, "plugin_pcie_inclusive": plug,
-        "phases_ms_per_step": {}, "launch": "one persistent kernel for all %d iterations" % args.steps, "final_loss": final_loss, "world_size_seen": 1,
-    }
+        "multi_launch": multi, "plugin_pcie_inclusive": plug})
     if multi and "ms_per_step" in multi:
         line["speedup_vs_multi_launch"] = multi["ms_per_step"] / line["ms_per_step"]
     W.copy_(state[0]); H.copy_(state[1]); d.copy_(state[2])
@@ -880,6 +907,22 @@ def bench_c5(args):
         outputs = dict(W_T=W.cpu().numpy(), H=H.cpu().numpy(), d=d.cpu().numpy(), theta=theta.cpu().numpy(), loss=out4[:1].cpu().numpy())
     ev = ops.event_ms()
     phases = {name: round(ms / args.steps, 4) for name, (c, ms) in sorted(ev.items())}
+    line = {
+        "metric": "ALS updates/sec (cols solved/s), k=%d sparse NMF, loss = nb" % k,
+        "value": args.steps * (m + n) / dt, "unit": "cols/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": "configs[4]: NB counts %dx%d (Poisson-Gamma, size 5, %.3g%%-dense CSC), k=%d, loss = 'nb' IRLS "
+                               "(irls_max_iter=%d, irls_tol=%g, cd_maxit=%d), per-row size by method of moments, NB likelihood every "
+                               "iteration" % (m, n, 100.0 * A.nnz / (m * float(n)), k, irls_max_iter, irls_tol, args.cd_maxit),
+                   "rows": m, "cols_per_gpu": n, "nnz_per_gpu": A.nnz, "k": k, "solver": "irls+cd", "parallelism": "one GPU"},
+        "phases_ms_per_step": phases, "launch": "eager", "final_loss": final_loss, "world_size_seen": 1,
+    }
+    if not args.full:
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
+        print(json.dumps(line))
+        return
     # ---- work of one more iteration, counted by the kernels themselves (outside the timed region; two atomics per column)
     ops.ctx.set_option(ops._abi.OPT_CD_COUNT_NOOP, 1)
     counts = {}
@@ -906,24 +949,14 @@ def bench_c5(args):
                       # every pass re-reads the column's (row, value) pairs and gathers one k-row of F per nonzero
                       "gathered_row_TBps": nzp * k * sv / sec / 1e12, "csc_stream_GBps": nzp * (4 + sv) / sec / 1e9}
     big = "H" if roof["H"]["avg_launch_ms"] >= roof["W"]["avg_launch_ms"] else "W"
-    line = {
-        "metric": "ALS updates/sec (cols solved/s), k=%d sparse NMF, loss = nb" % k,
-        "value": args.steps * (m + n) / dt, "unit": "cols/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": "configs[4]: NB counts %dx%d (Poisson-Gamma, size 5, %.3g%%-dense CSC), k=%d, loss = 'nb' IRLS "
-                               "(irls_max_iter=%d, irls_tol=%g, cd_maxit=%d), per-row size by method of moments, NB likelihood every "
-                               "iteration" % (m, n, 100.0 * A.nnz / (m * float(n)), k, irls_max_iter, irls_tol, args.cd_maxit),
-                   "rows": m, "cols_per_gpu": n, "nnz_per_gpu": A.nnz, "k": k, "solver": "irls+cd", "parallelism": "one GPU"},
+    line.update({
         "roofline": dict({"bound": "mfma", "unit": "TFLOP/s", "peak": 157.3 if args.dtype == "f32" else 78.6, "traffic": None,
                           "kernel": "irls_nb_mfma32_kernel (%s half-update: per-column weighted Gram G + F diag(w - 1) F^T on "
                                     "v_mfma_f32_32x32x2_f32, one wave per column, then the CD solve)" % big,
                           "counted": "2 k_pad^2 flops per nonzero and IRLS pass (the weighted Gram on the matrix cores) + 2 k_pad^2 per column-sweep of "
                                      "the per-pass CD solves (VALU, same f32 peak); passes and sweeps counted by the kernels in one extra, untimed "
                                      "iteration; `frac_weighted_gram_only` is the figure of rounds 3-5"}, **roof[big]),
-        "roofline_other_side": roof["W" if big == "H" else "H"],
-        "phases_ms_per_step": phases, "launch": "eager", "final_loss": final_loss, "world_size_seen": 1,
-    }
+        "roofline_other_side": roof["W" if big == "H" else "H"]})
     if not args.no_cpu_ref:
         # the metric's second half for this configuration: a WHOLE fit (3 outer NB iterations: IRLS half-updates, size updates,
         # likelihood) through the 73-pointer fp64 entry against the CPU oracle's fp64 fit from the same starting factors
@@ -1085,7 +1118,7 @@ def cd_noop_fraction(st, ops, cfg, k):
 def fp64_leg(args, ref_loss):
     """The same workload in fp64 (parity mode) as a child process: ms per step, cols/s and the loss deviation from the CPU
     reference fit.  Reported beside the fp32 headline; never `value`."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--dtype", "f64", "--init-f32", "--no-cpu-baseline", "--no-plugin-figure",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--dtype", "f64", "--init-f32", "--no-cpu-baseline", "--no-plugin-figure",
            "--no-cpu-ref", "--no-fp64-leg", "--steps", str(args.steps), "--warmup", str(args.warmup), "--config", args.config,
            "--rows", str(args.rows), "--cols", str(args.cols), "--density", str(args.density), "--k", str(args.k),
            "--solver", args.solver, "--cd-maxit", str(args.cd_maxit), "--seed", str(args.seed)]

@@ -59,7 +59,7 @@ if calls:
 json.dump(doc, open(os.path.join(dst, tag + "_pmc.json"), "w"), indent=1)
 
 with open(os.path.join(dst, tag + "_summary.md"), "w") as f:
-    f.write("# rocprofv3 summary `%s`\n\nCommand: `python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-plugin-figure` "
+    f.write("# rocprofv3 summary `%s`\n\nCommand: `python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-plugin-figure` "
             "(profiles/run_rocprof.sh; pass 1 `--kernel-trace --stats`, passes 2/3 `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE`).\n\n" % tag)
     f.write("| kernel | calls | avg us | total ms | % |\n|---|---|---|---|---|\n")
     for r in keep:

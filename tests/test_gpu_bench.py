@@ -1,6 +1,7 @@
 """bench.py end to end on a reduced shape: the JSON line carries what the driver contract and the tier's measurement rules
 ask for, and the two launch modes (replays of one captured hipGraph / eager loop) time the same arithmetic -- identical
-final loss, identical work counters."""
+final loss, identical work counters.  The figures beyond the headline (rooflines, per-phase times, CPU legs, ...) need
+`bench.py --full`; a plain run times the same steps and prints the headline alone."""
 import json
 import os
 import subprocess
@@ -13,10 +14,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*extra):
+def _run(*extra, full=True):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "3000", "--cols", "24000", "--density", "0.01", "--k", "64",
            "--steps", "4", "--warmup", "3", "--no-cpu-baseline", "--no-plugin-figure", "--no-cpu-ref", "--no-fp64-leg",
-           "--no-noop-count", *extra]
+           "--no-noop-count", *(["--full"] if full else []), *extra]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     return json.loads(out.stdout.strip().splitlines()[-1])
@@ -85,6 +86,43 @@ def test_bench_dump_outputs_follow_the_timed_steps(tmp_path):
     assert not np.array_equal(a["H"], dump("e", "--steps", "3")["H"])
 
 
+def test_bench_plain_line_times_the_steps_of_the_full_one(tmp_path):
+    """Without --full the run sets up, warms up, times the steps, dumps and prints the headline: the same timed steps as a --full
+    run (same loss, same dumped outputs, graph replays or the eager loop alike) and none of the figures that take runs of their own."""
+    for mode in ((), ("--no-graph",)):
+        p = _run("--dump-outputs", str(tmp_path / "plain"), *mode, full=False)
+        f = _run("--dump-outputs", str(tmp_path / "full"), *mode)
+        for key in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "launch", "fused_tail", "final_loss", "config"):
+            assert p[key] == f[key], key
+        assert abs(p["value"] - 4 * (3000 + 24000) / (p["ms_per_step"] * 4e-3)) / p["value"] < 1e-6
+        assert not {"roofline", "roofline_rhs", "roofline_cd", "fit_from_start", "cpu_baseline", "cpu_ref", "fp64", "cd_noop_steps",
+                    "plugin_pcie_inclusive"} & set(p)
+        assert p["eager_ms_per_step"] is None
+        # graph replays carry no HIP events (the eager re-run behind them is --full's); the eager loop records its phases as it runs
+        assert (p["phases_ms_per_step"] == {}) if not mode else (set(p["phases_ms_per_step"]) == set(f["phases_ms_per_step"]))
+        for name in ("H", "W_T", "d", "loss"):
+            assert np.array_equal(np.load(str(tmp_path / "plain" / (name + ".npy"))), np.load(str(tmp_path / "full" / (name + ".npy")))), name
+
+
+def test_bench_plain_c1_and_c5_lines():
+    """--config c1 / c5 without --full: the timed launch(es) and the line, without the extra runs (repeats, fit from the start, multi-launch
+    loop, plugin call, counted iteration, CPU legs)."""
+    for cfg in (["--config", "c1", "--steps", "6", "--warmup", "3"],
+                ["--config", "c5", "--rows", "2000", "--cols", "12000", "--steps", "3", "--warmup", "2"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *cfg], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads(out.stdout.strip().splitlines()[-1])
+        steps, cols = (6, 183 + 1183) if cfg[1] == "c1" else (3, 2000 + 12000)
+        assert d["steps"] == steps and d["unit"] == "cols/s" and d["higher_is_better"] and d["dtype"] == "f32"
+        assert abs(d["value"] - steps * cols / (d["ms_per_step"] * steps * 1e-3)) / d["value"] < 1e-6 and d["final_loss"] == d["final_loss"]
+        assert not {"fit_from_start", "multi_launch", "plugin_pcie_inclusive", "repeats_ms_per_step", "roofline_other_side", "cpu_baseline",
+                    "cpu_ref"} & set(d)
+        if cfg[1] == "c1":
+            assert d["inside_the_kernel"]["kernel_us"] > 0
+        else:
+            assert set(d["phases_ms_per_step"]) >= {"solve_H", "solve_W", "nb_size_loss"} and "roofline" not in d
+
+
 def test_bench_line_carries_cpu_reference_deviation_and_fp64_leg():
     """BASELINE.json's metric is "cols solved/s + MSE vs CPU ref": the line holds the relative deviation of the fit's loss
     from the CPU reference fit (fp64 oracle, same inputs, same iteration count) for the fp32 headline AND for the fp64 leg, the
@@ -102,7 +140,7 @@ def test_bench_line_carries_cpu_reference_deviation_and_fp64_leg():
 
 def _run_full():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "3000", "--cols", "24000", "--density", "0.01", "--k", "64",
-           "--steps", "4", "--warmup", "3", "--no-cpu-baseline", "--no-plugin-figure"]
+           "--steps", "4", "--warmup", "3", "--no-cpu-baseline", "--no-plugin-figure", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     return json.loads(out.stdout.strip().splitlines()[-1])
@@ -169,7 +207,7 @@ def test_bench_c3_line_on_the_movielens_fixture():
     """--config c3: BASELINE configs[2] (movielens, k = 32, L1 = c(0, 0.1)) through the same loop; the fp64 leg stays inside the
     north star's 1e-6 of the CPU reference fit."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c3", "--steps", "4", "--warmup", "3", "--no-plugin-figure",
-           "--cpu-seconds", "1", "--no-noop-count"]
+           "--cpu-seconds", "1", "--no-noop-count", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -182,7 +220,7 @@ def test_bench_c5_line_reduced_shape():
     """--config c5 (NB IRLS) on a reduced shape: the line carries the weighted-Gram roofline with the passes the kernel counted
     (between 1 and irls_max_iter per column) and a CPU baseline of the same half-updates."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c5", "--rows", "2000", "--cols", "12000", "--steps", "3",
-           "--warmup", "2", "--cpu-seconds", "1"]
+           "--warmup", "2", "--cpu-seconds", "1", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -205,7 +243,7 @@ def test_bench_c1_line_one_kernel_fit():
     kernel, `inside_the_kernel` accounts for workgroup 0's clock, the same fit from the start and on the multi-launch loop are beside
     it, and the loss stays within the fp32 bar of the CPU reference fit."""
     for solver in ("cd", "chol"):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--solver", solver, "--steps", "6", "--warmup", "3"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--solver", solver, "--steps", "6", "--warmup", "3", "--full"]
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
         assert out.returncode == 0, out.stderr[-2000:]
         d = json.loads(out.stdout.strip().splitlines()[-1])

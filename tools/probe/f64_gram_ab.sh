@@ -11,8 +11,8 @@ for k in a.files:
     print(k, "bitwise equal:", bool(np.array_equal(a[k], b[k])), "symmetric:", bool(np.array_equal(b[k], b[k].T)))
 PY
 for rep in 1 2; do
-RCPPML_GPU_LIB_PATH=$PWD/tools/probe/old_lib/RcppML_gpu_old.so python bench.py --dtype f64 --steps 20 --warmup 3 --no-cpu-baseline --no-plugin-figure --no-cpu-ref --no-noop-count 2>/dev/null | python -c "
+RCPPML_GPU_LIB_PATH=$PWD/tools/probe/old_lib/RcppML_gpu_old.so python bench.py --full --dtype f64 --steps 20 --warmup 3 --no-cpu-baseline --no-plugin-figure --no-cpu-ref --no-noop-count 2>/dev/null | python -c "
 import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('old lib fp64 ms %.4f'%r['ms_per_step'], r['phases_ms_per_step'], 'loss %.12g'%r['final_loss'])"
-python bench.py --dtype f64 --steps 20 --warmup 3 --no-cpu-baseline --no-plugin-figure --no-cpu-ref --no-noop-count 2>/dev/null | python -c "
+python bench.py --full --dtype f64 --steps 20 --warmup 3 --no-cpu-baseline --no-plugin-figure --no-cpu-ref --no-noop-count 2>/dev/null | python -c "
 import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('new lib fp64 ms %.4f'%r['ms_per_step'], r['phases_ms_per_step'], 'loss %.12g'%r['final_loss'])"
 done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the non-temporal hints on the window rhs (slot-stream LDS-DMA loads): RcppML_gpu.so (nt) against
 # RcppML_gpu_np.so (make BUILD=build_np OUT=../lib/RcppML_gpu_np.so RWFLAGS=-DRW_SLOTS_DEFAULT_POLICY), alternating, on one box.
-B="--no-cpu-baseline --no-cpu-ref --no-fp64-leg --no-plugin-figure --no-noop-count"
+B="--full --no-cpu-baseline --no-cpu-ref --no-fp64-leg --no-plugin-figure --no-noop-count"
 for rep in 1 2 3; do
   for lib in RcppML_gpu RcppML_gpu_np; do
     RCPPML_GPU_LIB_PATH=$PWD/rcppml_amd/lib/$lib.so python bench.py $B 2>/dev/null | python -c "

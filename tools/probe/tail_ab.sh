@@ -8,7 +8,7 @@ out=gpurun_out/tail_ab.txt
 for rep in 1 2 3; do
   for mode in fused separate; do
     flag=""; [ $mode = separate ] && flag="--no-fused-tail"
-    python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-plugin-figure $flag > gpurun_out/tail_ab_$mode$rep.json 2> gpurun_out/tail_ab_$mode$rep.err
+    python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-plugin-figure $flag > ${out%.txt}_$mode$rep.json 2> ${out%.txt}_$mode$rep.err
     python - "$mode$rep" gpurun_out/tail_ab_$mode$rep.json >> $out <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
