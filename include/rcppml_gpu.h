@@ -384,6 +384,34 @@ RCPPML_GPU_API void rcppml_gpu_assess_plan(const int* labels, int* n, int* n_cla
         int* knn_folds, int* seed, int* out_init_idx, int* init_capacity, int* out_sil_samples, int* out_sil_counts,
         int* sil_capacity, int* out_fold_ids, int* fold_capacity, int* out_status);
 
+/* Distribution diagnostics (rcppml_amd/csrc/ops_distribution.hip): the device side of the reference's score_test_distribution,
+ * diagnose_zero_inflation and diagnose_dispersion (R/auto_distribution.R:194-452), fp64, with mu = (W diag(d)) H formed a tile at a
+ * time and never stored.  Build-defined: R does not call these entries.  The matrix comes as a CSC (col_ptr, row_idx, values, *nnz)
+ * or as a column-major m x n dense array: exactly one of col_ptr and dense is non-NULL.  The model: W_T (k x m), d (k), H (k x n).
+ * Refused (*out_status = -1, reason in rcppml_gpu_last_error, no output written): m, n or k below 1; both matrix forms or neither;
+ * a malformed CSC (row indices strictly increasing within each column); a non-finite value in the matrix or the model; arguments
+ * outside their range; a call that does not fit in free device memory (the message gives the byte count); no device.
+ *
+ * Score test over the observed entries (sparse: the stored values != 0; dense: all m*n), mu' = max(mu, *min_mu), r = x - mu':
+ * out_T[q] = mean(r^2 / mu'^powers[q] - 1) (1 <= *n_powers <= 8), *out_T_nb = mean((r^2 - mu') / mu'^2), *out_all_integer = every
+ * observed x integral, *out_count = the number of observed entries.  mu'^p is mu' * mu' for p = 2, 1 for p = 0, pow otherwise. */
+RCPPML_GPU_API void rcppml_gpu_score_test_double(const int* col_ptr, const int* row_idx, const double* values, int* nnz,
+        const double* dense, int* m, int* n, int* k, const double* W_T, const double* d, const double* H, const double* powers,
+        int* n_powers, double* min_mu, double* out_T, double* out_T_nb, int* out_all_integer, int64_t* out_count, int* out_status);
+/* Zero inflation: out_expected_row (m) / out_expected_col (n) = row / column sums of exp(-max(mu, 1e-8)) over all m*n entries;
+ * out_observed_row / out_observed_col = zeros per row / column (sparse: n - stored entries of the row, m - stored entries of the
+ * column, explicit zeros counting as stored; dense: entries == 0). */
+RCPPML_GPU_API void rcppml_gpu_zero_inflation_double(const int* col_ptr, const int* row_idx, const double* values, int* nnz,
+        const double* dense, int* m, int* n, int* k, const double* W_T, const double* d, const double* H, double* out_expected_row,
+        double* out_expected_col, double* out_observed_row, double* out_observed_col, int* out_status);
+/* Dispersion: phi = (x - mu')^2 / mu'^*power over all m*n entries (x = 0 where a CSC stores nothing), mu' = max(mu, *min_mu);
+ * trimmed means (R's mean(x, trim): the mean of the order statistics floor(N trim) + 1 .. N - floor(N trim), 0 <= *trim < 0.5)
+ * per row (out_row_phi, m), per column (out_col_phi, n) and over all entries (*out_global_phi).  Needs 8 m n bytes of device memory
+ * for phi beyond the inputs. */
+RCPPML_GPU_API void rcppml_gpu_dispersion_double(const int* col_ptr, const int* row_idx, const double* values, int* nnz,
+        const double* dense, int* m, int* n, int* k, const double* W_T, const double* d, const double* H, double* power,
+        double* min_mu, double* trim, double* out_row_phi, double* out_col_phi, double* out_global_phi, int* out_status);
+
 /* Last error text of the calling thread ("" if none). */
 RCPPML_GPU_API const char* rcppml_gpu_last_error(void);
 

@@ -7,6 +7,8 @@ Layout (only what the path needs):
   cluster.py bipartition() / dclust(): mirror of the R surface on the HIP clustering path (csrc/ops_cluster.hip)
   svd.py     svd() / pca(): mirror of the R surface on the HIP truncated-SVD path (csrc/ops_svd.hip)
   assess.py  assess() / knn(): mirror of the R surface on the HIP embedding-assessment path (csrc/ops_assess.hip)
+  distribution.py score_test_distribution() / diagnose_zero_inflation() / diagnose_dispersion() / auto_nmf_distribution(): mirror of
+             the R surface on the HIP distribution-diagnostics path (csrc/ops_distribution.hip)
   als.py     one-process-per-GPU column-sharded ALS loop over torch.distributed (RCCL): Comm, ShardedALS, HipOps
   data.py    synthetic inputs (restatement of R/simulateNMF.R) and CSC helpers
 """

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_bipartition_double", "rcppml_gpu_dclust_double", "rcppml_gpu_bipartition_ex", "rcppml_gpu_dclust_ex",
     "rcppml_gpu_svd_pca_double", "rcppml_gpu_svd_pca_float", "rcppml_gpu_svd_pca_dense_double", "rcppml_gpu_svd_pca_dense_float",
     "rcppml_gpu_assess", "rcppml_gpu_assess_ex", "rcppml_gpu_knn_float", "rcppml_gpu_assess_plan",
+    "rcppml_gpu_score_test_double", "rcppml_gpu_zero_inflation_double", "rcppml_gpu_dispersion_double",
 ]
 
 
@@ -986,4 +987,72 @@ def assess_plan(labels, n_classes, *, nstart=10, spc=200, folds=5, seed=42, capa
         tot = int(np.sum(np.maximum(counts[:n_classes], 0)))
         r.update(init=init[:max(nstart, 0) * n_classes].reshape(max(nstart, 0), n_classes), sil_counts=counts[:n_classes].copy(),
                  sil_samples=samples[:tot].copy(), fold_ids=folds_out[:n].copy())
+    return r
+
+
+# ----------------------------------------------------------------------------- distribution diagnostics (ops_distribution.hip)
+def _dist_head(csc, dense, m, n, k, W_T, d, H):
+    """The shared head (col_ptr, row_idx, values, nnz, dense, m, n, k, W_T, d, H) and the arrays to keep alive.  csc: an object with
+    p / i / x (data.CSC) or a (p, i, x) tuple, or None; dense: m x n (any order; handed over column-major) or None.  W_T: (m, k)
+    row-major (= k x m), d: (k), H: (n, k) row-major (= k x n)."""
+    keep = []
+    if csc is not None:
+        p, i, x = (csc.p, csc.i, csc.x) if hasattr(csc, "p") else csc
+        p = np.ascontiguousarray(p, np.int32); i = np.ascontiguousarray(i, np.int32); x = np.ascontiguousarray(x, np.float64)
+        keep += [p, i, x]
+        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(x.shape[0])]
+    else:
+        head = [None, None, None, _ci(0)]
+    if dense is not None:
+        dn = np.asfortranarray(dense, np.float64)
+        keep.append(dn)
+        head.append(_np_ptr(dn))
+    else:
+        head.append(None)
+    W_T = np.ascontiguousarray(W_T, np.float64); d = np.ascontiguousarray(d, np.float64); H = np.ascontiguousarray(H, np.float64)
+    keep += [W_T, d, H]
+    head += [_ci(m), _ci(n), _ci(k), _np_ptr(W_T), _np_ptr(d), _np_ptr(H)]
+    return head, keep
+
+
+def score_test_double(csc, dense, m, n, k, W_T, d, H, powers, min_mu=1e-6, init=-7.0):
+    """rcppml_gpu_score_test_double: dict(status, error, T (per power), T_nb, all_integer, count, buffers).  Outputs start at `init`
+    (a refused call leaves them so)."""
+    head, keep = _dist_head(csc, dense, m, n, k, W_T, d, H)
+    pw = np.ascontiguousarray(powers, np.float64).reshape(-1)
+    T = np.full(max(pw.shape[0], 1), init)
+    tnb, allint, cnt, st = C.c_double(init), C.c_int(-7), C.c_int64(-7), C.c_int(-99)
+    lib().rcppml_gpu_score_test_double(*head, _np_ptr(pw), _ci(pw.shape[0]), _cd(min_mu), _np_ptr(T), C.byref(tnb), C.byref(allint),
+                                       C.byref(cnt), C.byref(st))
+    del keep
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(T, tnb.value, allint.value, cnt.value))
+    if st.value == 0:
+        r.update(T=T[:pw.shape[0]].copy(), T_nb=tnb.value, all_integer=bool(allint.value), count=int(cnt.value))
+    return r
+
+
+def zero_inflation_double(csc, dense, m, n, k, W_T, d, H, init=-7.0):
+    """rcppml_gpu_zero_inflation_double: dict(status, error, expected_row, expected_col, observed_row, observed_col, buffers)."""
+    head, keep = _dist_head(csc, dense, m, n, k, W_T, d, H)
+    bufs = [np.full(max(v, 1), init) for v in (m, n, m, n)]
+    st = C.c_int(-99)
+    lib().rcppml_gpu_zero_inflation_double(*head, *[_np_ptr(b) for b in bufs], C.byref(st))
+    del keep
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=bufs)
+    if st.value == 0:
+        r.update(expected_row=bufs[0][:m].copy(), expected_col=bufs[1][:n].copy(), observed_row=bufs[2][:m].copy(),
+                 observed_col=bufs[3][:n].copy())
+    return r
+
+
+def dispersion_double(csc, dense, m, n, k, W_T, d, H, power, min_mu=1e-6, trim=0.1, init=-7.0):
+    """rcppml_gpu_dispersion_double: dict(status, error, row_phi (m), col_phi (n), global_phi, buffers)."""
+    head, keep = _dist_head(csc, dense, m, n, k, W_T, d, H)
+    rp, cp, gp = np.full(max(m, 1), init), np.full(max(n, 1), init), C.c_double(init)
+    st = C.c_int(-99)
+    lib().rcppml_gpu_dispersion_double(*head, _cd(power), _cd(min_mu), _cd(trim), _np_ptr(rp), _np_ptr(cp), C.byref(gp), C.byref(st))
+    del keep
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(rp, cp, gp.value))
+    if st.value == 0:
+        r.update(row_phi=rp[:m].copy(), col_phi=cp[:n].copy(), global_phi=gp.value)
     return r

@@ -2417,6 +2417,20 @@ __device__ __forceinline__ double dist_loss_term(int loss_type, double y, double
     return -lgamma(y + r) + lgamma(r) - r * log(r / (r + mu)) - y * log(mu / (r + mu));
 }
 
+// The per-nonzero gather p = sum_f d_f W_T(f,row) H(f,j) of one wavefront (lanes stride the factors, butterfly sum: every lane
+// returns the same value).  Shared by loss_nonzeros_kernel and the distribution diagnostics (kernels_distribution.hip.h).
+template <class T>
+__device__ __forceinline__ double wave_pred(const T* __restrict__ W_T, const T* __restrict__ d, const T* __restrict__ H, int row,
+                                            int64_t j, int k, int lane) {
+    T p = T(0);
+    for (int f = lane; f < k; f += 64)
+        p += (W_T[(int64_t)row * k + f] * d[f]) * H[j * (int64_t)k + f];
+    double pd = static_cast<double>(p);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) pd += __shfl_xor(pd, off, 64);
+    return pd;
+}
+
 // Loss over (unmasked) nonzeros, fp64 accumulation, one wavefront per column
 // (reference nmf/masked_nnls.hpp:250-282; also the nonzero pass of evaluate()):
 //   partial[2b]   = sum (a - p)^2,  partial[2b+1] = sum p^2,   p = sum_f d_f W_T(f,i) H(f,j)
@@ -2440,12 +2454,7 @@ __global__ __launch_bounds__(256) void loss_nonzeros_kernel(
             const int row = rowidx[t];
             while (ms < me && mask_i[ms] < row) ++ms;
             if (ms < me && mask_i[ms] == row) continue;
-            T p = T(0);
-            for (int f = lane; f < k; f += 64)
-                p += (W_T[(int64_t)row * k + f] * d[f]) * H[j * (int64_t)k + f];
-            double pd = static_cast<double>(p);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) pd += __shfl_xor(pd, off, 64);
+            const double pd = wave_pred(W_T, d, H, row, j, k, lane);
             if (loss_type == 0) {
                 const double df = static_cast<double>(vals[t]) - pd;
                 acc += df * df;   // identical in all lanes
