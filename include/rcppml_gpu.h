@@ -412,6 +412,36 @@ RCPPML_GPU_API void rcppml_gpu_dispersion_double(const int* col_ptr, const int* 
         const double* dense, int* m, int* n, int* k, const double* W_T, const double* d, const double* H, double* power,
         double* min_mu, double* trim, double* out_row_phi, double* out_col_phi, double* out_global_phi, int* out_status);
 
+/* Consensus clustering (rcppml_amd/csrc/ops_consensus.hip): what the reference's consensus_nmf does after its fits
+ * (R/consensus.R:102-137).  Build-defined: R has no hook for these entries (its consensus stage runs in R and in c_knn_jaccard,
+ * src/RcppFunctions_utils.cpp:560-618).
+ *
+ * rcppml_gpu_consensus_double, on the device, replaces R/consensus.R:102-129 and c_knn_jaccard.  W_stack: *reps replicates, each
+ * k x m column-major like the ABI's W (sample i = k contiguous values).  *method 0 (hard): label = first maximum of a sample's k
+ * values (which.max), out_consensus[i, j] = (replicates with equal labels) / reps; out_labels (reps x m, 0-based, may be NULL) is
+ * written for this method only.  *method 1 (knn_jaccard), per replicate: samples scaled to unit 2-norm, sim = Wn Wn^T in fp64,
+ * actual_k = min(*knn, m - 1), the neighbour set of i = the actual_k largest sim[i, j], j != i,
+ * J[i, j] = |Si & Sj| / (2 actual_k - |Si & Sj|) (0 when the denominator is 0, 1 on the diagonal), J added in replicate order and
+ * divided by reps.  Two rules of this build where the reference is undefined: equal similarities go to the lower index
+ * (std::partial_sort leaves ties open), and a sample with zero norm has similarity 0 to every sample (R: NaN).  out_consensus: m x m
+ * (symmetric).  Device memory: 8 m^2 + the W stack + 4 reps m (hard) or 8 m ceil(m / 64) + a sim strip of at most 64 MiB
+ * (knn_jaccard).  Refused (*out_status = -1, reason in rcppml_gpu_last_error, no output written): a null pointer, m < 2, k < 1,
+ * reps < 1, method outside {0, 1}, knn < 1, a non-finite value in W_stack (negative values are accepted, as R accepts them), no HIP
+ * device, not enough free device memory (the message gives the byte count). */
+RCPPML_GPU_API void rcppml_gpu_consensus_double(const double* W_stack, int* m, int* k, int* reps, int* method, int* knn,
+        double* out_consensus, int* out_labels, int* out_status);
+/* Host only, no device work: hclust(as.dist(dist), "average"), cutree(k = *k_cut) and cor(as.dist(dist), cophenetic(hc))
+ * (replaces R/consensus.R:133-137).  dist: m x m column-major, only the entries below the diagonal are read.  Each step merges the
+ * pair with the smallest dissimilarity; among equal minima the pair with the smallest lower index, then the smallest upper index
+ * (this build's rule; believed to be R's hclust, not verified against R).  The merged cluster keeps the lower slot and is updated by
+ * Lance-Williams, (na da + nb db) / (na + nb).  out_merge: (m - 1) x 2 column-major in R's convention (negative: sample, 1-based;
+ * positive: step, 1-based; samples before clusters, the lower sample or earlier step first); out_height (m - 1): the merge
+ * dissimilarities; out_clusters (m): the last k_cut - 1 merges undone, clusters numbered 1..k_cut by first appearance;
+ * *out_cophenetic: Pearson correlation over the m (m - 1) / 2 pairs (two-pass, clamped to [-1, 1]), NaN when all dissimilarities or
+ * all merge heights are equal.  Refused: a null pointer, m < 2, k_cut outside [1, m], a non-finite dissimilarity. */
+RCPPML_GPU_API void rcppml_gpu_hclust_average_double(const double* dist, int* m, int* k_cut, int* out_merge, double* out_height,
+        int* out_clusters, double* out_cophenetic, int* out_status);
+
 /* Last error text of the calling thread ("" if none). */
 RCPPML_GPU_API const char* rcppml_gpu_last_error(void);
 

@@ -9,6 +9,8 @@ Layout (only what the path needs):
   assess.py  assess() / knn(): mirror of the R surface on the HIP embedding-assessment path (csrc/ops_assess.hip)
   distribution.py score_test_distribution() / diagnose_zero_inflation() / diagnose_dispersion() / auto_nmf_distribution(): mirror of
              the R surface on the HIP distribution-diagnostics path (csrc/ops_distribution.hip)
+  consensus.py consensus_nmf() / consensus_matrix() / hclust_average(): mirror of the R surface on the HIP consensus-clustering
+             path (csrc/ops_consensus.hip)
   als.py     one-process-per-GPU column-sharded ALS loop over torch.distributed (RCCL): Comm, ShardedALS, HipOps
   data.py    synthetic inputs (restatement of R/simulateNMF.R) and CSC helpers
 """

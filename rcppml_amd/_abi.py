@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_svd_pca_double", "rcppml_gpu_svd_pca_float", "rcppml_gpu_svd_pca_dense_double", "rcppml_gpu_svd_pca_dense_float",
     "rcppml_gpu_assess", "rcppml_gpu_assess_ex", "rcppml_gpu_knn_float", "rcppml_gpu_assess_plan",
     "rcppml_gpu_score_test_double", "rcppml_gpu_zero_inflation_double", "rcppml_gpu_dispersion_double",
+    "rcppml_gpu_consensus_double", "rcppml_gpu_hclust_average_double",
 ]
 
 
@@ -1055,4 +1056,46 @@ def dispersion_double(csc, dense, m, n, k, W_T, d, H, power, min_mu=1e-6, trim=0
     r = dict(status=st.value, error=last_error() if st.value else "", buffers=(rp, cp, gp.value))
     if st.value == 0:
         r.update(row_phi=rp[:m].copy(), col_phi=cp[:n].copy(), global_phi=gp.value)
+    return r
+
+
+# ----------------------------------------------------------------------------- consensus clustering (ops_consensus.hip)
+CONSENSUS_METHOD = {"hard": 0, "knn_jaccard": 1}
+
+
+def consensus_double(W_stack, m, k, reps, method, knn=10, *, labels=True, init=-7.0):
+    """rcppml_gpu_consensus_double: dict(status, error, consensus (m x m), labels (reps x m, hard with labels=True), buffers).
+    W_stack: (reps, m, k) C-contiguous (each replicate k x m column-major), or None (a null pointer).  method: 0 / 1 or a name of
+    CONSENSUS_METHOD.  Outputs start at `init` / -7 (a refused call leaves them so)."""
+    W = None if W_stack is None else np.ascontiguousarray(W_stack, np.float64)
+    method = CONSENSUS_METHOD.get(method, method)
+    mm, rr = max(int(m), 1), max(int(reps), 1)
+    cons = np.full((mm, mm), init)
+    lab = np.full((rr, mm), -7, np.int32) if labels else None
+    st = C.c_int(-99)
+    lib().rcppml_gpu_consensus_double(_np_ptr(W) if W is not None else None, _ci(m), _ci(k), _ci(reps), _ci(method), _ci(knn),
+                                      _np_ptr(cons), _np_ptr(lab) if lab is not None else None, C.byref(st))
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(cons,) if lab is None else (cons, lab))
+    if st.value == 0:
+        r.update(consensus=cons, labels=lab if (lab is not None and method == 0) else None)
+    return r
+
+
+def hclust_average_double(dist, k_cut, *, m=None, init=-7.0):
+    """rcppml_gpu_hclust_average_double (host only, no device): dict(status, error, merge ((m - 1) x 2, R's convention), height
+    (m - 1), clusters (m, numbered 1.. by first appearance), cophenetic, buffers).  dist: m x m, the entries below the diagonal are
+    read (dist[i, j] with i > j), or None (a null pointer)."""
+    D = None if dist is None else np.asfortranarray(dist, np.float64)
+    if m is None:
+        m = D.shape[0]
+    mm = max(int(m), 2)
+    merge = np.full((mm - 1, 2), -7, np.int32, order="F")
+    height = np.full(mm - 1, init)
+    clusters = np.full(mm, -7, np.int32)
+    coph, st = C.c_double(init), C.c_int(-99)
+    lib().rcppml_gpu_hclust_average_double(_np_ptr(D) if D is not None else None, _ci(m), _ci(k_cut), _np_ptr(merge), _np_ptr(height),
+                                           _np_ptr(clusters), C.byref(coph), C.byref(st))
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(merge, height, clusters, coph.value))
+    if st.value == 0:
+        r.update(merge=merge, height=height, clusters=clusters, cophenetic=coph.value)
     return r
