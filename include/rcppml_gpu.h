@@ -442,6 +442,43 @@ RCPPML_GPU_API void rcppml_gpu_consensus_double(const double* W_stack, int* m, i
 RCPPML_GPU_API void rcppml_gpu_hclust_average_double(const double* dist, int* m, int* k_cut, int* out_merge, double* out_height,
         int* out_clusters, double* out_cophenetic, int* out_status);
 
+/* Label-guided refinement (rcppml_amd/csrc/ops_refine.hip): the reference's compute_target() (R/compute_target.R:65-121) and
+ * refine() without a batch (R/refine.R:109-187), fp64.  Build-defined: R has no hook for these entries.  H: k x n column-major (k
+ * leading); labels: n ints in 0 .. *n_classes - 1, a negative value is R's NA (the column is unguided).  The per-class sums, ||H||_F^2
+ * and the correction run on the device; the k x C stage (centroids, OAS shrinkage, cyclic-Jacobi eigendecomposition, ZCA, shifts)
+ * on the host.  Results are bitwise-repeatable: no atomics, every summation order is fixed by (k, n, the labels).
+ * Refused (*out_status = -1, reason in rcppml_gpu_last_error, no output written): a null pointer; k, n or m below 1; n_classes < 0;
+ * a label >= n_classes; lambda outside [0, 1]; cycles < 0; both matrix forms or neither; a malformed CSC (row indices strictly
+ * increasing within a column); a non-finite value in H, W, d or the matrix; k > 64 where a refit runs; not enough free device
+ * memory (the message gives the byte count); no HIP device.
+ *
+ * rcppml_gpu_compute_target_double: out_target (k x n) = shift[, label_j] (0 for NA).  centroid_c = the class mean (0 for an empty
+ * class); grand_mean = the mean of the non-empty classes' centroids.  *whiten and n_classes > 1: X = (centroids - grand_mean)
+ * sqrt(max(count, 1)), S = X X^T / sum(count), rho = ((1 - 2/k) tr(S^2) + tr(S)^2) / ((sum(count) + 1 - 2/k) (tr(S^2) - tr(S)^2 / k))
+ * clamped to [0, 1] (1 when |denominator| < 1e-12), S_shrunk = (1 - rho) S + rho tr(S) / k I, W_zca = V diag(1 / sqrt(max(eig,
+ * 1e-10))) V^T applied to the centroids and to grand_mean.  shift = centroids - grand_mean.  out_shift (k x n_classes) and
+ * out_counts (n_classes) may be NULL. */
+RCPPML_GPU_API void rcppml_gpu_compute_target_double(const double* H, const int* labels, int* k, int* n, int* n_classes, int* whiten,
+        double* out_target, double* out_shift, int* out_counts, int* out_status);
+/* Stage 1 of refine() (R/refine.R:109-122): out_H_corr = H + *lambda * s * T with T the target above and s = ||H||_F / ||T||_F
+ * (applied only when ||T||_F > 1e-10), clipped at 0 when *nonneg.  out_target (k x n, the unscaled T) may be NULL. */
+RCPPML_GPU_API void rcppml_gpu_refine_correct_double(const double* H, const int* labels, int* k, int* n, int* n_classes, int* whiten,
+        double* lambda, int* nonneg, double* out_H_corr, double* out_target, int* out_status);
+/* The W refit of a refine() cycle alone (R/refine.R:137-145): out_W (k x m) = solve(G + 1e-8 I, B) with dH = diag(d) H_corr,
+ * G = dH dH^T, B = A dH^T, clipped at 0 when *nonneg (an unconstrained solve and a clip, not NNLS).  The matrix: a host CSC
+ * (col_ptr, row_idx, values, *nnz) or a column-major m x n dense array, exactly one of the two. */
+RCPPML_GPU_API void rcppml_gpu_refine_wfit_double(const int* col_ptr, const int* row_idx, const double* values, int* nnz,
+        const double* dense, int* m, int* n, int* k, const double* d, const double* H_corr, int* nonneg, double* out_W,
+        int* out_status);
+/* refine(): stage 1, then *cycles cycles of (R/refine.R:135-187): the W refit above; H = solve(W^T W + 1e-8 I, W^T A), clipped
+ * when *nonneg; d = the L2 row norms of H floored at 1e-10, H divided by d, W multiplied by d; stage 1 again on the new H.  W_T
+ * (k x m), d (k), H (k x n) are read only; out_W, out_d, out_H: the model after the cycles (the inputs when *cycles = 0: the matrix may
+ * then be absent, both pointers NULL); out_H_corr: the corrected H.  The matrix and the factors stay on the device between cycles. */
+RCPPML_GPU_API void rcppml_gpu_refine_double(const int* col_ptr, const int* row_idx, const double* values, int* nnz,
+        const double* dense, int* m, int* n, int* k, const double* W_T, const double* d, const double* H, const int* labels,
+        int* n_classes, double* lambda, int* cycles, int* nonneg, int* whiten, double* out_W, double* out_d, double* out_H,
+        double* out_H_corr, int* out_status);
+
 /* Last error text of the calling thread ("" if none). */
 RCPPML_GPU_API const char* rcppml_gpu_last_error(void);
 

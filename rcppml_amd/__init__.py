@@ -11,7 +11,11 @@ Layout (only what the path needs):
              the R surface on the HIP distribution-diagnostics path (csrc/ops_distribution.hip)
   consensus.py consensus_nmf() / consensus_matrix() / hclust_average(): mirror of the R surface on the HIP consensus-clustering
              path (csrc/ops_consensus.hip)
+  refine.py  compute_target() / refine(): mirror of the R surface on the HIP label-guided refinement path (csrc/ops_refine.hip)
   als.py     one-process-per-GPU column-sharded ALS loop over torch.distributed (RCCL): Comm, ShardedALS, HipOps
   data.py    synthetic inputs (restatement of R/simulateNMF.R) and CSC helpers
 """
 __version__ = "0.1.0"
+
+# the package attribute `refine` is the function from here on; the module's other names come with `from rcppml_amd.refine import ...`
+from .refine import compute_target, refine  # noqa: E402,F401

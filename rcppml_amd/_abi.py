@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_assess", "rcppml_gpu_assess_ex", "rcppml_gpu_knn_float", "rcppml_gpu_assess_plan",
     "rcppml_gpu_score_test_double", "rcppml_gpu_zero_inflation_double", "rcppml_gpu_dispersion_double",
     "rcppml_gpu_consensus_double", "rcppml_gpu_hclust_average_double",
+    "rcppml_gpu_compute_target_double", "rcppml_gpu_refine_correct_double", "rcppml_gpu_refine_wfit_double", "rcppml_gpu_refine_double",
 ]
 
 
@@ -1098,4 +1099,113 @@ def hclust_average_double(dist, k_cut, *, m=None, init=-7.0):
     r = dict(status=st.value, error=last_error() if st.value else "", buffers=(merge, height, clusters, coph.value))
     if st.value == 0:
         r.update(merge=merge, height=height, clusters=clusters, cophenetic=coph.value)
+    return r
+
+
+# ----------------------------------------------------------------------------- label-guided refinement (ops_refine.hip)
+def _opt_ptr(a):
+    return _np_ptr(a) if a is not None else None
+
+
+def _labels_arg(labels):
+    return None if labels is None else np.ascontiguousarray(labels, np.int32).reshape(-1)
+
+
+def compute_target_double(H, labels, n_classes, whiten=True, *, k=None, n=None, init=-7.0):
+    """rcppml_gpu_compute_target_double: dict(status, error, target (n, k) row-major = k x n, shift (n_classes, k), counts, buffers).
+    H: (n, k) row-major (= k x n column-major) or None (a null pointer); labels: n ints, negative = NA, or None.  Outputs start at
+    `init` / -7 (a refused call leaves them so)."""
+    Hc = None if H is None else np.ascontiguousarray(H, np.float64)
+    lab = _labels_arg(labels)
+    if n is None:
+        n = Hc.shape[0]
+    if k is None:
+        k = Hc.shape[1]
+    nn, kk, cc = max(int(n), 1), max(int(k), 1), max(int(n_classes), 1)
+    T = np.full((nn, kk), init)
+    shift = np.full((cc, kk), init)
+    counts = np.full(cc, -7, np.int32)
+    st = C.c_int(-99)
+    lib().rcppml_gpu_compute_target_double(_opt_ptr(Hc), _opt_ptr(lab), _ci(k), _ci(n), _ci(n_classes), _ci(bool(whiten)), _np_ptr(T),
+                                           _np_ptr(shift), _np_ptr(counts), C.byref(st))
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(T, shift, counts))
+    if st.value == 0:
+        r.update(target=T, shift=shift[:int(n_classes)], counts=counts[:int(n_classes)])
+    return r
+
+
+def refine_correct_double(H, labels, n_classes, lambda_, nonneg=True, whiten=True, *, k=None, n=None, want_target=True, init=-7.0):
+    """rcppml_gpu_refine_correct_double (stage 1 of refine()): dict(status, error, H_corr (n, k), target (n, k) or None, buffers)."""
+    Hc = None if H is None else np.ascontiguousarray(H, np.float64)
+    lab = _labels_arg(labels)
+    if n is None:
+        n = Hc.shape[0]
+    if k is None:
+        k = Hc.shape[1]
+    nn, kk = max(int(n), 1), max(int(k), 1)
+    out = np.full((nn, kk), init)
+    T = np.full((nn, kk), init) if want_target else None
+    st = C.c_int(-99)
+    lib().rcppml_gpu_refine_correct_double(_opt_ptr(Hc), _opt_ptr(lab), _ci(k), _ci(n), _ci(n_classes), _ci(bool(whiten)),
+                                           _cd(lambda_), _ci(bool(nonneg)), _np_ptr(out), _opt_ptr(T), C.byref(st))
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(out,) if T is None else (out, T))
+    if st.value == 0:
+        r.update(H_corr=out, target=T)
+    return r
+
+
+def _matrix_head(csc, dense):
+    """(col_ptr, row_idx, values, nnz, dense) of the entries that take either matrix form, and the arrays to keep alive."""
+    keep = []
+    if csc is not None:
+        p, i, x = (csc.p, csc.i, csc.x) if hasattr(csc, "p") else csc
+        p = np.ascontiguousarray(p, np.int32); i = np.ascontiguousarray(i, np.int32); x = np.ascontiguousarray(x, np.float64)
+        keep += [p, i, x]
+        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(x.shape[0])]
+    else:
+        head = [None, None, None, _ci(0)]
+    if dense is not None:
+        dn = np.asfortranarray(dense, np.float64)
+        keep.append(dn)
+        head.append(_np_ptr(dn))
+    else:
+        head.append(None)
+    return head, keep
+
+
+def refine_wfit_double(csc, dense, m, n, k, d, H_corr, nonneg=True, init=-7.0):
+    """rcppml_gpu_refine_wfit_double: dict(status, error, W ((m, k) row-major = k x m), buffers).  csc / dense as in
+    score_test_double; d: (k); H_corr: (n, k) row-major."""
+    head, keep = _matrix_head(csc, dense)
+    dd = None if d is None else np.ascontiguousarray(d, np.float64)
+    Hc = None if H_corr is None else np.ascontiguousarray(H_corr, np.float64)
+    W = np.full((max(int(m), 1), max(int(k), 1)), init)
+    st = C.c_int(-99)
+    lib().rcppml_gpu_refine_wfit_double(*head, _ci(m), _ci(n), _ci(k), _opt_ptr(dd), _opt_ptr(Hc), _ci(bool(nonneg)), _np_ptr(W),
+                                        C.byref(st))
+    del keep
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(W,))
+    if st.value == 0:
+        r.update(W=W)
+    return r
+
+
+def refine_double(csc, dense, m, n, k, W_T, d, H, labels, n_classes, lambda_=0.8, cycles=0, nonneg=True, whiten=True, init=-7.0):
+    """rcppml_gpu_refine_double: dict(status, error, W (m, k), d (k), H (n, k), H_corr (n, k), buffers).  W_T: (m, k) row-major
+    (= k x m), H: (n, k) row-major (= k x n); any of them None hands over a null pointer."""
+    head, keep = _matrix_head(csc, dense)
+    Wc = None if W_T is None else np.ascontiguousarray(W_T, np.float64)
+    dd = None if d is None else np.ascontiguousarray(d, np.float64)
+    Hc = None if H is None else np.ascontiguousarray(H, np.float64)
+    lab = _labels_arg(labels)
+    mm, nn, kk = max(int(m), 1), max(int(n), 1), max(int(k), 1)
+    oW, od, oH, oC = np.full((mm, kk), init), np.full(kk, init), np.full((nn, kk), init), np.full((nn, kk), init)
+    st = C.c_int(-99)
+    lib().rcppml_gpu_refine_double(*head, _ci(m), _ci(n), _ci(k), _opt_ptr(Wc), _opt_ptr(dd), _opt_ptr(Hc), _opt_ptr(lab),
+                                   _ci(n_classes), _cd(lambda_), _ci(cycles), _ci(bool(nonneg)), _ci(bool(whiten)), _np_ptr(oW),
+                                   _np_ptr(od), _np_ptr(oH), _np_ptr(oC), C.byref(st))
+    del keep
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(oW, od, oH, oC))
+    if st.value == 0:
+        r.update(W=oW, d=od, H=oH, H_corr=oC)
     return r
