@@ -59,9 +59,10 @@ RCPPML_GPU_API void rcppml_gpu_detect(int* num_gpus, double* total_mem_mb, doubl
  * env RCPPML_GPU_DEVICES=n shards plain MSE fits over n devices (plugin_multi.hip).  Not implemented
  * -- REJECTED with *out_status = -1 so the caller falls back to CPU rather than silently dropping
  * them: classifier guides, dispersion = per_col (n values: the bridge's out_theta holds m, gpu/bridge_nmf.hpp:284 --
- * rcppml_gpu_nmf_ex takes a capacity), zero-inflated losses, k > 256 (k > 128 for IRLS losses,
- * explicit masks, angular and graph penalties).  Target regularisation has no slot in these 73 arguments: see
- * rcppml_gpu_nmf_target below. */
+ * rcppml_gpu_nmf_ex takes a capacity), k > 256 (k > 128 for IRLS losses,
+ * explicit masks, angular and graph penalties).  Target regularisation and zero-inflation (zi_mode, zi_em_iters) have no slot in
+ * these 73 arguments: see rcppml_gpu_nmf_target and rcppml_gpu_nmf_zi_double below -- through the 73-pointer entries a fit is never
+ * zero-inflated. */
 #define RCPPML_NMF_UNIFIED_ARGS                                                                    \
     const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz, int* k, \
         double* W, double* H, double* d, int* max_iter, double* tol, double* L1_H, double* L1_W,   \
@@ -478,6 +479,50 @@ RCPPML_GPU_API void rcppml_gpu_refine_double(const int* col_ptr, const int* row_
         const double* dense, int* m, int* n, int* k, const double* W_T, const double* d, const double* H, const int* labels,
         int* n_classes, double* lambda, int* cycles, int* nonneg, int* whiten, double* out_W, double* out_d, double* out_H,
         double* out_H_corr, int* out_status);
+
+/* Zero-inflated GP / NB NMF (rcppml_amd/csrc/ops_zi.hip, kernels_zi.hip.h).  Build-defined: the reference's bridge has no slot for zi and
+ * its device path ignores it, so the specification is the reference's CPU fit, inst/include/FactorNet/nmf/fit_cpu.hpp:
+ *   :350-400    pi_row[i] = min(0.5 (1 - nnz_row_i / n), 0.3), pi_col[j] = min(0.5 (1 - nnz_col_j / m), 0.3), counts of STORED entries
+ *               (an entry is a zero iff the CSC does not store it; an explicit stored 0 is not a zero);
+ *   :403-421    A_imputed = A as a dense matrix;
+ *   :589-596, :833-840  from ALS iteration 1 on both half-updates are the dense IRLS (every entry weighted, each batch from zero) on
+ *               A_imputed and its transpose; iteration 0 is the plain sparse IRLS fit's;
+ *   :1285-1479  after the W update and the dispersion update (on the original A) of EVERY iteration: zi_em_iters rounds of the E-step
+ *               over the unstored (i, j) -- s = max((W_T o d)_i . h_j, 1e-10); NB p0 = (r_i / (r_i + s))^r_i, r_i = max(size_i, 1e-10);
+ *               GP p0 = exp(-s / (1 + theta_i)); z = pi / (pi + (1 - pi) p0 + 1e-300), summed per row (ROW) or column (COL) -- and the
+ *               M-step pi = clamp(zsum / n, 0.001, 0.999) (ROW; COL: / m) where the row / column has an unstored entry, each round
+ *               followed by theta_i = max(theta_i, gp_theta_min) (GP, gp_theta_min > 0);
+ *   :1490-1550  one imputation A_imputed(i, j) = z s at the unstored entries with the UPDATED pi, stored entries keep A's value;
+ *   :1684-1767  then the loss, on the original A's stored entries;  :1837-1840 pi_row / pi_col are returned.
+ * Scope: fp64, a host CSC (row indices strictly increasing within a column), the CD solver, k <= 128, L1 / L2 / nonneg / upper bounds
+ * as the IRLS path takes them, dispersion none / global / per row.  fp32, dense input, masks, cross-validation and several devices are
+ * not offered under ZI.  Refused (*out_status = -1, reason in rcppml_gpu_last_error, NO output buffer written): zi_mode 3 (TWOWAY,
+ * with the text of core/config.hpp:437-440) or outside {1 ROW, 2 COL}; a loss other than GP (4) / NB (5); dispersion mode 3 (per_col:
+ * the reference indexes the dispersion vector by row in the E-step); k > 128; zi_em_iters < 1; a malformed CSC; a null pointer; a
+ * call whose device arrays -- two m x n fp64 arrays, two m n int32 index arrays, the bitmask (m n / 8 bytes), the tile partials --
+ * exceed the free device memory (checked by arithmetic before anything is allocated; the message gives the byte count); m n >= 2^31;
+ * no HIP device.
+ * Results are bitwise-repeatable and independent of the launch grid: no floating-point atomics, per-tile partials in a fixed order
+ * added in tile order.
+ *
+ * rcppml_gpu_nmf_zi_double: W (k x m), H (k x n), d (k) in/out as in rcppml_gpu_nmf_ex; loss_history (>= *max_iter doubles) may be NULL;
+ * out_theta holds m doubles (*out_theta_len returns m); out_pi holds max(m, n) doubles, *out_pi_len returns m (ROW) or n (COL).
+ * *sort_model orders the factors by descending d; pi is per row / column and is not permuted. */
+RCPPML_GPU_API void rcppml_gpu_nmf_zi_double(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+        int* k, double* W, double* H, double* d, int* max_iter, double* tol, double* L1_H, double* L1_W, double* L2_H, double* L2_W,
+        double* ub_H, double* ub_W, int* cd_maxit, double* cd_tol, int* verbose, int* patience, int* nonneg_W, int* nonneg_H,
+        int* loss_type, int* irls_max_iter, double* irls_tol, int* norm_type, int* dispersion_mode, double* gp_theta_init,
+        double* gp_theta_max, double* gp_theta_min, double* nb_size_init, double* nb_size_max, double* nb_size_min, int* sort_model,
+        int* zi_mode, int* zi_em_iters, double* loss_history, double* out_theta, int* out_theta_len, double* out_pi, int* out_pi_len,
+        int* out_iter, int* out_converged, double* out_loss, double* out_tol, int* out_status);
+/* The stage alone (fit_cpu.hpp:1285-1552): *zi_em_iters rounds of E-step, M-step and theta floor, then one imputation.  W_T (k x m), d
+ * (k), H (k x n) are read; disp (m: NB sizes or GP theta) is in/out (floored for GP when *theta_min > 0); pi (m for ROW, n for COL,
+ * values in [0, 1]) is in/out; out_imputed (m x n column-major, may be NULL) receives A_imputed -- its stored entries are A's values
+ * bit for bit.  Here m n may exceed 2^31 (64-bit indexing; no index arrays are built).  Env RCPPML_GPU_ZI_GRID = the number of
+ * workgroups the tile kernels are launched with (a test hook: the result does not depend on it). */
+RCPPML_GPU_API void rcppml_gpu_zi_em_double(const int* col_ptr, const int* row_idx, const double* values, int* nnz, int* m, int* n,
+        int* k, const double* W_T, const double* d, const double* H, double* disp, int* loss_type, int* zi_mode, int* zi_em_iters,
+        double* theta_min, double* pi, double* out_imputed, int* out_status);
 
 /* Last error text of the calling thread ("" if none). */
 RCPPML_GPU_API const char* rcppml_gpu_last_error(void);

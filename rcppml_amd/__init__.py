@@ -12,6 +12,8 @@ Layout (only what the path needs):
   consensus.py consensus_nmf() / consensus_matrix() / hclust_average(): mirror of the R surface on the HIP consensus-clustering
              path (csrc/ops_consensus.hip)
   refine.py  compute_target() / refine(): mirror of the R surface on the HIP label-guided refinement path (csrc/ops_refine.hip)
+  zi.py      nmf_zi(): zero-inflated GP / NB NMF (zi = "row" / "col") on the HIP zero-inflation path (csrc/ops_zi.hip); nmf(zi = ...)
+             itself still refuses, routing it here is a later change
   als.py     one-process-per-GPU column-sharded ALS loop over torch.distributed (RCCL): Comm, ShardedALS, HipOps
   data.py    synthetic inputs (restatement of R/simulateNMF.R) and CSC helpers
 """

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_score_test_double", "rcppml_gpu_zero_inflation_double", "rcppml_gpu_dispersion_double",
     "rcppml_gpu_consensus_double", "rcppml_gpu_hclust_average_double",
     "rcppml_gpu_compute_target_double", "rcppml_gpu_refine_correct_double", "rcppml_gpu_refine_wfit_double", "rcppml_gpu_refine_double",
+    "rcppml_gpu_nmf_zi_double", "rcppml_gpu_zi_em_double",
 ]
 
 
@@ -1208,4 +1209,60 @@ def refine_double(csc, dense, m, n, k, W_T, d, H, labels, n_classes, lambda_=0.8
     r = dict(status=st.value, error=last_error() if st.value else "", buffers=(oW, od, oH, oC))
     if st.value == 0:
         r.update(W=oW, d=od, H=oH, H_corr=oC)
+    return r
+
+
+# ----------------------------------------------------------------------------- zero-inflated GP / NB (ops_zi.hip)
+ZI_MODE = {"row": 1, "col": 2, "twoway": 3}
+
+
+def zi_em_double(csc, m, n, k, W_T, d, H, disp, pi, loss_type, zi_mode, zi_em_iters=1, theta_min=0.0, want_imputed=True, init=-7.0):
+    """rcppml_gpu_zi_em_double (the E / M / impute stage alone): dict(status, error, pi, disp, imputed (m, n), buffers).  csc: an object
+    with p / i / x or a (p, i, x) tuple; W_T (m, k), H (n, k) row-major; disp (m), pi (m for ROW, n for COL) are copied, not changed.
+    A refused call leaves the copies as they were handed over and the imputed buffer at `init`."""
+    p, i, x = (csc.p, csc.i, csc.x) if hasattr(csc, "p") else csc
+    p = np.ascontiguousarray(p, np.int32); i = np.ascontiguousarray(i, np.int32); x = np.ascontiguousarray(x, np.float64)
+    W_T = np.ascontiguousarray(W_T, np.float64); d = np.ascontiguousarray(d, np.float64); H = np.ascontiguousarray(H, np.float64)
+    disp = np.array(disp, np.float64).reshape(-1).copy()
+    pi = np.array(pi, np.float64).reshape(-1).copy()
+    imp = np.full(max(m * n, 1), init) if want_imputed else None
+    st = C.c_int(-99)
+    lib().rcppml_gpu_zi_em_double(_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(x.shape[0]), _ci(m), _ci(n), _ci(k), _np_ptr(W_T), _np_ptr(d),
+                                  _np_ptr(H), _np_ptr(disp), _ci(loss_type), _ci(zi_mode), _ci(zi_em_iters), _cd(theta_min), _np_ptr(pi),
+                                  _np_ptr(imp) if imp is not None else None, C.byref(st))
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(pi, disp, imp), pi=pi, disp=disp)
+    if st.value == 0 and imp is not None:
+        r["imputed"] = imp[:m * n].reshape(n, m).T.copy()          # column-major m x n
+    return r
+
+
+def nmf_zi_double(p, i, x, m, n, k, W_T, H, *, zi_mode, zi_em_iters=1, loss_type=5, max_iter=100, tol=1e-4, L1_H=0.0, L1_W=0.0,
+                  L2_H=0.0, L2_W=0.0, ub_H=0.0, ub_W=0.0, cd_maxit=100, cd_tol=1e-8, verbose=0, patience=5, nonneg_W=1, nonneg_H=1,
+                  irls_max_iter=5, irls_tol=1e-4, norm_type=0, dispersion_mode=2, gp_theta=(0.1, 5.0, 0.0), nb_size=(10.0, 1e6, 0.01),
+                  sort_model=1, want_history=True, init=-7.0):
+    """rcppml_gpu_nmf_zi_double.  W_T (m, k) and H (n, k) float64 (memory = column-major k x m / k x n) are updated IN PLACE.  Returns
+    dict(status, error, d, iter, converged, loss, tol, theta, pi, loss_history, buffers); the output buffers start at `init` (d: ones) and a
+    refused call leaves them and W_T / H so."""
+    p = np.ascontiguousarray(p, np.int32); i = np.ascontiguousarray(i, np.int32); x = np.ascontiguousarray(x, np.float64)
+    assert W_T.dtype == np.float64 and H.dtype == np.float64 and W_T.flags.c_contiguous and H.flags.c_contiguous
+    assert W_T.shape == (m, k) and H.shape == (n, k)
+    d = np.ones(max(k, 1), np.float64)
+    theta = np.full(max(m, 1), init)
+    pi = np.full(max(m, n, 1), init)
+    hist = np.full(max(max_iter, 1), np.nan) if want_history else None
+    theta_len, pi_len, out_iter, out_conv, st = C.c_int(-7), C.c_int(-7), C.c_int(-7), C.c_int(-7), C.c_int(-99)
+    out_loss, out_tol = C.c_double(init), C.c_double(init)
+    lib().rcppml_gpu_nmf_zi_double(
+        _np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0]), _ci(k), _np_ptr(W_T), _np_ptr(H), _np_ptr(d), _ci(max_iter),
+        _cd(tol), _cd(L1_H), _cd(L1_W), _cd(L2_H), _cd(L2_W), _cd(ub_H), _cd(ub_W), _ci(cd_maxit), _cd(cd_tol), _ci(verbose), _ci(patience),
+        _ci(nonneg_W), _ci(nonneg_H), _ci(loss_type), _ci(irls_max_iter), _cd(irls_tol), _ci(norm_type), _ci(dispersion_mode),
+        _cd(gp_theta[0]), _cd(gp_theta[1]), _cd(gp_theta[2]), _cd(nb_size[0]), _cd(nb_size[1]), _cd(nb_size[2]), _ci(sort_model),
+        _ci(zi_mode), _ci(zi_em_iters), _np_ptr(hist) if hist is not None else None, _np_ptr(theta), C.byref(theta_len), _np_ptr(pi),
+        C.byref(pi_len), C.byref(out_iter), C.byref(out_conv), C.byref(out_loss), C.byref(out_tol), C.byref(st))
+    r = dict(status=st.value, error=last_error() if st.value else "", d=d[:k], buffers=(d, theta, pi, theta_len.value, pi_len.value,
+                                                                                          out_iter.value, out_loss.value))
+    if st.value == 0:
+        r.update(iter=out_iter.value, converged=bool(out_conv.value), loss=out_loss.value, tol=out_tol.value,
+                 theta=theta[:theta_len.value].copy(), pi=pi[:pi_len.value].copy(),
+                 loss_history=hist[:out_iter.value].copy() if hist is not None else None)
     return r

@@ -8,6 +8,7 @@
 // ============================================================================
 #include <chrono>
 #include "plugin_common.hip.h"
+#include "zi_stage.hip.h"
 
 extern "C" const char* rcppml_gpu_last_error(void) { return rcppml_err().c_str(); }
 
@@ -283,6 +284,16 @@ void fit(FitParams& P) {
         HIPCHK(hipMemcpyAsync(dtheta.p, th.data(), dlen * sizeof(T), hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
     }
+    // zero-inflated GP / NB (fit_cpu.hpp:350-421): pi from the stored pattern, the bitmask, A_imputed and A_imputed^T with the stored
+    // entries in place, and the index arrays of the CSCs that store every entry of the two (sparse host CSC, fp64: the entry checks)
+    rcppml_zi::Stage zi;
+    const bool is_zi = P.zi_mode != 0;
+    if (is_zi) {
+        std::vector<double> pi0;
+        std::vector<int> zc;
+        rcppml_zi::pi_init_host(P.col_ptr, P.row_idx, m, n, P.zi_mode, pi0, zc);
+        zi.setup(s, m, n, k, P.loss_type, P.zi_mode, dAp.as<int>(), dAi.as<int>(), static_cast<const double*>(dAx.p), pi0, zc, true, true, true);
+    }
     const double eps = 1e-15;
     double prev_loss = std::numeric_limits<double>::max();
     if (std::is_same<T, float>::value) prev_loss = std::numeric_limits<float>::max();
@@ -367,7 +378,11 @@ void fit(FitParams& P) {
             if (P.ub_H > 0) OPCHK(rcppml_hip_clip_upper(c, dt, dH.p, (int64_t)k * n, P.ub_H));      // :636-637
         } else if (is_nb) {                                                                    // :565-606 (G: eps only)
             OPCHK(rcppml_hip_gram(c, dt, dW.p, k, m, eps, 0.0, dG.p));
-            OPCHK(rcppml_hip_solve_irls(c, dt, P.loss_type, dAp.as<int>(), dAi.as<int>(), dAx.p, n, dW.p, dG.p, dH.p, k, P.L1_H,
+            // :589-597 ZIGP / ZINB from iteration 1 on: nnls_batch_irls_dense on A_imputed = the per-nonzero IRLS over the CSC that stores
+            // every entry of it
+            const bool zd = is_zi && iter > 0;
+            OPCHK(rcppml_hip_solve_irls(c, dt, P.loss_type, zd ? zi.fwd_p.as<int>() : dAp.as<int>(), zd ? zi.fwd_i.as<int>() : dAi.as<int>(),
+                                        zd ? zi.imp.p : dAx.p, n, dW.p, dG.p, dH.p, k, P.L1_H,
                                         P.L2_H, P.nonneg_H, P.cd_maxit, P.irls_max_iter, P.irls_tol,
                                         (is_gp || per_col) ? nullptr : dtheta.p, (!is_gp && per_col) ? dtheta.p : nullptr,   // :577-583
                                         P.tweedie_power, P.robust_delta));
@@ -433,7 +448,9 @@ void fit(FitParams& P) {
             if (P.ub_W > 0) OPCHK(rcppml_hip_clip_upper(c, dt, dW.p, (int64_t)k * m, P.ub_W));      // :884-885
         } else if (is_nb) {                                                             // :811-852 theta_per_col = r of the row
             OPCHK(rcppml_hip_gram(c, dt, dH.p, k, n, eps, 0.0, dG.p));
-            OPCHK(rcppml_hip_solve_irls(c, dt, P.loss_type, dTp.as<int>(), dTi.as<int>(), dTx.p, m, dH.p, dG.p, dW.p, k, P.L1_W,
+            const bool zd = is_zi && iter > 0;                                          // :833-842 on A_imputed^T
+            OPCHK(rcppml_hip_solve_irls(c, dt, P.loss_type, zd ? zi.bwd_p.as<int>() : dTp.as<int>(), zd ? zi.bwd_i.as<int>() : dTi.as<int>(),
+                                        zd ? zi.impT.p : dTx.p, m, dH.p, dG.p, dW.p, k, P.L1_W,
                                         P.L2_W, P.nonneg_W, P.cd_maxit, P.irls_max_iter, P.irls_tol,
                                         (!is_gp && per_col) ? dtheta.p : nullptr,            // :820-830 PER_COL: the ROW of A^T
                                         (is_gp || per_col) ? nullptr : dtheta.p, P.tweedie_power, P.robust_delta));
@@ -499,6 +516,12 @@ void fit(FitParams& P) {
             OPCHK(rcppml_hip_dispersion_update(c, dt, P.loss_type, P.dispersion_mode, dTp.as<int>(), dTi.as<int>(), dTx.p, m, P.nnz,
                                                dW.p, dd.p, dH.p, n, k, P.tweedie_power, P.gamma_phi_min,
                                                P.loss_type == 4 ? P.gp_theta_max : P.gamma_phi_max, dtheta.p));
+        // ZIGP / ZINB (fit_cpu.hpp:1285-1552): after the dispersion update on the original A and before the loss (:1684-1767, also on
+        // the original A): zi_em_iters x (E-step, M-step, theta floor), then the imputation the NEXT iteration's half-updates read.
+        // (NB per row: the fused pass above has the loss already; the stage changes nothing that loss reads.)
+        if (is_zi)
+            zi.run(c, s, static_cast<const double*>(dW.p), static_cast<const double*>(dd.p), static_cast<const double*>(dH.p),
+                   static_cast<double*>(dtheta.p), P.zi_em_iters, P.gp_theta_min);
         if (nb_fused) {
             // loss already in dloss
         } else if (has_mask) {
@@ -619,6 +642,11 @@ void fit(FitParams& P) {
         DevBuf& th = dtheta;
         download_cast<T>(c, th, dlen, P.out_theta, s);
         P.out_theta_len = (int)dlen;
+    }
+    if (is_zi && P.out_pi) {                                                            // :1837-1840 pi_row / pi_col
+        HIPCHK(hipMemcpyAsync(P.out_pi, zi.pi.p, (size_t)zi.len() * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        P.out_pi_len = (int)zi.len();
     }
     phase("iterations", s);
     // ---- sort by descending d (core/result.hpp:169-188) on the device, download
@@ -1313,6 +1341,69 @@ extern "C" void rcppml_gpu_nmf_target(RCPPML_NMF_UNIFIED_ARGS, const int* mask_p
     nmf_entry(RCPPML_NMF_UNIFIED_PASS, use_mask ? mask_p : nullptr, use_mask ? mask_i : nullptr, *cd_tol, *sort_model,
               *precision, loss_history, target_H, target_lambda_H ? *target_lambda_H : 0.0, target_W,
               target_lambda_W ? *target_lambda_W : 0.0, theta_cap);
+}
+
+// Zero-inflated GP / NB fit (fit_cpu.hpp:350-421, :589-596, :833-840, :1285-1552, :1837-1840): the IRLS fit of rcppml_gpu_nmf_ex with
+// the ZI stage (ops_zi.hip) after every dispersion update and, from iteration 1 on, the dense IRLS half-updates on A_imputed.
+// Every refusal happens before an output buffer is written.
+extern "C" void rcppml_gpu_nmf_zi_double(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz, int* k,
+                                         double* W, double* H, double* d, int* max_iter, double* tol, double* L1_H, double* L1_W,
+                                         double* L2_H, double* L2_W, double* ub_H, double* ub_W, int* cd_maxit, double* cd_tol,
+                                         int* verbose, int* patience, int* nonneg_W, int* nonneg_H, int* loss_type, int* irls_max_iter,
+                                         double* irls_tol, int* norm_type, int* dispersion_mode, double* gp_theta_init,
+                                         double* gp_theta_max, double* gp_theta_min, double* nb_size_init, double* nb_size_max,
+                                         double* nb_size_min, int* sort_model, int* zi_mode, int* zi_em_iters, double* loss_history,
+                                         double* out_theta, int* out_theta_len, double* out_pi, int* out_pi_len, int* out_iter,
+                                         int* out_converged, double* out_loss, double* out_tol, int* out_status) {
+    if (!out_status) return;
+    try {
+        rcppml_err().clear();
+        if (!m || !n || !nnz || !k || !max_iter || !tol || !L1_H || !L1_W || !L2_H || !L2_W || !ub_H || !ub_W || !cd_maxit || !cd_tol ||
+            !verbose || !patience || !nonneg_W || !nonneg_H || !loss_type || !irls_max_iter || !irls_tol || !norm_type ||
+            !dispersion_mode || !gp_theta_init || !gp_theta_max || !gp_theta_min || !nb_size_init || !nb_size_max || !nb_size_min ||
+            !sort_model || !zi_mode || !zi_em_iters)
+            throw std::invalid_argument("null scalar argument");
+        if (!W || !H || !d || !out_theta || !out_theta_len || !out_pi || !out_pi_len || !out_iter || !out_converged || !out_loss || !out_tol)
+            throw std::invalid_argument("null output");
+        if (*m < 1 || *n < 1) throw std::invalid_argument("empty matrix");
+        rcppml_zi::validate_common(*loss_type, *zi_mode, *zi_em_iters, *dispersion_mode, *k);
+        if (*norm_type < 0 || *norm_type > 2) throw std::invalid_argument("bad norm_type");
+        if (*nnz < 0) throw std::invalid_argument("nnz must be >= 0");
+        if (*nnz > 0 && !values) throw std::invalid_argument("null CSC array");
+        if (*max_iter < 0) throw std::invalid_argument("max_iter must be >= 0");
+        rcppml_zi::validate_csc(col_ptr, row_idx, *m, *n, *nnz);
+        // the memory guard comes before every allocation: the stage's arrays (two m x n fp64 arrays, two m n int32 index arrays, the
+        // bitmask, the tile partials) plus what the plain IRLS fit takes (the CSC twice, factors, right-hand sides)
+        const size_t plain = (size_t)96 * (size_t)std::max(*nnz, 1) + (size_t)96 * (size_t)*k * ((size_t)*m + (size_t)*n) + ((size_t)256 << 20);
+        rcppml_zi::device_guard(rcppml_zi::stage_bytes(*m, *n, *k, *zi_mode, true, true, true) + plain);
+        if ((int64_t)*m * (int64_t)*n >= ((int64_t)1 << 31))
+            throw std::invalid_argument("zero-inflated fit: m * n must be below 2^31 (the dense IRLS half-updates index A_imputed with 32-bit offsets)");
+        FitParams P;
+        P.m = *m; P.n = *n; P.k = *k; P.nnz = *nnz;
+        P.col_ptr = col_ptr; P.row_idx = row_idx; P.values = values;
+        P.W = W; P.H = H; P.d = d;
+        P.max_iter = *max_iter; P.tol = *tol;
+        P.L1_H = *L1_H; P.L1_W = *L1_W; P.L2_H = *L2_H; P.L2_W = *L2_W; P.ub_H = *ub_H; P.ub_W = *ub_W;
+        P.cd_maxit = *cd_maxit > 0 ? *cd_maxit : 10;
+        P.cd_tol = *cd_tol > 0 ? *cd_tol : 1e-8;
+        P.verbose = *verbose; P.patience = *patience; P.nonneg_W = *nonneg_W; P.nonneg_H = *nonneg_H;
+        P.norm_type = *norm_type; P.solver_mode = 0;
+        P.mask_p = nullptr; P.mask_i = nullptr;
+        P.sort_model = *sort_model; P.loss_history = loss_history;
+        P.loss_type = *loss_type; P.irls_max_iter = *irls_max_iter; P.irls_tol = *irls_tol;
+        P.dispersion_mode = *dispersion_mode; P.nb_size_init = *nb_size_init; P.nb_size_max = *nb_size_max; P.nb_size_min = *nb_size_min;
+        P.gp_theta_init = *gp_theta_init; P.gp_theta_max = *gp_theta_max; P.gp_theta_min = *gp_theta_min;
+        std::vector<double> theta((size_t)*m), pi((size_t)std::max(*m, *n));
+        P.out_theta = theta.data();
+        P.zi_mode = *zi_mode; P.zi_em_iters = *zi_em_iters; P.out_pi = pi.data();
+        fit<double>(P);
+        std::copy(theta.begin(), theta.begin() + P.out_theta_len, out_theta);
+        std::copy(pi.begin(), pi.begin() + P.out_pi_len, out_pi);
+        *out_theta_len = P.out_theta_len; *out_pi_len = P.out_pi_len;
+        *out_iter = P.out_iter; *out_converged = P.out_converged; *out_loss = P.out_loss; *out_tol = P.out_tol;
+        *out_status = 0;
+    } catch (const std::exception& e) { rcppml_err() = e.what(); *out_status = -1; }
+    catch (...) { rcppml_err() = "unknown error"; *out_status = -1; }
 }
 
 // nnls()/predict() projection in fp64 (src/RcppFunctions_utils.cpp:313-366)

@@ -125,6 +125,10 @@ struct FitParams {
     double gp_theta_init = 0.1, gp_theta_max = 5.0;                       // core/config.hpp:169-172
     double gamma_phi_init = 1.0, gamma_phi_max = 1e4, gamma_phi_min = 1e-6;   // core/config.hpp:201-207
     double* out_theta = nullptr; int out_theta_len = 0;
+    // zero-inflated GP / NB (rcppml_gpu_nmf_zi_double; fit_cpu.hpp:350-421, :1285-1552): 0 = none, 1 = ROW, 2 = COL
+    int zi_mode = 0, zi_em_iters = 1;
+    double gp_theta_min = 0;
+    double* out_pi = nullptr; int out_pi_len = 0;      // m (ROW) or n (COL) values; not permuted by sort_model (pi is per row / column)
     // outputs
     int out_iter = 0, out_converged = 0; double out_loss = 0, out_tol = 0;
 };
