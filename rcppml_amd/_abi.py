@@ -121,6 +121,13 @@ def _chk(rc, what):
 
 
 # ----------------------------------------------------------------------------- plugin boundary
+def _check(r, what):
+    """The result dict of an entry wrapper, or BackendError with the entry's reason."""
+    if r["status"] != 0:
+        raise BackendError("GPU %s failed: %s" % (what, r["error"]))
+    return r
+
+
 def detect(max_gpus=8):
     """rcppml_gpu_detect -> list of (total_mb, free_mb); [] if no device (reference R/gpu_backend.R:101-106)."""
     n, st, mx = C.c_int(0), C.c_int(0), C.c_int(max_gpus)
@@ -739,6 +746,26 @@ def _csc_args(p, i, x):
     return (np.ascontiguousarray(p, np.int32), np.ascontiguousarray(i, np.int32), np.ascontiguousarray(x, np.float64))
 
 
+def _matrix_head(csc, dense):
+    """(col_ptr, row_idx, values, nnz, dense) of the entries that take either matrix form, and the arrays to keep alive.  csc: an
+    object with p / i / x (data.CSC) or a (p, i, x) tuple, or None; dense: m x n (any order; handed over column-major) or None.
+    None hands over null pointers."""
+    keep = []
+    if csc is not None:
+        p, i, x = _csc_args(*((csc.p, csc.i, csc.x) if hasattr(csc, "p") else csc))
+        keep += [p, i, x]
+        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(x.shape[0])]
+    else:
+        head = [None, None, None, _ci(0)]
+    if dense is not None:
+        dn = np.asfortranarray(dense, np.float64)
+        keep.append(dn)
+        head.append(_np_ptr(dn))
+    else:
+        head.append(None)
+    return head, keep
+
+
 def bipartition_double(p, i, x, m, n, *, max_iter=100, tol=1e-5, nonneg=True, seed=0.0, partition=None, v=None, center=None):
     """The R-shaped 15-pointer entry (reference src/gpu_bridge_cluster.cu:57-62), with R's buffer sizes by default: partition n
     ints, v m doubles, center 2 m doubles (tests hand in larger buffers to watch what lies past them).  Returns dict(status,
@@ -995,23 +1022,9 @@ def assess_plan(labels, n_classes, *, nstart=10, spc=200, folds=5, seed=42, capa
 
 # ----------------------------------------------------------------------------- distribution diagnostics (ops_distribution.hip)
 def _dist_head(csc, dense, m, n, k, W_T, d, H):
-    """The shared head (col_ptr, row_idx, values, nnz, dense, m, n, k, W_T, d, H) and the arrays to keep alive.  csc: an object with
-    p / i / x (data.CSC) or a (p, i, x) tuple, or None; dense: m x n (any order; handed over column-major) or None.  W_T: (m, k)
-    row-major (= k x m), d: (k), H: (n, k) row-major (= k x n)."""
-    keep = []
-    if csc is not None:
-        p, i, x = (csc.p, csc.i, csc.x) if hasattr(csc, "p") else csc
-        p = np.ascontiguousarray(p, np.int32); i = np.ascontiguousarray(i, np.int32); x = np.ascontiguousarray(x, np.float64)
-        keep += [p, i, x]
-        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(x.shape[0])]
-    else:
-        head = [None, None, None, _ci(0)]
-    if dense is not None:
-        dn = np.asfortranarray(dense, np.float64)
-        keep.append(dn)
-        head.append(_np_ptr(dn))
-    else:
-        head.append(None)
+    """The shared head (col_ptr, row_idx, values, nnz, dense, m, n, k, W_T, d, H) and the arrays to keep alive.  csc / dense as in
+    _matrix_head.  W_T: (m, k) row-major (= k x m), d: (k), H: (n, k) row-major (= k x n)."""
+    head, keep = _matrix_head(csc, dense)
     W_T = np.ascontiguousarray(W_T, np.float64); d = np.ascontiguousarray(d, np.float64); H = np.ascontiguousarray(H, np.float64)
     keep += [W_T, d, H]
     head += [_ci(m), _ci(n), _ci(k), _np_ptr(W_T), _np_ptr(d), _np_ptr(H)]
@@ -1155,25 +1168,6 @@ def refine_correct_double(H, labels, n_classes, lambda_, nonneg=True, whiten=Tru
     return r
 
 
-def _matrix_head(csc, dense):
-    """(col_ptr, row_idx, values, nnz, dense) of the entries that take either matrix form, and the arrays to keep alive."""
-    keep = []
-    if csc is not None:
-        p, i, x = (csc.p, csc.i, csc.x) if hasattr(csc, "p") else csc
-        p = np.ascontiguousarray(p, np.int32); i = np.ascontiguousarray(i, np.int32); x = np.ascontiguousarray(x, np.float64)
-        keep += [p, i, x]
-        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(x.shape[0])]
-    else:
-        head = [None, None, None, _ci(0)]
-    if dense is not None:
-        dn = np.asfortranarray(dense, np.float64)
-        keep.append(dn)
-        head.append(_np_ptr(dn))
-    else:
-        head.append(None)
-    return head, keep
-
-
 def refine_wfit_double(csc, dense, m, n, k, d, H_corr, nonneg=True, init=-7.0):
     """rcppml_gpu_refine_wfit_double: dict(status, error, W ((m, k) row-major = k x m), buffers).  csc / dense as in
     score_test_double; d: (k); H_corr: (n, k) row-major."""
@@ -1220,16 +1214,15 @@ def zi_em_double(csc, m, n, k, W_T, d, H, disp, pi, loss_type, zi_mode, zi_em_it
     """rcppml_gpu_zi_em_double (the E / M / impute stage alone): dict(status, error, pi, disp, imputed (m, n), buffers).  csc: an object
     with p / i / x or a (p, i, x) tuple; W_T (m, k), H (n, k) row-major; disp (m), pi (m for ROW, n for COL) are copied, not changed.
     A refused call leaves the copies as they were handed over and the imputed buffer at `init`."""
-    p, i, x = (csc.p, csc.i, csc.x) if hasattr(csc, "p") else csc
-    p = np.ascontiguousarray(p, np.int32); i = np.ascontiguousarray(i, np.int32); x = np.ascontiguousarray(x, np.float64)
+    head, keep = _matrix_head(csc, None)
     W_T = np.ascontiguousarray(W_T, np.float64); d = np.ascontiguousarray(d, np.float64); H = np.ascontiguousarray(H, np.float64)
     disp = np.array(disp, np.float64).reshape(-1).copy()
     pi = np.array(pi, np.float64).reshape(-1).copy()
     imp = np.full(max(m * n, 1), init) if want_imputed else None
     st = C.c_int(-99)
-    lib().rcppml_gpu_zi_em_double(_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(x.shape[0]), _ci(m), _ci(n), _ci(k), _np_ptr(W_T), _np_ptr(d),
-                                  _np_ptr(H), _np_ptr(disp), _ci(loss_type), _ci(zi_mode), _ci(zi_em_iters), _cd(theta_min), _np_ptr(pi),
-                                  _np_ptr(imp) if imp is not None else None, C.byref(st))
+    lib().rcppml_gpu_zi_em_double(*head[:4], _ci(m), _ci(n), _ci(k), _np_ptr(W_T), _np_ptr(d), _np_ptr(H), _np_ptr(disp), _ci(loss_type),
+                                  _ci(zi_mode), _ci(zi_em_iters), _cd(theta_min), _np_ptr(pi), _opt_ptr(imp), C.byref(st))
+    del keep
     r = dict(status=st.value, error=last_error() if st.value else "", buffers=(pi, disp, imp), pi=pi, disp=disp)
     if st.value == 0 and imp is not None:
         r["imputed"] = imp[:m * n].reshape(n, m).T.copy()          # column-major m x n
@@ -1243,7 +1236,7 @@ def nmf_zi_double(p, i, x, m, n, k, W_T, H, *, zi_mode, zi_em_iters=1, loss_type
     """rcppml_gpu_nmf_zi_double.  W_T (m, k) and H (n, k) float64 (memory = column-major k x m / k x n) are updated IN PLACE.  Returns
     dict(status, error, d, iter, converged, loss, tol, theta, pi, loss_history, buffers); the output buffers start at `init` (d: ones) and a
     refused call leaves them and W_T / H so."""
-    p = np.ascontiguousarray(p, np.int32); i = np.ascontiguousarray(i, np.int32); x = np.ascontiguousarray(x, np.float64)
+    p, i, x = _csc_args(p, i, x)
     assert W_T.dtype == np.float64 and H.dtype == np.float64 and W_T.flags.c_contiguous and H.flags.c_contiguous
     assert W_T.shape == (m, k) and H.shape == (n, k)
     d = np.ones(max(k, 1), np.float64)

@@ -5,19 +5,11 @@ raise BackendError."""
 import numpy as np
 
 from . import _abi
-from .data import CSC
+from .data import as_matrix
 
 
 def _as_csc(data):
-    if isinstance(data, CSC):
-        return data
-    if hasattr(data, "tocsc"):
-        return CSC.from_scipy(data)
-    a = np.asarray(data, dtype=np.float64)
-    if a.ndim != 2:
-        raise ValueError("data must be a matrix")
-    import scipy.sparse as sp                      # dense input goes sparse, as R's .to_dgCMatrix (R/dclust.R)
-    return CSC.from_scipy(sp.csc_matrix(a))
+    return as_matrix(data, dense_ok=False)[0]      # dense input goes sparse, as R's .to_dgCMatrix (R/dclust.R)
 
 
 def _seed(seed):

@@ -10,15 +10,10 @@ import numpy as np
 
 from . import _abi
 from . import nmf as _nmf
+from ._abi import _check
 from .distribution import match_arg
 
 METHODS = ("hard", "knn_jaccard")
-
-
-def _check(r, what):
-    if r["status"] != 0:
-        raise _abi.BackendError("GPU %s failed: %s" % (what, r["error"]))
-    return r
 
 
 def consensus_matrix(W_list, method="hard", knn=10):

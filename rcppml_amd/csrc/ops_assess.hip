@@ -10,7 +10,7 @@
 // the training order of the reference is ascending index, so its train-list ties are index ties), the batch pass excludes the query
 // itself.  The reference takes k + 1 neighbours with self and drops self; that is the top k of the candidates other than self, also
 // when duplicates push self out of its list.
-#include "plugin_common.hip.h"
+#include "entry_common.hip.h"
 #include "kernels_assess.hip.h"
 
 #include <climits>
@@ -21,30 +21,6 @@
 namespace {
 using namespace rcppml_plugin;
 using namespace ras;
-
-struct Stream {
-    hipStream_t s = nullptr;
-    Stream() {
-        HIPCHK(hipSetDevice(env_device()));
-        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    }
-    ~Stream() { if (s) (void)hipStreamDestroy(s); }
-    void sync() { HIPCHK(hipStreamSynchronize(s)); }
-};
-
-template <class T> T* dalloc(DevBuf& b, size_t count) {
-    b.alloc(std::max<size_t>(count, 1) * sizeof(T));
-    return b.as<T>();
-}
-template <class T> T* upload(DevBuf& b, const T* h, size_t count, hipStream_t s) {
-    T* p = dalloc<T>(b, count);
-    if (count) HIPCHK(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, s));
-    return p;
-}
-template <class T> void download(T* h, const T* d, size_t count, hipStream_t s) {
-    if (count) HIPCHK(hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-}
 
 // compile-time width of the register paths (0: the general path)
 int bucket(int dim) { return dim <= 8 ? 8 : dim <= 16 ? 16 : dim <= 32 ? 32 : dim <= 64 ? 64 : 0; }
@@ -505,6 +481,15 @@ void check_scalar_outputs(const In& in, double* out_ari, double* out_nmi, double
         throw std::invalid_argument("null output");
 }
 
+// the assessment on the device RCPPML_GPU_DEVICE names (selected before the engine's stream is made)
+Out run_engine(const In& in) {
+    HIPCHK(hipSetDevice(env_device()));
+    Out o;
+    Engine E(in);
+    E.run(o);
+    return o;
+}
+
 void need(bool used, const int* cap, long count, const char* what) {
     if (!used) return;
     if (!cap || *cap < count) throw std::invalid_argument(std::string(what) + " is too small");
@@ -512,32 +497,20 @@ void need(bool used, const int* cap, long count, const char* what) {
 
 }  // namespace
 
-#define ASSESS_TRY  try { rcppml_err().clear();
-#define ASSESS_CATCH                                                                \
-    } catch (const std::exception& e) { rcppml_err() = e.what(); *out_status = -1; } \
-    catch (...) { rcppml_err() = "unknown error"; *out_status = -1; }
-
 extern "C" void rcppml_gpu_assess(ASSESS_PARAMS, int* out_status) {
-    if (!out_status) return;
-    ASSESS_TRY
+    entry_guard(out_status, [&] {
         const In in = ASSESS_READ;
         check_scalar_outputs(in, out_ari, out_nmi, out_silhouette, out_knn_accuracy, out_knn_f1, out_batch_sil, out_batch_entropy);
-        Out o;
-        {
-            Engine E(in);
-            E.run(o);
-        }
+        const Out o = run_engine(in);
         write_scalars(in, o, out_ari, out_nmi, out_silhouette, out_knn_accuracy, out_knn_f1, out_batch_sil, out_batch_entropy);
-        *out_status = 0;
-    ASSESS_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_assess_ex(ASSESS_PARAMS, int* out_assignments, double* out_restart_ari, double* out_restart_nmi,
                                      float* out_sil_point, int* out_fold_ids, double* out_fold_accuracy, double* out_fold_f1,
                                      double* out_batch_entropy_point, double* out_batch_sil_point, int* point_capacity,
                                      int* restart_capacity, int* fold_capacity, int* out_status) {
-    if (!out_status) return;
-    ASSESS_TRY
+    entry_guard(out_status, [&] {
         const In in = ASSESS_READ;
         check_scalar_outputs(in, out_ari, out_nmi, out_silhouette, out_knn_accuracy, out_knn_f1, out_batch_sil, out_batch_entropy);
         need(in.clust && out_assignments, point_capacity, in.n, "point_capacity");
@@ -546,11 +519,7 @@ extern "C" void rcppml_gpu_assess_ex(ASSESS_PARAMS, int* out_assignments, double
         need(in.bat && (out_batch_entropy_point || out_batch_sil_point), point_capacity, in.n, "point_capacity");
         need(in.clust && (out_restart_ari || out_restart_nmi), restart_capacity, in.nstart, "restart_capacity");
         need(in.clf && (out_fold_accuracy || out_fold_f1), fold_capacity, in.folds, "fold_capacity");
-        Out o;
-        {
-            Engine E(in);
-            E.run(o);
-        }
+        const Out o = run_engine(in);
         write_scalars(in, o, out_ari, out_nmi, out_silhouette, out_knn_accuracy, out_knn_f1, out_batch_sil, out_batch_entropy);
         if (in.clust) {
             if (out_assignments && !o.assign.empty()) std::copy(o.assign.begin(), o.assign.end(), out_assignments);
@@ -567,15 +536,13 @@ extern "C" void rcppml_gpu_assess_ex(ASSESS_PARAMS, int* out_assignments, double
             if (out_batch_entropy_point) std::copy(o.bent_pt.begin(), o.bent_pt.end(), out_batch_entropy_point);
             if (out_batch_sil_point) std::copy(o.bsil_pt.begin(), o.bsil_pt.end(), out_batch_sil_point);
         }
-        *out_status = 0;
-    ASSESS_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_knn_float(const float* query, int* n_query, const float* train, int* n_train, int* dim, int* k,
                                      int* mask_mode, const int* group, const int* group_k, int* n_groups, int* out_idx,
                                      float* out_dist, int* out_capacity, int* out_status) {
-    if (!out_status) return;
-    ASSESS_TRY
+    entry_guard(out_status, [&] {
         if (!n_query || !dim || !k || !mask_mode || !out_capacity) throw std::invalid_argument("null scalar argument");
         const int nq = *n_query, d = *dim, K = *k, mode = *mask_mode;
         const bool self = train == nullptr;
@@ -598,6 +565,7 @@ extern "C" void rcppml_gpu_knn_float(const float* query, int* n_query, const flo
                     if (v < 0 || v > K) throw std::invalid_argument("group_k must lie in [0, k]");
             }
         }
+        HIPCHK(hipSetDevice(env_device()));
         Stream st;
         DevBuf Qb, Tb, Gb, Kb, Ib, Db;
         const float* dQ = upload<float>(Qb, query, (size_t)nq * d, st.s);
@@ -613,15 +581,13 @@ extern "C" void rcppml_gpu_knn_float(const float* query, int* n_query, const flo
         download<float>(hd.data(), dd, hd.size(), st.s);
         std::copy(hi.begin(), hi.end(), out_idx);
         std::copy(hd.begin(), hd.end(), out_dist);
-        *out_status = 0;
-    ASSESS_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_assess_plan(const int* labels, int* n, int* n_classes, int* kmeans_nstart, int* sil_samples_per_class,
                                        int* knn_folds, int* seed, int* out_init_idx, int* init_capacity, int* out_sil_samples,
                                        int* out_sil_counts, int* sil_capacity, int* out_fold_ids, int* fold_capacity, int* out_status) {
-    if (!out_status) return;
-    ASSESS_TRY
+    entry_guard(out_status, [&] {
         if (!n || !n_classes || !seed) throw std::invalid_argument("null scalar argument");
         const int N = *n, nc = *n_classes;
         const unsigned sd = (unsigned)*seed;
@@ -655,6 +621,5 @@ extern "C" void rcppml_gpu_assess_plan(const int* labels, int* n, int* n_classes
         if (out_sil_samples) std::copy(samples.begin(), samples.end(), out_sil_samples);
         if (out_sil_counts) std::copy(counts.begin(), counts.end(), out_sil_counts);
         if (out_fold_ids) std::copy(folds.begin(), folds.end(), out_fold_ids);
-        *out_status = 0;
-    ASSESS_CATCH
+    });
 }

@@ -10,7 +10,7 @@
 //
 // Host round trips per level chunk: the transpose (it reads the level's nonzero count), the run count, one poll of the "any cluster
 // still active" flag every kPoll iterations, and the read of sizes / distances / iteration counts that decides the splits.
-#include "plugin_common.hip.h"
+#include "entry_common.hip.h"
 #include "kernels_cluster.hip.h"
 
 #include <climits>
@@ -35,21 +35,6 @@ size_t cluster_budget() {
     return b;
 }
 
-// the reference's initial w (bipartition.hpp:429-435): 2 x m uniform() draws of SplitMix64(seed), row 0 first (rng/rng.hpp:89-104)
-std::vector<double> splitmix_w(unsigned seed, int m) {
-    uint64_t state = seed == 0 ? 12345ull : (uint64_t)seed;
-    std::vector<double> w((size_t)2 * m);
-    for (auto& x : w) {
-        state += 0x9e3779b97f4a7c15ull;
-        uint64_t z = state;
-        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-        z = z ^ (z >> 31);
-        x = static_cast<double>(z) / static_cast<double>(UINT64_MAX);
-    }
-    return w;
-}
-
 struct Args {
     int m, n;
     int64_t nnz;
@@ -59,24 +44,13 @@ struct Args {
 
 void check_common(const Args& a) {
     if (a.m < 1 || a.n < 1) throw std::invalid_argument("the matrix must have at least one row and one column");
-    if (a.nnz < 0 || a.nnz >= INT_MAX) throw std::invalid_argument("nnz out of range");
-    if (!a.p || (a.nnz > 0 && (!a.i || !a.x))) throw std::invalid_argument("null CSC array");
-    if (a.p[0] != 0 || (int64_t)a.p[a.n] != a.nnz) throw std::invalid_argument("col_ptr must start at 0 and end at nnz");
-    for (int j = 0; j < a.n; ++j)
-        if (a.p[j + 1] < a.p[j]) throw std::invalid_argument("col_ptr must be non-decreasing");
-    for (int64_t e = 0; e < a.nnz; ++e)
-        if (a.i[e] < 0 || a.i[e] >= a.m) throw std::invalid_argument("row index out of range");
+    check_csc_lenient(a.p, a.i, a.x, a.m, a.n, a.nnz);
     if (a.maxit < 1) throw std::invalid_argument("maxit must be at least 1 (the reference reads an uninitialised h at maxit = 0)");
     if (!(a.tol < 1.0)) throw std::invalid_argument("tol must be below 1 (at tol >= 1 the reference runs no iteration)");
 }
 unsigned seed_of(double s) {
     if (!(s >= 0.0 && s <= 4294967295.0)) throw std::invalid_argument("seed must be in [0, 2^32)");
     return static_cast<unsigned>(s);
-}
-
-template <class T> T* grow(DevBuf& b, size_t count) {
-    if (b.bytes < count * sizeof(T) || !b.p) b.alloc(count * sizeof(T));
-    return b.as<T>();
 }
 
 // One call's device state: A uploaded once, perm, and level buffers sized for the largest level.
@@ -99,7 +73,8 @@ struct Engine {
         upload_ints(a.i, (size_t)std::max<int64_t>(a.nnz, 1), dAi, s);
         upload_cast<double>(g.c, a.x, (size_t)std::max<int64_t>(a.nnz, 1), dAx, s);
         upload_ints(perm.data(), perm.size(), dperm, s);
-        const std::vector<double> w0 = splitmix_w(a.seed, a.m);
+        // the reference's initial w (bipartition.hpp:429-435): 2 x m uniform() draws of SplitMix64(seed), seed 0 -> 12345, row 0 first
+        const std::vector<double> w0 = splitmix<double>(a.seed == 0 ? 12345ull : (uint64_t)a.seed, 0, (size_t)2 * a.m);
         upload_cast<double>(g.c, w0.data(), w0.size(), dw0, s);
         grow<int>(any, 1);
     }
@@ -375,15 +350,10 @@ void need(int* len, int64_t needed, const char* what) {
 
 }  // namespace
 
-#define RCPPML_CLUSTER_TRY  try { rcppml_err().clear(); *out_status = -1;
-#define RCPPML_CLUSTER_CATCH                                                        \
-    } catch (const std::exception& e) { rcppml_err() = e.what(); *out_status = -1; } \
-    catch (...) { rcppml_err() = "unknown error"; *out_status = -1; }
-
 extern "C" void rcppml_gpu_bipartition_double(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
                                               int* max_iter, double* tol, int* nonneg, double* seed, int* partition, double* v,
                                               double* center, double* dist, int* out_status) {
-    RCPPML_CLUSTER_TRY
+    entry_guard(out_status, [&] {
         const Args a = make_args(col_ptr, row_idx, values, m, n, nnz, max_iter, tol, nonneg, seed);
         std::vector<int> all(std::max(*n, 0));
         std::iota(all.begin(), all.end(), 0);
@@ -394,8 +364,7 @@ extern "C" void rcppml_gpu_bipartition_double(const int* col_ptr, const int* row
         for (int j = 0; j < std::min(a.m, a.n); ++j) v[j] = r.v[j];
         std::copy(r.center.begin(), r.center.end(), center);
         *dist = r.dist;
-        *out_status = 0;
-    RCPPML_CLUSTER_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_bipartition_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
@@ -403,7 +372,7 @@ extern "C" void rcppml_gpu_bipartition_ex(const int* col_ptr, const int* row_idx
                                           int* calc_dist, int* partition, int* partition_len, double* v, int* v_len, double* center,
                                           int* center_len, int* out_size1, int* out_size2, double* out_dist, int* out_iter,
                                           int* out_status) {
-    RCPPML_CLUSTER_TRY
+    entry_guard(out_status, [&] {
         const Args a = make_args(col_ptr, row_idx, values, m, n, nnz, max_iter, tol, nonneg, seed);
         std::vector<int> smp;
         if (samples && *n_samples > 0) smp.assign(samples, samples + *n_samples);
@@ -417,14 +386,13 @@ extern "C" void rcppml_gpu_bipartition_ex(const int* col_ptr, const int* row_idx
         std::copy(r.center.begin(), r.center.end(), center);
         *partition_len = (int)ns; *v_len = (int)ns; *center_len = 2 * a.m;
         *out_size1 = r.size1; *out_size2 = r.size2; *out_dist = r.dist; *out_iter = r.iter;
-        *out_status = 0;
-    RCPPML_CLUSTER_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_dclust_double(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
                                          int* max_clusters, int* min_samples, double* min_dist, int* max_iter, double* tol, int* nonneg,
                                          double* seed, int* assignments, int* out_num_clusters, int* out_status) {
-    RCPPML_CLUSTER_TRY
+    entry_guard(out_status, [&] {
         const Args a = make_args(col_ptr, row_idx, values, m, n, nnz, max_iter, tol, nonneg, seed);
         const Tree T = dclust_run(a, *min_samples, *min_dist, false);
         int nc = (int)T.leaves.size();
@@ -435,8 +403,7 @@ extern "C" void rcppml_gpu_dclust_double(const int* col_ptr, const int* row_idx,
             for (int k = L.off; k < L.off + L.size; ++k) assignments[T.perm[k]] = c;
         }
         *out_num_clusters = nc;
-        *out_status = 0;
-    RCPPML_CLUSTER_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_dclust_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
@@ -444,7 +411,7 @@ extern "C" void rcppml_gpu_dclust_ex(const int* col_ptr, const int* row_idx, con
                                      int* assignments, int* cluster_cap, int* out_size, double* out_radius, int* out_node,
                                      double* out_center, int* node_cap, int* node_parent, int* node_bit, int* node_iter,
                                      int* out_status) {
-    RCPPML_CLUSTER_TRY
+    entry_guard(out_status, [&] {
         const Args a = make_args(col_ptr, row_idx, values, m, n, nnz, max_iter, tol, nonneg, seed);
         if (!cluster_cap || !node_cap) throw std::invalid_argument("capacity pointer is NULL");
         const Tree T = dclust_run(a, *min_samples, *min_dist, out_center != nullptr);
@@ -460,6 +427,5 @@ extern "C" void rcppml_gpu_dclust_ex(const int* col_ptr, const int* row_idx, con
         for (int k = 0; k < N; ++k) { node_parent[k] = T.nodes[k].parent; node_bit[k] = T.nodes[k].bit; node_iter[k] = T.nodes[k].iter; }
         if (out_center) std::copy(T.centers.begin(), T.centers.end(), out_center);
         *cluster_cap = L; *node_cap = N;
-        *out_status = 0;
-    RCPPML_CLUSTER_CATCH
+    });
 }

@@ -12,7 +12,7 @@
 // Rules where the reference is undefined: equal similarities go to the lower index; a zero-norm row has similarity 0 to everything.
 // Tree ties: among equal smallest dissimilarities the pair with the smallest lower index, then the smallest upper index, is merged
 // (believed to be what R's hclust does; not verified against R).
-#include "plugin_common.hip.h"
+#include "entry_common.hip.h"
 #include "kernels_consensus.hip.h"
 
 #include <cmath>
@@ -25,29 +25,6 @@ using namespace rcppml_plugin;
 using namespace rcons;
 
 constexpr size_t kStripBytes = size_t(64) << 20;     // sim strip scratch
-
-struct Stream {
-    hipStream_t s = nullptr;
-    Stream() { HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-    ~Stream() { if (s) (void)hipStreamDestroy(s); }
-};
-
-// device present, device selected, `need` bytes free
-void device_ready(size_t need) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {
-        (void)hipGetLastError();
-        throw std::runtime_error("no HIP device");
-    }
-    const int dev = env_device();
-    if (dev < 0 || dev >= count) throw std::runtime_error("RCPPML_GPU_DEVICE names no device");
-    HIPCHK(hipSetDevice(dev));
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    if (need > free_b)
-        throw std::runtime_error("the call needs " + std::to_string(need) + " bytes of device memory, " + std::to_string(free_b) +
-                                 " are free");
-}
 
 unsigned blocks(int64_t n, int per) {
     const int64_t b = (n + per - 1) / per;
@@ -185,14 +162,9 @@ Tree hclust_average(const double* dist, int64_t m, int k_cut) {
 
 }  // namespace
 
-#define CONS_TRY  if (!out_status) return; try { rcppml_err().clear();
-#define CONS_CATCH                                                                  \
-    } catch (const std::exception& e) { rcppml_err() = e.what(); *out_status = -1; } \
-    catch (...) { rcppml_err() = "unknown error"; *out_status = -1; }
-
 extern "C" void rcppml_gpu_consensus_double(const double* W_stack, int* m, int* k, int* reps, int* method, int* knn,
                                             double* out_consensus, int* out_labels, int* out_status) {
-    CONS_TRY
+    entry_guard(out_status, [&] {
         if (!m || !k || !reps || !method || !knn) throw std::invalid_argument("null scalar argument");
         if (*m < 2) throw std::invalid_argument("m must be >= 2");
         if (*k < 1) throw std::invalid_argument("k must be >= 1");
@@ -257,13 +229,12 @@ extern "C" void rcppml_gpu_consensus_double(const double* W_stack, int* m, int* 
         HIPCHK(hipStreamSynchronize(st.s));
         HIPCHK(hipMemcpy(out_consensus, dOut.p, 8 * (size_t)M * (size_t)M, hipMemcpyDeviceToHost));
         if (hard && out_labels) std::copy(lab.begin(), lab.end(), out_labels);
-        *out_status = 0;
-    CONS_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_hclust_average_double(const double* dist, int* m, int* k_cut, int* out_merge, double* out_height,
                                                  int* out_clusters, double* out_cophenetic, int* out_status) {
-    CONS_TRY
+    entry_guard(out_status, [&] {
         if (!m || !k_cut) throw std::invalid_argument("null scalar argument");
         if (*m < 2) throw std::invalid_argument("m must be >= 2");
         if (*k_cut < 1 || *k_cut > *m) throw std::invalid_argument("k_cut must lie in [1, m]");
@@ -278,6 +249,5 @@ extern "C" void rcppml_gpu_hclust_average_double(const double* dist, int* m, int
         std::copy(t.height.begin(), t.height.end(), out_height);
         std::copy(t.clusters.begin(), t.clusters.end(), out_clusters);
         *out_cophenetic = t.cophenetic;
-        *out_status = 0;
-    CONS_CATCH
+    });
 }

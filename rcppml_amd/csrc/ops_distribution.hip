@@ -9,7 +9,7 @@
 // on m, n or k below 1, both or neither matrix forms, a malformed CSC (rows strictly increasing within a column: the dgCMatrix
 // invariant, and what keeps the per-nonzero overwrite of phi race-free), non-finite values in the matrix or the model, arguments
 // outside their range, a call that does not fit in free device memory (the message gives the byte count), or no device.
-#include "plugin_common.hip.h"
+#include "entry_common.hip.h"
 #include "kernels_distribution.hip.h"
 
 #include <cmath>
@@ -31,11 +31,6 @@ struct In {
     const double *W_T = nullptr, *d = nullptr, *H = nullptr;
 };
 
-void all_finite(const double* v, size_t count, const char* what) {
-    for (size_t q = 0; q < count; ++q)
-        if (!std::isfinite(v[q])) throw std::invalid_argument(std::string(what) + " holds a non-finite value");
-}
-
 In read_in(const int* col_ptr, const int* row_idx, const double* values, const int* nnz, const double* dense, const int* m,
            const int* n, const int* k, const double* W_T, const double* d, const double* H) {
     if (!m || !n || !k) throw std::invalid_argument("null scalar argument");
@@ -49,15 +44,7 @@ In read_in(const int* col_ptr, const int* row_idx, const double* values, const i
         if (!nnz || *nnz < 0) throw std::invalid_argument("nnz must be >= 0");
         if (*nnz > 0 && (!row_idx || !values)) throw std::invalid_argument("null CSC array");
         in.p = col_ptr; in.i = row_idx; in.x = values; in.nnz = *nnz;
-        if (col_ptr[0] != 0 || col_ptr[in.n] != *nnz) throw std::invalid_argument("malformed CSC: col_ptr[0] != 0 or col_ptr[n] != nnz");
-        for (int64_t j = 0; j < in.n; ++j) {
-            if (col_ptr[j + 1] < col_ptr[j]) throw std::invalid_argument("malformed CSC: col_ptr decreases");
-            for (int e = col_ptr[j]; e < col_ptr[j + 1]; ++e) {
-                if (row_idx[e] < 0 || row_idx[e] >= in.m) throw std::invalid_argument("malformed CSC: a row index outside [0, m)");
-                if (e > col_ptr[j] && row_idx[e] <= row_idx[e - 1])
-                    throw std::invalid_argument("malformed CSC: row indices not strictly increasing within a column");
-            }
-        }
+        check_csc_strict(col_ptr, row_idx, in.m, in.n, in.nnz);
         all_finite(values, (size_t)in.nnz, "the matrix");
     } else {
         in.dense = dense;
@@ -69,47 +56,9 @@ In read_in(const int* col_ptr, const int* row_idx, const double* values, const i
     return in;
 }
 
-// device present, device selected, `need` bytes free
-void device_ready(size_t need) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {
-        (void)hipGetLastError();
-        throw std::runtime_error("no HIP device");
-    }
-    const int dev = env_device();
-    if (dev < 0 || dev >= count) throw std::runtime_error("RCPPML_GPU_DEVICE names no device");
-    HIPCHK(hipSetDevice(dev));
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    if (need > free_b)
-        throw std::runtime_error("the call needs " + std::to_string(need) + " bytes of device memory, " + std::to_string(free_b) +
-                                 " are free");
-}
-
 size_t model_bytes(const In& in) { return 8 * ((size_t)in.k * (size_t)(2 * in.m + in.n) + in.k); }
 size_t matrix_bytes(const In& in) {
     return in.dense ? 8 * (size_t)(in.m * in.n) : (size_t)(in.n + 1) * 4 + (size_t)in.nnz * 12;
-}
-
-struct Stream {
-    hipStream_t s = nullptr;
-    Stream() { HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-    ~Stream() { if (s) (void)hipStreamDestroy(s); }
-};
-
-template <class T> T* upload(DevBuf& b, const T* h, size_t count, hipStream_t s) {
-    b.alloc(std::max<size_t>(count, 1) * sizeof(T));
-    if (count) HIPCHK(hipMemcpyAsync(b.p, h, count * sizeof(T), hipMemcpyHostToDevice, s));
-    return b.as<T>();
-}
-template <class T> T* zeros(DevBuf& b, size_t count, hipStream_t s) {
-    b.alloc(std::max<size_t>(count, 1) * sizeof(T));
-    HIPCHK(hipMemsetAsync(b.p, 0, std::max<size_t>(count, 1) * sizeof(T), s));
-    return b.as<T>();
-}
-template <class T> void download(T* h, const DevBuf& b, size_t count, hipStream_t s) {
-    if (count) HIPCHK(hipMemcpyAsync(h, b.p, count * sizeof(T), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
 }
 
 // The matrix and the model on the device; a = W_T * d formed on the host (R's W %*% diag(d), one rounding per element).
@@ -154,17 +103,12 @@ constexpr int kGlobBlocks = 2048;
 
 }  // namespace
 
-#define DIST_TRY  if (!out_status) return; try { rcppml_err().clear();
-#define DIST_CATCH                                                                  \
-    } catch (const std::exception& e) { rcppml_err() = e.what(); *out_status = -1; } \
-    catch (...) { rcppml_err() = "unknown error"; *out_status = -1; }
-
 extern "C" void rcppml_gpu_score_test_double(const int* col_ptr, const int* row_idx, const double* values, int* nnz,
                                              const double* dense, int* m, int* n, int* k, const double* W_T, const double* d,
                                              const double* H, const double* powers, int* n_powers, double* min_mu,
                                              double* out_T, double* out_T_nb, int* out_all_integer, int64_t* out_count,
                                              int* out_status) {
-    DIST_TRY
+    entry_guard(out_status, [&] {
         const In in = read_in(col_ptr, row_idx, values, nnz, dense, m, n, k, W_T, d, H);
         if (!n_powers || *n_powers < 1 || *n_powers > MAXP)
             throw std::invalid_argument("n_powers must be in [1, " + std::to_string(MAXP) + "]");
@@ -196,22 +140,21 @@ extern "C" void rcppml_gpu_score_test_double(const int* col_ptr, const int* row_
         HIPCHK(hipGetLastError());
         std::vector<double> s((size_t)np + 1);
         unsigned long long c[2];
-        download(s.data(), sums, s.size(), st.s);
-        download(c, cnt, 2, st.s);
+        download(s.data(), sums.as<double>(), s.size(), st.s);
+        download(c, cnt.as<unsigned long long>(), 2, st.s);
         const double count = in.dense ? (double)in.m * (double)in.n : (double)c[0];
         for (int q = 0; q < np; ++q) out_T[q] = s[q] / count;
         *out_T_nb = s[np] / count;
         *out_all_integer = c[1] == 0 ? 1 : 0;
         *out_count = in.dense ? in.m * in.n : (int64_t)c[0];
-        *out_status = 0;
-    DIST_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_zero_inflation_double(const int* col_ptr, const int* row_idx, const double* values, int* nnz,
                                                  const double* dense, int* m, int* n, int* k, const double* W_T, const double* d,
                                                  const double* H, double* out_expected_row, double* out_expected_col,
                                                  double* out_observed_row, double* out_observed_col, int* out_status) {
-    DIST_TRY
+    entry_guard(out_status, [&] {
         const In in = read_in(col_ptr, row_idx, values, nnz, dense, m, n, k, W_T, d, H);
         if (!out_expected_row || !out_expected_col || !out_observed_row || !out_observed_col)
             throw std::invalid_argument("null output");
@@ -236,12 +179,12 @@ extern "C" void rcppml_gpu_zero_inflation_double(const int* col_ptr, const int* 
                            ecol.as<double>());
         HIPCHK(hipGetLastError());
         std::vector<double> er((size_t)in.m), ec((size_t)in.n), orow((size_t)in.m), ocol((size_t)in.n);
-        download(er.data(), erow, er.size(), st.s);
-        download(ec.data(), ecol, ec.size(), st.s);
+        download(er.data(), erow.as<double>(), er.size(), st.s);
+        download(ec.data(), ecol.as<double>(), ec.size(), st.s);
         if (in.dense) {
             std::vector<unsigned long long> zr((size_t)in.m), zc((size_t)in.n);
-            download(zr.data(), zrow, zr.size(), st.s);
-            download(zc.data(), zcol, zc.size(), st.s);
+            download(zr.data(), zrow.as<unsigned long long>(), zr.size(), st.s);
+            download(zc.data(), zcol.as<unsigned long long>(), zc.size(), st.s);
             for (int64_t r = 0; r < in.m; ++r) orow[r] = (double)zr[r];
             for (int64_t j = 0; j < in.n; ++j) ocol[j] = (double)zc[j];
         } else {
@@ -255,15 +198,14 @@ extern "C" void rcppml_gpu_zero_inflation_double(const int* col_ptr, const int* 
         std::copy(ec.begin(), ec.end(), out_expected_col);
         std::copy(orow.begin(), orow.end(), out_observed_row);
         std::copy(ocol.begin(), ocol.end(), out_observed_col);
-        *out_status = 0;
-    DIST_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_dispersion_double(const int* col_ptr, const int* row_idx, const double* values, int* nnz,
                                              const double* dense, int* m, int* n, int* k, const double* W_T, const double* d,
                                              const double* H, double* power, double* min_mu, double* trim, double* out_row_phi,
                                              double* out_col_phi, double* out_global_phi, int* out_status) {
-    DIST_TRY
+    entry_guard(out_status, [&] {
         const In in = read_in(col_ptr, row_idx, values, nnz, dense, m, n, k, W_T, d, H);
         if (!power || !min_mu || !trim) throw std::invalid_argument("null argument");
         if (!std::isfinite(*power)) throw std::invalid_argument("power must be finite");
@@ -320,12 +262,11 @@ extern "C" void rcppml_gpu_dispersion_double(const int* col_ptr, const int* row_
         HIPCHK(hipGetLastError());
         std::vector<double> rp((size_t)in.m), cp((size_t)in.n);
         double gv = 0;
-        download(rp.data(), rphi, rp.size(), st.s);
-        download(cp.data(), cphi, cp.size(), st.s);
-        download(&gv, gphi, 1, st.s);
+        download(rp.data(), rphi.as<double>(), rp.size(), st.s);
+        download(cp.data(), cphi.as<double>(), cp.size(), st.s);
+        download(&gv, gphi.as<double>(), 1, st.s);
         std::copy(rp.begin(), rp.end(), out_row_phi);
         std::copy(cp.begin(), cp.end(), out_col_phi);
         *out_global_phi = gv;
-        *out_status = 0;
-    DIST_CATCH
+    });
 }

@@ -13,7 +13,7 @@
 //
 // Edge cases where R is undefined: with no labelled column at all (sum(counts) = 0) the whitening is skipped (R divides by zero);
 // the target is zero either way.
-#include "plugin_common.hip.h"
+#include "entry_common.hip.h"
 #include "kernels_refine.hip.h"
 
 #include <cmath>
@@ -24,41 +24,6 @@
 namespace {
 using namespace rcppml_plugin;
 using namespace rref;
-
-void all_finite(const double* v, size_t count, const char* what) {
-    for (size_t q = 0; q < count; ++q)
-        if (!std::isfinite(v[q])) throw std::invalid_argument(std::string(what) + " holds a non-finite value");
-}
-
-// device present, device selected, `need` bytes free
-void device_ready(size_t need) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {
-        (void)hipGetLastError();
-        throw std::runtime_error("no HIP device");
-    }
-    const int dev = env_device();
-    if (dev < 0 || dev >= count) throw std::runtime_error("RCPPML_GPU_DEVICE names no device");
-    HIPCHK(hipSetDevice(dev));
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    if (need > free_b)
-        throw std::runtime_error("the call needs " + std::to_string(need) + " bytes of device memory, " + std::to_string(free_b) +
-                                 " are free");
-}
-
-template <class T> T* upload(DevBuf& b, const T* h, size_t count, hipStream_t s) {
-    b.alloc(std::max<size_t>(count, 1) * sizeof(T));
-    if (count) {
-        HIPCHK(hipMemcpyAsync(b.p, h, count * sizeof(T), hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return b.as<T>();
-}
-template <class T> void download(T* h, const void* dev, size_t count, hipStream_t s) {
-    if (count) HIPCHK(hipMemcpyAsync(h, dev, count * sizeof(T), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-}
 
 unsigned grid_for(int64_t total) {
     const int64_t b = (total + NT - 1) / NT;
@@ -236,6 +201,7 @@ struct TargetStage {
         upload(dStart, L.chunk_start.data(), L.chunk_start.size(), s);
         upload(dLen, L.chunk_len.data(), L.chunk_len.size(), s);
         upload(dPtr, L.class_chunk_ptr.data(), L.class_chunk_ptr.size(), s);
+        HIPCHK(hipStreamSynchronize(s));          // these copies, and the caller's uploads queued before them, have landed
         dPartial.alloc(std::max<size_t>(L.chunk_start.size() * (size_t)k, 1) * 8);
         dSums.alloc(((size_t)k * L.C + 1) * 8);
         dTable.alloc(std::max<size_t>((size_t)k * L.C, 1) * 8);
@@ -274,7 +240,7 @@ struct TargetStage {
             HIPCHK(hipGetLastError());
         }
         std::vector<double> sums(kc + 1, 0.0);
-        download(sums.data(), dSums.p, dCorr ? kc + 1 : kc, s);
+        download(sums.data(), dSums.as<double>(), dCorr ? kc + 1 : kc, s);
         const double hsq = sums[kc];
         sums.resize(kc);
         double tn2 = 0;
@@ -325,15 +291,7 @@ MatIn read_matrix(const int* col_ptr, const int* row_idx, const double* values, 
         if (!nnz || *nnz < 0) throw std::invalid_argument("nnz must be >= 0");
         if (*nnz > 0 && (!row_idx || !values)) throw std::invalid_argument("null CSC array");
         in.p = col_ptr; in.i = row_idx; in.x = values; in.nnz = *nnz;
-        if (col_ptr[0] != 0 || col_ptr[n] != *nnz) throw std::invalid_argument("malformed CSC: col_ptr[0] != 0 or col_ptr[n] != nnz");
-        for (int64_t j = 0; j < n; ++j) {
-            if (col_ptr[j + 1] < col_ptr[j]) throw std::invalid_argument("malformed CSC: col_ptr decreases");
-            for (int e = col_ptr[j]; e < col_ptr[j + 1]; ++e) {
-                if (row_idx[e] < 0 || row_idx[e] >= m) throw std::invalid_argument("malformed CSC: a row index outside [0, m)");
-                if (e > col_ptr[j] && row_idx[e] <= row_idx[e - 1])
-                    throw std::invalid_argument("malformed CSC: row indices not strictly increasing within a column");
-            }
-        }
+        check_csc_strict(col_ptr, row_idx, m, n, in.nnz);
         all_finite(values, (size_t)in.nnz, "the matrix");
     } else {
         in.dense = dense;
@@ -361,11 +319,13 @@ struct DevMatrix {
     DevMatrix(rcppml_hip_ctx* c_, const MatIn& in_, int k_, hipStream_t s) : c(c_), in(in_), k(k_) {
         if (in.dense) {
             upload(X, in.dense, (size_t)(in.m * in.n), s);
+            HIPCHK(hipStreamSynchronize(s));
             return;
         }
         upload(Ap, in.p, (size_t)in.n + 1, s);
         upload(Ai, in.i, (size_t)in.nnz, s);
         upload(Ax, in.x, (size_t)in.nnz, s);
+        HIPCHK(hipStreamSynchronize(s));
         Tp.alloc(((size_t)in.m + 1) * 4);
         Ti.alloc(std::max<size_t>((size_t)in.nnz, 1) * 4);
         Tx.alloc(std::max<size_t>((size_t)in.nnz, 1) * 8);
@@ -411,14 +371,9 @@ void check_refit_rank(int k) {
 
 }  // namespace
 
-#define REF_TRY  if (!out_status) return; try { rcppml_err().clear();
-#define REF_CATCH                                                                   \
-    } catch (const std::exception& e) { rcppml_err() = e.what(); *out_status = -1; } \
-    catch (...) { rcppml_err() = "unknown error"; *out_status = -1; }
-
 extern "C" void rcppml_gpu_compute_target_double(const double* H, const int* labels, int* k, int* n, int* n_classes, int* whiten,
                                                  double* out_target, double* out_shift, int* out_counts, int* out_status) {
-    REF_TRY
+    entry_guard(out_status, [&] {
         const Dims D = read_dims(k, n, n_classes);
         if (!whiten) throw std::invalid_argument("null scalar argument");
         if (!H) throw std::invalid_argument("null H");
@@ -438,14 +393,13 @@ extern "C" void rcppml_gpu_compute_target_double(const double* H, const int* lab
         HIPCHK(hipMemcpy(out_target, dT.p, (size_t)D.k * (size_t)D.n * 8, hipMemcpyDeviceToHost));
         if (out_shift) std::copy(ts.shift.begin(), ts.shift.end(), out_shift);
         if (out_counts) std::copy(L.counts.begin(), L.counts.end(), out_counts);
-        *out_status = 0;
-    REF_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_refine_correct_double(const double* H, const int* labels, int* k, int* n, int* n_classes, int* whiten,
                                                  double* lambda, int* nonneg, double* out_H_corr, double* out_target,
                                                  int* out_status) {
-    REF_TRY
+    entry_guard(out_status, [&] {
         const Dims D = read_dims(k, n, n_classes);
         if (!whiten || !nonneg) throw std::invalid_argument("null scalar argument");
         check_lambda(lambda);
@@ -466,14 +420,13 @@ extern "C" void rcppml_gpu_refine_correct_double(const double* H, const int* lab
         HIPCHK(hipStreamSynchronize(g.s));
         HIPCHK(hipMemcpy(out_H_corr, dC.p, kn * 8, hipMemcpyDeviceToHost));
         if (out_target) HIPCHK(hipMemcpy(out_target, dT.p, kn * 8, hipMemcpyDeviceToHost));
-        *out_status = 0;
-    REF_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_refine_wfit_double(const int* col_ptr, const int* row_idx, const double* values, int* nnz,
                                               const double* dense, int* m, int* n, int* k, const double* d, const double* H_corr,
                                               int* nonneg, double* out_W, int* out_status) {
-    REF_TRY
+    entry_guard(out_status, [&] {
         if (!m || !n || !k || !nonneg) throw std::invalid_argument("null scalar argument");
         if (*m < 1 || *n < 1 || *k < 1) throw std::invalid_argument("m, n and k must be >= 1");
         check_refit_rank(*k);
@@ -491,18 +444,18 @@ extern "C" void rcppml_gpu_refine_wfit_double(const int* col_ptr, const int* row
         DevBuf dHc, dd, dHd((size_t)K * N * 8), dG((size_t)K * K * 8), dBw((size_t)K * M * 8), dW((size_t)K * M * 8);
         upload(dHc, H_corr, (size_t)K * (size_t)N, g.s);
         upload(dd, d, (size_t)K, g.s);
+        HIPCHK(hipStreamSynchronize(g.s));
         refit_W(g.c, A, K, M, N, dHc.p, dd.p, *nonneg != 0, dHd, dG, dBw, dW.p);
         HIPCHK(hipStreamSynchronize(g.s));
         HIPCHK(hipMemcpy(out_W, dW.p, (size_t)K * (size_t)M * 8, hipMemcpyDeviceToHost));
-        *out_status = 0;
-    REF_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_refine_double(const int* col_ptr, const int* row_idx, const double* values, int* nnz, const double* dense,
                                          int* m, int* n, int* k, const double* W_T, const double* d, const double* H,
                                          const int* labels, int* n_classes, double* lambda, int* cycles, int* nonneg, int* whiten,
                                          double* out_W, double* out_d, double* out_H, double* out_H_corr, int* out_status) {
-    REF_TRY
+    entry_guard(out_status, [&] {
         if (!m) throw std::invalid_argument("null scalar argument");
         if (*m < 1) throw std::invalid_argument("m must be >= 1");
         const Dims D = read_dims(k, n, n_classes);
@@ -556,14 +509,13 @@ extern "C" void rcppml_gpu_refine_double(const int* col_ptr, const int* row_idx,
         }
         // nothing is written to the caller's buffers before the device work has succeeded
         std::vector<double> hW(km), hd((size_t)K), hH(kn), hC(kn);
-        download(hW.data(), dW.p, km, g.s);
-        download(hd.data(), dd.p, (size_t)K, g.s);
-        download(hH.data(), dH.p, kn, g.s);
-        download(hC.data(), dHc.p, kn, g.s);
+        download(hW.data(), dW.as<double>(), km, g.s);
+        download(hd.data(), dd.as<double>(), (size_t)K, g.s);
+        download(hH.data(), dH.as<double>(), kn, g.s);
+        download(hC.data(), dHc.as<double>(), kn, g.s);
         std::copy(hW.begin(), hW.end(), out_W);
         std::copy(hd.begin(), hd.end(), out_d);
         std::copy(hH.begin(), hH.end(), out_H);
         std::copy(hC.begin(), hC.end(), out_H_corr);
-        *out_status = 0;
-    REF_CATCH
+    });
 }

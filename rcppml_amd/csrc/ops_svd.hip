@@ -12,7 +12,7 @@
 // Anything else is refused (status -1, reason in rcppml_gpu_last_error, no output written).
 //
 // Centering never densifies: A'u - (mu . u) 1 and A v - mu sum(v) are scalar corrections inside the epilogues.
-#include "plugin_common.hip.h"
+#include "entry_common.hip.h"
 #include "kernels_svd.hip.h"
 
 #include <chrono>
@@ -27,26 +27,6 @@ constexpr int kPoll = 8;
 
 int nblk(long len) { return (int)((len + CH - 1) / CH); }
 int wblk(long len) { return (int)((len + NW - 1) / NW); }
-
-template <class T> T* grow(DevBuf& b, size_t count) {
-    if (b.bytes < count * sizeof(T) || !b.p) b.alloc(count * sizeof(T));
-    return b.as<T>();
-}
-
-// SplitMix64 uniform<S>() draws (rng/rng.hpp:89-104): draw `off` .. off + count - 1 of the stream of `seed`
-template <class S> std::vector<S> splitmix(uint64_t seed, uint64_t off, size_t count) {
-    std::vector<S> out(count);
-    uint64_t state = seed + off * 0x9e3779b97f4a7c15ull;
-    for (auto& x : out) {
-        state += 0x9e3779b97f4a7c15ull;
-        uint64_t z = state;
-        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-        z = z ^ (z >> 31);
-        x = static_cast<S>(z) / static_cast<S>(UINT64_MAX);
-    }
-    return out;
-}
 
 struct Opts {
     int m, n, k;
@@ -521,16 +501,6 @@ template <class T> void run_entry(const Raw& a, Opts o) {
     write_out(a, o, R, ms);
 }
 
-void check_csc(const Opts& o) {
-    if (o.nnz < 0 || o.nnz >= INT_MAX) throw std::invalid_argument("nnz out of range");
-    if (!o.p || (o.nnz > 0 && (!o.i || !o.x))) throw std::invalid_argument("null CSC array");
-    if (o.p[0] != 0 || (int64_t)o.p[o.n] != o.nnz) throw std::invalid_argument("col_ptr must start at 0 and end at nnz");
-    for (int j = 0; j < o.n; ++j)
-        if (o.p[j + 1] < o.p[j]) throw std::invalid_argument("col_ptr must be non-decreasing");
-    for (int64_t e = 0; e < o.nnz; ++e)
-        if (o.i[e] < 0 || o.i[e] >= o.m) throw std::invalid_argument("row index out of range");
-}
-
 }  // namespace
 
 #define RCPPML_SVD_PARAMS                                                                                                         \
@@ -548,31 +518,24 @@ void check_csc(const Opts& o) {
         L21_u, L21_v, angular_u, angular_v, test_fraction, cv_seed, patience, mask_zeros, algorithm, graph_u_nnz,                 \
         graph_u_lambda_val, graph_v_nnz, graph_v_lambda_val, obs_mask_nnz, out_k_selected, out_wall_time_ms,                      \
         out_iters_per_factor, out_frobenius_norm_sq, out_row_means, robust_delta}
-#define RCPPML_SVD_TRY  try { rcppml_err().clear(); *out_status = -1;
-#define RCPPML_SVD_CATCH                                                            \
-    } catch (const std::exception& e) { rcppml_err() = e.what(); *out_status = -1; } \
-    catch (...) { rcppml_err() = "unknown error"; *out_status = -1; }
-
 template <class T>
 static void svd_sparse(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz, const Raw& a,
                        int* out_status) {
-    RCPPML_SVD_TRY
+    entry_guard(out_status, [&] {
         Opts o = make_opts(a, *m, *n);
         o.nnz = *nnz; o.p = col_ptr; o.i = row_idx; o.x = values;
-        check_csc(o);
+        check_csc_lenient(o.p, o.i, o.x, o.m, o.n, o.nnz);
         run_entry<T>(a, o);
-        *out_status = 0;
-    RCPPML_SVD_CATCH
+    });
 }
 template <class T>
 static void svd_dense(const double* A, int* m, int* n, const Raw& a, int* out_status) {
-    RCPPML_SVD_TRY
+    entry_guard(out_status, [&] {
         Opts o = make_opts(a, *m, *n);
         if (!A) throw std::invalid_argument("null matrix");
         o.nnz = (int64_t)*m * *n; o.dense = A;
         run_entry<T>(a, o);
-        *out_status = 0;
-    RCPPML_SVD_CATCH
+    });
 }
 
 extern "C" void rcppml_gpu_svd_pca_double(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,

@@ -35,15 +35,7 @@ void validate_common(int loss_type, int zi_mode, int zi_em_iters, int dispersion
 
 void validate_csc(const int* col_ptr, const int* row_idx, int64_t m, int64_t n, int64_t nnz) {
     if (!col_ptr || (nnz > 0 && !row_idx)) throw std::invalid_argument("null CSC array");
-    if (col_ptr[0] != 0 || col_ptr[n] != nnz) throw std::invalid_argument("malformed CSC: col_ptr[0] != 0 or col_ptr[n] != nnz");
-    for (int64_t j = 0; j < n; ++j) {
-        if (col_ptr[j + 1] < col_ptr[j]) throw std::invalid_argument("malformed CSC: col_ptr decreases");
-        for (int e = col_ptr[j]; e < col_ptr[j + 1]; ++e) {
-            if (row_idx[e] < 0 || row_idx[e] >= m) throw std::invalid_argument("malformed CSC: a row index outside [0, m)");
-            if (e > col_ptr[j] && row_idx[e] <= row_idx[e - 1])
-                throw std::invalid_argument("malformed CSC: row indices not strictly increasing within a column");
-        }
-    }
+    check_csc_strict(col_ptr, row_idx, m, n, nnz);
 }
 
 size_t stage_bytes(int64_t m, int64_t n, int k, int zi_mode, bool imputed, bool transposed, bool full_index) {
@@ -57,22 +49,6 @@ size_t stage_bytes(int64_t m, int64_t n, int k, int zi_mode, bool imputed, bool 
     if (transposed) b += 8 * M * N;
     if (full_index) b += 2 * 4 * M * N + 4 * (M + N + 2);
     return b;
-}
-
-void device_guard(size_t need) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {
-        (void)hipGetLastError();
-        throw std::runtime_error("no HIP device");
-    }
-    const int dev = env_device();
-    if (dev < 0 || dev >= count) throw std::runtime_error("RCPPML_GPU_DEVICE names no device");
-    HIPCHK(hipSetDevice(dev));
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    if (need > free_b)
-        throw std::runtime_error("the zero-inflated fit needs " + std::to_string(need) + " bytes of device memory, " +
-                                 std::to_string(free_b) + " are free");
 }
 
 void pi_init_host(const int* col_ptr, const int* row_idx, int64_t m, int64_t n, int zi_mode, std::vector<double>& pi,
@@ -195,9 +171,7 @@ extern "C" void rcppml_gpu_zi_em_double(const int* col_ptr, const int* row_idx, 
                                         int* zi_mode, int* zi_em_iters, double* theta_min, double* pi, double* out_imputed,
                                         int* out_status) {
     using namespace rcppml_zi;
-    if (!out_status) return;
-    try {
-        rcppml_err().clear();
+    entry_guard(out_status, [&] {
         if (!m || !n || !k || !nnz || !loss_type || !zi_mode || !zi_em_iters || !theta_min) throw std::invalid_argument("null scalar argument");
         if (*m < 1 || *n < 1) throw std::invalid_argument("m and n must be >= 1");
         validate_common(*loss_type, *zi_mode, *zi_em_iters, 2, *k);
@@ -208,37 +182,30 @@ extern "C" void rcppml_gpu_zi_em_double(const int* col_ptr, const int* row_idx, 
         const int64_t M = *m, N = *n, NNZ = *nnz;
         const int K = *k;
         validate_csc(col_ptr, row_idx, M, N, NNZ);
-        auto finite = [](const double* v, size_t cnt, const char* what) {
-            for (size_t q = 0; q < cnt; ++q)
-                if (!std::isfinite(v[q])) throw std::invalid_argument(std::string(what) + " holds a non-finite value");
-        };
-        finite(values, (size_t)NNZ, "the matrix");
-        finite(W_T, (size_t)K * M, "W");
-        finite(d, (size_t)K, "d");
-        finite(H, (size_t)K * N, "H");
-        finite(disp, (size_t)M, "the dispersion vector");
+        all_finite(values, (size_t)NNZ, "the matrix");
+        all_finite(W_T, (size_t)K * M, "W");
+        all_finite(d, (size_t)K, "d");
+        all_finite(H, (size_t)K * N, "H");
+        all_finite(disp, (size_t)M, "the dispersion vector");
         const int64_t L = *zi_mode == 1 ? M : N;
-        finite(pi, (size_t)L, "pi");
+        all_finite(pi, (size_t)L, "pi");
         for (int64_t q = 0; q < L; ++q)
             if (pi[q] < 0.0 || pi[q] > 1.0) throw std::invalid_argument("pi must lie in [0, 1]");
         const bool want = out_imputed != nullptr;
-        device_guard(stage_bytes(M, N, K, *zi_mode, want, false, false) + (size_t)(N + 1) * 4 + (size_t)NNZ * 12 +
-                     8 * ((size_t)K * (size_t)(M + N) + K + M) + 65536);
+        device_ready(stage_bytes(M, N, K, *zi_mode, want, false, false) + (size_t)(N + 1) * 4 + (size_t)NNZ * 12 +
+                         8 * ((size_t)K * (size_t)(M + N) + K + M) + 65536,
+                     "the zero-inflated fit");
         CtxGuard g(env_device());
         hipStream_t s = g.s;
         DevBuf dp, di, dx, dW, dd, dH, ddisp;
         upload_ints(col_ptr, (size_t)N + 1, dp, s);
         if (NNZ > 0) upload_ints(row_idx, (size_t)NNZ, di, s);
         else di.alloc(16);
-        auto up = [&](DevBuf& b, const double* h, size_t cnt) {
-            b.alloc(std::max<size_t>(cnt, 1) * 8);
-            if (cnt) HIPCHK(hipMemcpyAsync(b.p, h, cnt * 8, hipMemcpyHostToDevice, s));
-        };
-        up(dx, values, (size_t)NNZ);
-        up(dW, W_T, (size_t)K * M);
-        up(dd, d, (size_t)K);
-        up(dH, H, (size_t)K * N);
-        up(ddisp, disp, (size_t)M);
+        upload(dx, values, (size_t)NNZ, s);
+        upload(dW, W_T, (size_t)K * M, s);
+        upload(dd, d, (size_t)K, s);
+        upload(dH, H, (size_t)K * N, s);
+        upload(ddisp, disp, (size_t)M, s);
         std::vector<double> pi0;
         std::vector<int> zc;
         pi_init_host(col_ptr, row_idx, M, N, *zi_mode, pi0, zc);
@@ -253,7 +220,5 @@ extern "C" void rcppml_gpu_zi_em_double(const int* col_ptr, const int* row_idx, 
         HIPCHK(hipStreamSynchronize(s));
         std::copy(hpi.begin(), hpi.end(), pi);
         std::copy(hdisp.begin(), hdisp.end(), disp);
-        *out_status = 0;
-    } catch (const std::exception& e) { rcppml_err() = e.what(); *out_status = -1; }
-    catch (...) { rcppml_err() = "unknown error"; *out_status = -1; }
+    });
 }

@@ -1355,9 +1355,7 @@ extern "C" void rcppml_gpu_nmf_zi_double(const int* col_ptr, const int* row_idx,
                                          double* nb_size_min, int* sort_model, int* zi_mode, int* zi_em_iters, double* loss_history,
                                          double* out_theta, int* out_theta_len, double* out_pi, int* out_pi_len, int* out_iter,
                                          int* out_converged, double* out_loss, double* out_tol, int* out_status) {
-    if (!out_status) return;
-    try {
-        rcppml_err().clear();
+    entry_guard(out_status, [&] {
         if (!m || !n || !nnz || !k || !max_iter || !tol || !L1_H || !L1_W || !L2_H || !L2_W || !ub_H || !ub_W || !cd_maxit || !cd_tol ||
             !verbose || !patience || !nonneg_W || !nonneg_H || !loss_type || !irls_max_iter || !irls_tol || !norm_type ||
             !dispersion_mode || !gp_theta_init || !gp_theta_max || !gp_theta_min || !nb_size_init || !nb_size_max || !nb_size_min ||
@@ -1375,7 +1373,7 @@ extern "C" void rcppml_gpu_nmf_zi_double(const int* col_ptr, const int* row_idx,
         // the memory guard comes before every allocation: the stage's arrays (two m x n fp64 arrays, two m n int32 index arrays, the
         // bitmask, the tile partials) plus what the plain IRLS fit takes (the CSC twice, factors, right-hand sides)
         const size_t plain = (size_t)96 * (size_t)std::max(*nnz, 1) + (size_t)96 * (size_t)*k * ((size_t)*m + (size_t)*n) + ((size_t)256 << 20);
-        rcppml_zi::device_guard(rcppml_zi::stage_bytes(*m, *n, *k, *zi_mode, true, true, true) + plain);
+        device_ready(rcppml_zi::stage_bytes(*m, *n, *k, *zi_mode, true, true, true) + plain, "the zero-inflated fit");
         if ((int64_t)*m * (int64_t)*n >= ((int64_t)1 << 31))
             throw std::invalid_argument("zero-inflated fit: m * n must be below 2^31 (the dense IRLS half-updates index A_imputed with 32-bit offsets)");
         FitParams P;
@@ -1401,18 +1399,14 @@ extern "C" void rcppml_gpu_nmf_zi_double(const int* col_ptr, const int* row_idx,
         std::copy(pi.begin(), pi.begin() + P.out_pi_len, out_pi);
         *out_theta_len = P.out_theta_len; *out_pi_len = P.out_pi_len;
         *out_iter = P.out_iter; *out_converged = P.out_converged; *out_loss = P.out_loss; *out_tol = P.out_tol;
-        *out_status = 0;
-    } catch (const std::exception& e) { rcppml_err() = e.what(); *out_status = -1; }
-    catch (...) { rcppml_err() = "unknown error"; *out_status = -1; }
+    });
 }
 
 // nnls()/predict() projection in fp64 (src/RcppFunctions_utils.cpp:313-366)
 extern "C" void rcppml_gpu_nnls_double(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n,
                                        int* nnz, int* k, const double* w_T, double* h, int* cd_maxit, double* cd_tol,
                                        double* L1, double* L2, double* ub, int* nonneg, int* warm, int* out_status) {
-    try {
-        rcppml_err().clear();
-        *out_status = -1;
+    entry_guard(out_status, [&] {
         if (*k < 1 || *k > 256) throw std::runtime_error("k must be in [1,256]");
         CtxGuard g(env_device());
         hipStream_t s = g.s;
@@ -1430,20 +1424,14 @@ extern "C" void rcppml_gpu_nnls_double(const int* col_ptr, const int* row_idx, c
         OPCHK(rcppml_hip_solve_cd(g.c, RCPPML_F64, dG.p, dB.p, dH.p, *k, *n, 0.0, *warm ? 1 : 0, *warm ? 0 : 1, *L1, 0.0,
                                   *nonneg, *cd_maxit, *warm ? 0.0 : *cd_tol, *ub, 0.0, RCPPML_CD_AUTO, nullptr, nullptr));
         download_cast<double>(g.c, dH, (size_t)*k * *n, h, s);
-        *out_status = 0;
-    } catch (const std::exception& e) {
-        rcppml_err() = e.what();
-        *out_status = -1;
-    } catch (...) { rcppml_err() = "unknown error"; *out_status = -1; }
+    });
 }
 
 // evaluate() in fp64 without densifying W H (src/RcppFunctions_utils.cpp:95-163 semantics: MEAN)
 extern "C" void rcppml_gpu_evaluate_mse_double(const int* col_ptr, const int* row_idx, const double* values, int* m,
                                                int* n, int* nnz, int* k, const double* W_T, const double* d,
                                                const double* H, int* mask_zeros, double* out_loss, int* out_status) {
-    try {
-        rcppml_err().clear();
-        *out_status = -1;
+    entry_guard(out_status, [&] {
         CtxGuard g(env_device());
         hipStream_t s = g.s;
         DevBuf dAp, dAi, dAx, dW, dH, dd;
@@ -1476,11 +1464,7 @@ extern "C" void rcppml_gpu_evaluate_mse_double(const int* col_ptr, const int* ro
             const double total = (nz[0] - nz[1]) + allp2;
             *out_loss = total / (static_cast<double>(*m) * static_cast<double>(*n));
         }
-        *out_status = 0;
-    } catch (const std::exception& e) {
-        rcppml_err() = e.what();
-        *out_status = -1;
-    } catch (...) { rcppml_err() = "unknown error"; *out_status = -1; }
+    });
 }
 
 // ----------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // zi_stage.hip.h -- host interface of the zero-inflated GP / NB stage (ops_zi.hip; kernels: kernels_zi.hip.h), shared by the stage's
 // own entry (rcppml_gpu_zi_em_double) and the ALS loop of plugin.hip (rcppml_gpu_nmf_zi_double).  fp64, sparse input, mode ROW / COL.
 #pragma once
-#include "plugin_common.hip.h"
+#include "entry_common.hip.h"
 
 namespace rcppml_zi {
 
@@ -13,9 +13,6 @@ void validate_csc(const int* col_ptr, const int* row_idx, int64_t m, int64_t n, 
 // device bytes of the stage's own arrays: the bitmask, the tile partials, the z sums, the zero counts, a = W_T o d, and -- when asked
 // for -- A_imputed, A_imputed^T (m n doubles each) and the two full index sets (m n + extent + 1 ints each)
 size_t stage_bytes(int64_t m, int64_t n, int k, int zi_mode, bool imputed, bool transposed, bool full_index);
-// selects the device (RCPPML_GPU_DEVICE) and refuses, with the byte count, a call whose `need` bytes exceed hipMemGetInfo's free
-// bytes.  Allocates and launches nothing.
-void device_guard(size_t need);
 
 // pi = min(0.5 (1 - stored / extent), 0.3) per row (ROW) or column (COL) and the counts of unstored entries, from the host CSC
 // (fit_cpu.hpp:355-400)

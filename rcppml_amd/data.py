@@ -59,6 +59,22 @@ class CSC:
         return sp.csc_matrix((self.x, self.i, self.p), shape=self.shape)
 
 
+def as_matrix(data, dense_ok=True, what="data must be a matrix"):
+    """(csc, dense) of a matrix argument, one of them None: a CSC as it is, scipy sparse input as a CSC, anything else as a 2-D
+    float64 array (ValueError(what) when it is not 2-D).  dense_ok=False: a dense matrix goes sparse too, as R's .to_dgCMatrix."""
+    if isinstance(data, CSC):
+        return data, None
+    if hasattr(data, "tocsc"):
+        return CSC.from_scipy(data), None
+    a = np.asarray(data, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError(what)
+    if dense_ok:
+        return None, a
+    import scipy.sparse as sp
+    return CSC.from_scipy(sp.csc_matrix(a)), None
+
+
 def splitmix64_raw(seed, offset, count):
     """`count` outputs of SplitMix64(seed) starting at stream position `offset` (0-based), as uint64."""
     seed = np.uint64(12345 if int(seed) == 0 else int(seed))

@@ -11,7 +11,8 @@ import numpy as np
 
 from . import _abi
 from . import nmf as _nmf
-from .data import CSC
+from ._abi import _check
+from .data import CSC, as_matrix
 
 POWER_LABELS = {"0": "gaussian", "1": "gp", "2": "gamma", "3": "inverse_gaussian"}
 DISTRIBUTIONS = ("mse", "gp", "nb")
@@ -104,15 +105,10 @@ def is_sparse(data):
 
 def _matrix(data):
     """dict(csc=CSC or None, dense=column-major float64 or None, m, n)."""
-    if isinstance(data, CSC):
-        return dict(csc=data, dense=None, m=data.rows, n=data.cols)
-    if hasattr(data, "tocsc"):
-        c = CSC.from_scipy(data)
-        return dict(csc=c, dense=None, m=c.rows, n=c.cols)
-    a = np.asarray(data, np.float64)
-    if a.ndim != 2:
-        raise ValueError("data must be a matrix")
-    return dict(csc=None, dense=np.asfortranarray(a), m=a.shape[0], n=a.shape[1])
+    csc, dense = as_matrix(data)
+    if csc is not None:
+        return dict(csc=csc, dense=None, m=csc.rows, n=csc.cols)
+    return dict(csc=None, dense=np.asfortranarray(dense), m=dense.shape[0], n=dense.shape[1])
 
 
 def _model(model, m, n):
@@ -124,12 +120,6 @@ def _model(model, m, n):
     if w.shape != (m, k) or h.shape != (k, n):
         raise ValueError("model dimensions (w %s, d %d, h %s) do not match the data (%d x %d)" % (w.shape, k, h.shape, m, n))
     return np.ascontiguousarray(w), np.ascontiguousarray(d), np.ascontiguousarray(h.T), k
-
-
-def _check(r, what):
-    if r["status"] != 0:
-        raise _abi.BackendError("GPU %s failed: %s" % (what, r["error"]))
-    return r
 
 
 # ------------------------------------------------------------------------------------------------------------ the four R functions

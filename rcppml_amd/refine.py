@@ -9,13 +9,8 @@ import numpy as np
 
 from . import _abi
 from . import nmf as _nmf
-from .data import CSC
-
-
-def _check(r, what):
-    if r["status"] != 0:
-        raise _abi.BackendError("GPU %s failed: %s" % (what, r["error"]))
-    return r
+from ._abi import _check
+from .data import as_matrix
 
 
 def _is_na(v):
@@ -64,17 +59,13 @@ def _stage1(H, codes, C, lambda_, nonneg, whiten):
 
 
 def _matrix_forms(data, m, n):
-    """(csc, dense) for the entries that take either form; a 2-D ndarray is the reference's dense matrix."""
-    if isinstance(data, np.ndarray):
-        if data.ndim != 2:
-            raise ValueError("data must be a matrix")
-        if data.shape != (m, n):
-            raise ValueError("dimensions of 'data' (%d x %d) do not match the model (%d x %d)" % (data.shape + (m, n)))
-        return None, np.asarray(data, np.float64)
-    A = data if isinstance(data, CSC) else _nmf._as_csc(data)
-    if tuple(A.shape) != (m, n):
-        raise ValueError("dimensions of 'data' (%d x %d) do not match the model (%d x %d)" % (tuple(A.shape) + (m, n)))
-    return A, None
+    """(csc, dense) for the entries that take either form; a 2-D ndarray is the reference's dense matrix, anything else goes
+    sparse."""
+    csc, dense = as_matrix(data, dense_ok=isinstance(data, np.ndarray))
+    shape = tuple((csc if dense is None else dense).shape)
+    if shape != (m, n):
+        raise ValueError("dimensions of 'data' (%d x %d) do not match the model (%d x %d)" % (shape + (m, n)))
+    return csc, dense
 
 
 def refine(x, data=None, labels=None, batch=None, lambda_=0.8, cycles=0, nonneg=True, whiten=True):

@@ -5,7 +5,7 @@ a device the calls raise BackendError."""
 import numpy as np
 
 from . import _abi
-from .data import CSC
+from .data import as_matrix
 
 VALID_METHODS = ("auto", "deflation", "krylov", "lanczos", "irlba", "randomized")
 _MISSING = object()
@@ -54,33 +54,22 @@ def resolve_method(k, method="auto", maxit=_MISSING, tol=1e-5, L1=0, L2=0, nonne
     return method, int(maxit), float(tol), (L1, L2, nonneg, upper_bound)
 
 
-def _input(A):
-    if isinstance(A, CSC):
-        return ("sparse", A)
-    if hasattr(A, "tocsc"):
-        return ("sparse", CSC.from_scipy(A))
-    a = np.asarray(A, dtype=np.float64)
-    if a.ndim != 2:
-        raise ValueError("'A' must be a matrix, dgCMatrix, or path to a .spz file")
-    return ("dense", a)
-
-
 def svd(A, k=10, tol=1e-5, maxit=_MISSING, center=False, seed=None, L1=0, L2=0, nonneg=False, upper_bound=0, method="auto",
         precision="float"):
     """Truncated SVD on the GPU (R/svd.R with resource = "gpu").  A: scipy sparse / CSC (the sparse entries) or a dense matrix (the
     dense entries).  precision: "float" (fp32 on the device, R's default) or "double".  Constrained fits with k >= 8 resolve to
     krylov, as in R, which the GPU refuses (BackendError); pass method="deflation" for them.  Returns dict(u, d, v, misc) with
     misc = dict(iters_per_factor, frobenius_norm_sq, row_means (or None), method, wall_time_ms)."""
-    kind, M = _input(A)
+    M, dense = as_matrix(A, what="'A' must be a matrix, dgCMatrix, or path to a .spz file")
     method, maxit, tol, (L1v, L2v, nn, ub) = resolve_method(k, method, maxit, tol, L1, L2, nonneg, upper_bound)
     if precision not in ("float", "double"):
         raise ValueError("precision must be 'float' or 'double'")
     s = 0 if seed is None else int(seed)
     kw = dict(precision=precision, tol=tol, max_iter=maxit, center=center, seed=s, L1=L1v, L2=L2v, nonneg=nn, upper_bound=ub,
               algorithm=_abi.SVD_ALGORITHMS[method])
-    if kind == "dense":
-        r = _abi.svd_pca(M, int(k), dense=True, **kw)
-        m = M.shape[0]
+    if dense is not None:
+        r = _abi.svd_pca(dense, int(k), dense=True, **kw)
+        m = dense.shape[0]
     else:
         r = _abi.svd_pca((M.p, M.i, M.x, M.rows, M.cols), int(k), **kw)
         m = M.rows

@@ -146,6 +146,31 @@ def test_refusals(kw, msg):
     assert all(r[k] == -7.0 for k in ("ari", "nmi", "silhouette", "knn_accuracy", "knn_f1", "batch_sil", "batch_entropy"))
 
 
+# a 3 x 2 embedding with one defect each (the assessment takes no CSC: these are its own argument checks)
+@pytest.mark.parametrize("kw, msg", [
+    (dict(labels=np.array([0, 1, 2])), "a label lies outside [0, n_classes)"),
+    (dict(batch=np.array([0, 1, 2])), "a batch label lies outside [0, n_batch)"),
+    (dict(maxiter=0), "kmeans_maxiter must be >= 1 for clustering"),
+    (dict(knn_k=0), "knn_k must be >= 1 for classification"),
+    (dict(folds=0), "knn_folds must be >= 1 for classification"),
+    (dict(batch_k=0), "batch_knn_k must be >= 1 for batch mixing"),
+])
+def test_refusals_are_exact(kw, msg):
+    """Refused before any device work (so with or without a GPU): status -1, this message, nothing written."""
+    base = dict(emb=np.arange(6.0).reshape(3, 2), labels=np.array([0, 1, 1]), n_classes=2, batch=np.array([0, 1, 0]), n_batch=2)
+    base.update(kw)
+    emb, labels, nc, batch, nb = (base.pop(k) for k in ("emb", "labels", "n_classes", "batch", "n_batch"))
+    r = _abi.assess_raw(emb, labels, nc, batch, nb, init=-7.0, **base)
+    assert (r["status"], r["error"]) == (-1, msg)
+    assert all(r[k] == -7.0 for k in ("ari", "nmi", "silhouette", "knn_accuracy", "knn_f1", "batch_sil", "batch_entropy"))
+    r = _abi.assess_ex(emb, labels, nc, batch, nb, init=-7.0, **base)
+    assert (r["status"], r["error"]) == (-1, msg)
+    assert all(r[k] == -7.0 for k in ("ari", "nmi", "silhouette", "knn_accuracy", "knn_f1", "batch_sil", "batch_entropy"))
+    b = r["buffers"]
+    assert all(np.all(b[k] == -7) for k in ("assignments", "fold_ids", "fold_accuracy", "fold_f1"))
+    assert all(np.all(np.isnan(b[k])) for k in ("restart_ari", "restart_nmi", "sil_point", "batch_entropy_point", "batch_sil_point"))
+
+
 def test_refusal_messages_are_distinct():
     msgs = {_call(**kw)["error"] for kw in (dict(maxiter=0), dict(knn_k=0), dict(folds=0), dict(batch_k=0),
                                             dict(emb=np.ones((6, 0))), dict(emb=np.ones((0, 2))))}

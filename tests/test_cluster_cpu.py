@@ -149,6 +149,29 @@ def test_abi_refuses_the_reference_hazards():
     assert _abi.bipartition_ex(p, i, x, 10, 10, seed=-1)["status"] == -1
 
 
+# a 3 x 2 matrix (p = [0, 2, 3], i = [0, 2, 1]) with one defect each; nnz is the length of x
+@pytest.mark.parametrize("p, i, msg", [
+    ([1, 2, 3], [0, 2, 1], "col_ptr must start at 0 and end at nnz"),
+    ([0, 4, 3], [0, 2, 1], "col_ptr must be non-decreasing"),
+    ([0, 2, 3], [0, 3, 1], "row index out of range"),
+])
+def test_malformed_csc_refusals_are_exact(p, i, msg):
+    """Refused before any device work (so with or without a GPU): status -1, this message, nothing written."""
+    from rcppml_amd import _abi
+    x = np.array([1.0, 2.0, 3.0])
+    part, v, center = np.full(2, 7, np.int32), np.full(3, 7.0), np.full(6, 7.0)
+    r = _abi.bipartition_double(p, i, x, 3, 2, seed=1, partition=part, v=v, center=center)
+    assert (r["status"], r["error"]) == (-1, msg)
+    assert np.all(part == 7) and np.all(v == 7.0) and np.all(center == 7.0)
+    asg = np.full(2, 7, np.int32)
+    r = _abi.dclust_double(p, i, x, 3, 2, min_samples=1, assignments=asg)
+    assert (r["status"], r["error"]) == (-1, msg) and np.all(asg == 7)
+    r = _abi.bipartition_ex(p, i, x, 3, 2)
+    assert (r["status"], r["error"]) == (-1, msg) and r["needed"] == [2, 2, 6]
+    r = _abi.dclust_ex(p, i, x, 3, 2, min_samples=1)
+    assert (r["status"], r["error"]) == (-1, msg) and (r["clusters"], r["nodes"]) == (2, 4)
+
+
 def test_surface_validation():
     from rcppml_amd import cluster
     A = known_10x10()

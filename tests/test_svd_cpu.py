@@ -129,6 +129,26 @@ def test_abi_refusals_leave_buffers_untouched(kw):
     assert r["status"] == -1 and r["error"]
 
 
+# a 3 x 2 matrix (p = [0, 2, 3], i = [0, 2, 1]) with one defect each; nnz is the length of x
+@pytest.mark.parametrize("p, i, k, msg", [
+    ([1, 2, 3], [0, 2, 1], 1, "col_ptr must start at 0 and end at nnz"),
+    ([0, 4, 3], [0, 2, 1], 1, "col_ptr must be non-decreasing"),
+    ([0, 2, 3], [0, 3, 1], 1, "row index out of range"),
+    ([0, 2, 3], [0, 2, 1], 0, "k_max must be in [1, min(m, n)]"),
+])
+@pytest.mark.parametrize("precision", ["double", "float"])
+def test_malformed_input_refusals_are_exact(p, i, k, msg, precision):
+    """Refused before any device work (so with or without a GPU): status -1, this message, nothing written."""
+    from rcppml_amd import _abi
+    x = np.array([1.0, 2.0, 3.0])
+    bufs = dict(U=np.full(3, 7.0), d=np.full(1, 7.0), V=np.full(2, 7.0), row_means=np.full(3, 7.0), iters=np.full(1, 7, np.int32),
+                test_loss=np.full(1, 7.0))
+    r = _abi.svd_pca((p, i, x, 3, 2), k, precision=precision, center=True, buffers=bufs)
+    assert (r["status"], r["error"]) == (-1, msg)
+    assert all(np.all(b == 7) for b in bufs.values())
+    assert (r["k"], r["frob"], r["wall_ms"]) == (0, 0.0, 0.0)
+
+
 def test_abi_refuses_obs_mask_and_graph():
     from rcppml_amd import _abi
     A, _ = known_30x20()
