@@ -549,13 +549,14 @@ enum { RCPPML_CD_AUTO = 0 /* = GROUP unless RCPPML_GPU_CD_VARIANT says otherwise
 RCPPML_GPU_API int rcppml_hip_ctx_create(rcppml_hip_ctx** out, int device, void* stream);
 RCPPML_GPU_API void rcppml_hip_ctx_destroy(rcppml_hip_ctx* ctx);
 RCPPML_GPU_API int rcppml_hip_ctx_sync(rcppml_hip_ctx* ctx);
-/* Work counters since creation / the last reset (synchronises the stream): out4[0] = column-sweeps executed by the
- * coordinate-descent kernels (sum over solved columns of the sweeps cd_nnls_col_fixed ran, nnls_batch.hpp:127-131;
- * x 2 k_pad^2 = the flops of the residual updates), out4[1] = columns solved, out4[2] = slot-sweeps the persistent LMF
+/* Work counters since creation / the last reset (synchronises the stream): out4[0] = column-sweeps of the
+ * coordinate-descent kernels (sum over solved columns of the sweeps cd_nnls_col_fixed ran, nnls_batch.hpp:127-131, i.e. the
+ * sum of sweeps_out: at tol = 0 the static-sweep kernel counts maxit for a column it left at its fixed point, so there these
+ * are sweeps reported, not executed; x 2 k_pad^2 = the flops of the residual updates), out4[1] = columns solved, out4[2] = slot-sweeps the persistent LMF
  * kernel executed (column slots x sweeps of their wave: idle slots and warm-start correction sweeps included, so
  * 1 - out4[0] / out4[2] is its idle fraction), out4[3] = coordinate steps of that kernel in which NO column of the wave
- * moved (only with RCPPML_OPT_CD_COUNT_NOOP; a step is one coordinate of one wave-sweep).  Counted by the GROUP, MFMA and
- * LMF kernels (what RCPPML_CD_AUTO dispatches to). */
+ * moved (only with RCPPML_OPT_CD_COUNT_NOOP; a step is one coordinate of one wave-sweep).  out4[0] and out4[1] are counted by
+ * every kernel rcppml_hip_solve_cd dispatches to (LANE, WAVE and the general-rank kernel included), out4[2..3] by LMF. */
 RCPPML_GPU_API int rcppml_hip_ctx_stats(rcppml_hip_ctx* ctx, int reset, unsigned long long* out4);
 /* IRLS work counters (only while RCPPML_OPT_CD_COUNT_NOOP is set; two atomics per column): out2[0] = IRLS passes summed over
  * the columns rcppml_hip_solve_irls solved (nnls_batch_irls.hpp:480-560: each pass rebuilds the weighted Gram and solves),
@@ -655,7 +656,9 @@ RCPPML_GPU_API int rcppml_hip_rhs_planned(rcppml_hip_ctx* ctx, const rcppml_rhs_
  *   CD(G, b, x, l1_cd, l2_cd, nonneg, maxit, ub_cd, tol); if (ub_post>0) x = min(x, ub_post).
  * B is NOT modified (the residual lives in registers).  G: k x k.
  * sweeps_out (device, ncols ints, may be NULL): sweeps executed per column = the value cd_nnls_col_fixed
- * returns (nnls_batch.hpp:127-131).
+ * returns (nnls_batch.hpp:127-131).  With tol = 0 that is maxit on every column, also where the static-sweep kernel
+ * RCPPML_CD_AUTO takes for small sides (k <= 64, plain non-negative steps, ncols <= 6 x CUs) leaves early because a sweep
+ * moved no coordinate: the sweeps it skips are no-ops, and it reports maxit as the reference does.
  * col_order (device, ncols ints, may be NULL): work order -- slot s of the launch solves column col_order[s]
  * (see rcppml_hip_order_columns).  Columns are independent: any permutation gives identical results. */
 RCPPML_GPU_API int rcppml_hip_solve_cd(rcppml_hip_ctx* ctx, int dtype, const void* G, const void* B,

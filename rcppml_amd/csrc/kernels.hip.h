@@ -149,7 +149,7 @@ __device__ __forceinline__ int cd_static_sweeps_tol(T& b, T& x, T gd, bool fok, 
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) term += __shfl_xor(term, off, 64);
             if (term * inv_k < tol) return it + 1;
-        } else if (!__any(moved)) return it + 1;
+        } else if (!__any(moved)) return maxit;      // fixed point: every later sweep is a no-op; the reference runs them and returns maxit
     }
     return maxit;
 }
@@ -794,6 +794,18 @@ template <class T> __device__ __forceinline__ T fast_div(T a, T b);
 template <> __device__ __forceinline__ float fast_div<float>(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 template <> __device__ __forceinline__ double fast_div<double>(double a, double b) { return a / b; }
 
+// one atomic pair per wavefront: sum of the per-lane sweep counts (0 on lanes that own no column) -> ctx counters
+__device__ __forceinline__ void cd_stats_add(unsigned long long* stats, int nsw, int ncol) {
+    if (!stats) return;
+    int v = nsw, c = ncol;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { v += __shfl_xor(v, off, 64); c += __shfl_xor(c, off, 64); }
+    if ((threadIdx.x & 63) == 0 && c > 0) {
+        atomicAdd(stats, (unsigned long long)v);
+        atomicAdd(stats + 1, (unsigned long long)c);
+    }
+}
+
 template <class T, int KP, bool EXACT>
 __global__ __launch_bounds__(64) void cd_lane_kernel(const T* __restrict__ Gp,
                                                       const T* __restrict__ invd,
@@ -801,7 +813,8 @@ __global__ __launch_bounds__(64) void cd_lane_kernel(const T* __restrict__ Gp,
                                                       int k, int64_t ncols, T l1_pre, int warm,
                                                       int zero_init, T l1_cd, T l2_cd, int nonneg,
                                                       int maxit, T tol, T ub_cd, T ub_post,
-                                                      int* __restrict__ sweeps, const int* __restrict__ order) {
+                                                      int* __restrict__ sweeps, const int* __restrict__ order,
+                                                      unsigned long long* __restrict__ stats) {
     const int64_t slot_j = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool inb = slot_j < ncols;
     const int64_t j = (inb && order) ? order[slot_j] : slot_j;
@@ -871,6 +884,7 @@ __global__ __launch_bounds__(64) void cd_lane_kernel(const T* __restrict__ Gp,
             }
         if (sweeps) sweeps[j] = nsweep;   // what cd_nnls_col_fixed returns (nnls_batch.hpp:127-131)
     }
+    cd_stats_add(stats, inb ? nsweep : 0, inb ? 1 : 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -964,18 +978,6 @@ struct CdGroupStep {
     }
 };
 
-
-// one atomic pair per wavefront: sum of the per-lane sweep counts (0 on lanes that own no column) -> ctx counters
-__device__ __forceinline__ void cd_stats_add(unsigned long long* stats, int nsw, int ncol) {
-    if (!stats) return;
-    int v = nsw, c = ncol;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { v += __shfl_xor(v, off, 64); c += __shfl_xor(c, off, 64); }
-    if ((threadIdx.x & 63) == 0 && c > 0) {
-        atomicAdd(stats, (unsigned long long)v);
-        atomicAdd(stats + 1, (unsigned long long)c);
-    }
-}
 
 // ---------------------------------------------------------------------------
 // CD NNLS for SMALL sides (fewer columns than ~1.5 waves per SIMD: C3's 610 columns, hawaiibirds): one wavefront per column,
@@ -1130,7 +1132,8 @@ __global__ __launch_bounds__(256) void cd_wave_kernel(const T* __restrict__ Gp,
                                                        int k, int64_t ncols, T l1_pre, int warm,
                                                        int zero_init, T l1_cd, T l2_cd, int nonneg,
                                                        int maxit, T tol, T ub_cd, T ub_post,
-                                                      int* __restrict__ sweeps, const int* __restrict__ order) {
+                                                      int* __restrict__ sweeps, const int* __restrict__ order,
+                                                      unsigned long long* __restrict__ stats) {
     constexpr int VPL = KP / 64;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const T* Gs = Gp;
@@ -1149,6 +1152,7 @@ __global__ __launch_bounds__(256) void cd_wave_kernel(const T* __restrict__ Gp,
 #pragma unroll
     for (int v = 0; v < VPL; ++v) { ginv[v] = invd[lane + 64 * v]; gdiag[v] = Gs[(lane + 64 * v) * KP + lane + 64 * v]; }
 
+    int wave_sweeps = 0, wave_cols = 0;          // this wave's share of the context's work counters
     for (int64_t sj = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); sj < ncols; sj += nwaves) {
         const int64_t j = order ? order[sj] : sj;
         T b[VPL], x[VPL];
@@ -1217,7 +1221,9 @@ __global__ __launch_bounds__(256) void cd_wave_kernel(const T* __restrict__ Gp,
             }
         }
         if (sweeps && lane == 0) sweeps[j] = nsweep;
+        wave_sweeps += nsweep; wave_cols += 1;
     }
+    cd_stats_add(stats, lane == 0 ? wave_sweeps : 0, lane == 0 ? wave_cols : 0);
 }
 
 // ---------------------------------------------------------------------------

@@ -14,7 +14,7 @@ static void cd_lane_launch(rcppml_hip_ctx* c, const T* Gp, const T* invd, const 
     constexpr bool EXACT = std::is_same<T, double>::value;
     const int64_t nblk = (ncols + 63) / 64;
     hipLaunchKernelGGL((cd_lane_kernel<T, KP, EXACT>), dim3((unsigned)nblk), dim3(64), 0, c->stream, Gp, invd,
-                       B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order);
+                       B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats);
     HIPCHK(hipGetLastError());
 }
 template <class T, int KP, bool GLDS = true>
@@ -35,7 +35,7 @@ static void cd_wave_launch(rcppml_hip_ctx* c, const T* Gp, const T* invd, const 
     if (nblk > need) nblk = need;
     if (nblk < 1) nblk = 1;
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), smem, c->stream, Gp, invd, B, X, k, ncols, l1_pre,
-                       warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order);
+                       warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats);
     HIPCHK(hipGetLastError());
 }
 

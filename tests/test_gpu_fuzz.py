@@ -54,8 +54,10 @@ def test_fuzz_rhs_gram_scaling(env, dtype):
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_fuzz_cd_auto(env, dtype):
-    """The AUTO solve (MFMA kernels for k <= 128, the general-rank wave-per-column kernel up to 256) on odd ranks and
-    column counts, cold and warm, with and without the early exit."""
+    """The AUTO solve on odd ranks and column counts, cold and warm, with and without the early exit.  With at most 130 columns
+    AUTO takes cd_wave_static_kernel for k <= 64 (small side: ncols <= 6 x CUs), the 32-column fp32 / 16-column fp64 MFMA kernels
+    for 64 < k <= 128, and the general-rank wave-per-column kernel up to 256; the MFMA kernels at k <= 64 and the AUTO thresholds
+    are covered by tests/test_gpu_cd_matrix.py."""
     torch, _abi, ctx = env
     dt = _abi.F32 if dtype == np.float32 else _abi.F64
     tol = 3e-4 if dtype == np.float32 else 1e-9
