@@ -98,8 +98,8 @@ template <class T> struct WideCol {
     }
     // cd_nnls_col_fixed on the tile: sequential sweeps with ballot skipping of coordinates that do not move.  l1_in: subtracted
     // from every quotient (the CV / IRLS callers); tol > 0: the masked solver's relative-change stop; otherwise a sweep without
-    // any effective step ends the solve (all later sweeps are no-ops too)
-    __device__ void cd(T (&b)[2], T (&x)[2], T l1_in, int nonneg, int maxit, T tol) {
+    // any effective step ends the solve (all later sweeps are no-ops too).  Returns the sweeps executed (the IRLS work counter).
+    __device__ int cd(T (&b)[2], T (&x)[2], T l1_in, int nonneg, int maxit, T tol) {
         T gd[2], ginv[2];
 #pragma unroll
         for (int s = 0; s < 2; ++s) { gd[s] = Gl[(lane + 64 * s) * WKP + lane + 64 * s]; ginv[s] = gd[s] > T(0) ? T(1) / gd[s] : T(0); }
@@ -140,11 +140,13 @@ template <class T> struct WideCol {
                 const T x0n = x[0] + aown[0], x1n = x[1] + aown[1];
                 const bool moved = x0n != x[0] || x1n != x[1];
                 x[0] = x0n; x[1] = x1n;
-                if (!__any(moved)) break;   // no step, or the iterate is at its floating-point fixed point
+                if (!__any(moved)) return it + 1;   // no step, or the iterate is at its floating-point fixed point
             }
-            return;
+            return maxit > 0 ? maxit : 0;
         }
+        int nsw = 0;
         for (int it = 0; it < maxit; ++it) {
+            ++nsw;
             T tol_sum = T(0);
             bool any = false;
             const T xs0 = x[0], xs1 = x[1];
@@ -176,6 +178,7 @@ template <class T> struct WideCol {
             if (check) { if (tol_sum * inv_k < tol) break; }
             else if (!any || !__any(x[0] != xs0 || x[1] != xs1)) break;   // no step, or the iterate is at its floating-point fixed point
         }
+        return nsw;
     }
     // in-LDS Cholesky (left-looking) of the leading k x k block, forward / back substitution, clip: x = max(G^-1 b, 0)
     __device__ void chol(const T (&b)[2], T (&x)[2], int nonneg) {
@@ -257,7 +260,7 @@ __global__ __launch_bounds__(64) void wide_irls_solve_kernel(
     const int as = colptr[j], ae = colptr[j + 1];
     const T th_col = theta_col ? theta_col[j] : T(0);
     T x[2] = {T(0), T(0)};
-    int passes = 0;
+    int passes = 0, nsw = 0;      // IRLS passes; CD sweeps executed over all passes (work counters)
     for (int irls = 0; irls < irls_max_iter; ++irls) {
         ++passes;
         wc.set_base(Gbase, T(0));
@@ -292,12 +295,12 @@ __global__ __launch_bounds__(64) void wide_irls_solve_kernel(
             b[0] = tfma(-wc.Gl[c * WKP + wc.lane], xc, b[0]);
             b[1] = tfma(-wc.Gl[c * WKP + wc.lane + 64], xc, b[1]);
         }
-        wc.cd(b, x, l1, nonneg, cd_maxit, T(0));
+        nsw += wc.cd(b, x, l1, nonneg, cd_maxit, T(0));
         RK_WAVE_SYNC();
         if (wc.rel_change(x, xo) < irls_tol) break;
     }
     wc.store_x(X, j, x);
-    if (stats && wc.lane == 0) { atomicAdd(stats, (unsigned long long)passes); atomicAdd(stats + 1, (unsigned long long)passes * (unsigned long long)(ae - as)); }
+    if (stats && wc.lane == 0) { atomicAdd(stats, (unsigned long long)passes); atomicAdd(stats + 1, (unsigned long long)passes * (unsigned long long)(ae - as)); atomicAdd(stats + 4, (unsigned long long)nsw); }
 }
 
 // ---------------------------------------------------------------------------
