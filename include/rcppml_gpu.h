@@ -337,6 +337,47 @@ RCPPML_GPU_API void rcppml_gpu_svd_pca_dense_float(const double* A_data, int* m,
         int* out_iters_per_factor, double* out_frobenius_norm_sq, double* out_row_means, double* robust_delta, int* irls_max_iter,
         double* irls_tol, int* out_status);
 
+/* Cross-validated / auto-rank and obs-masked deflation SVD (rcppml_amd/csrc/ops_svd.hip, kernels_svd_cv.hip.h).  BUILD-DEFINED: the
+ * reference has no such symbols; it runs this inside its deflation loop (svd/deflation.hpp:431-565, :713-781, :869-896), which the four
+ * entries above still refuse.  The reference's CPU path is what is restated, not its GPU variant (svd/deflation_gpu.cuh:857-1345, whose
+ * hold-out rule differs):
+ *   mask      entry (i, j) is held out when SplitMix64::hash(seed, i, j) < UINT64_MAX / inv_prob (rng/rng.hpp:129-170), inv_prob =
+ *             (uint64)(1.0 / *test_fraction) (nmf/speckled_cv.hpp:121, taken from the double in both precisions), seed = *cv_seed != 0 ?
+ *             *cv_seed : (*seed != 0 ? *seed ^ 0xBEEF : 42) (core/svd_config.hpp:149-151)
+ *   test set  sparse: the held-out stored entries, with either *mask_zeros (svd/test_entries.hpp:84-108); dense: every held-out
+ *             (i, j) (:131-141); taken from the original A, minus the row mean when *center, in column-major order
+ *   training  the pattern of A with held-out values and the values at obs_mask positions set to 0 (:264-315, deflation.hpp:452-487);
+ *             both products read it; row means and out_frobenius_norm_sq come from the full A (deflation.hpp:377-417)
+ *   updates   |u_hat|^2 and |v|^2 are scaled by 1 - *test_fraction * nnz / (m n) with *mask_zeros, else by 1 - *test_fraction (dense:
+ *             1 - *test_fraction either way), where they divide the update and where the element constraints take them
+ *             (deflation.hpp:552-559, :724-739, :769-784); not in the warm start or the Rayleigh quotient
+ *   rank      after each stored factor r_e -= sigma u[row_e] v[col_e] and test_mse = sum r_e^2 / n_test (0 without test entries) goes to
+ *             out_test_loss; a value strictly below the best so far resets the counter, anything else counts, and the loop ends when the
+ *             counter reaches *patience -- with a fixed k_max too -- before the sigma < 100 eps stop (deflation.hpp:869-911)
+ * *test_fraction = 0: no hold-out, out_test_loss untouched, *out_k_selected = *out_k_computed; without an obs_mask this is
+ * rcppml_gpu_svd_pca_* with *algorithm 0, bit for bit.  obs_mask_p = NULL: no mask (the other obs_mask pointers are then not read); else a
+ * pattern CSC with the dimensions of A and strictly increasing rows within a column.
+ * Outputs: U (m x *k_max) and V (n x *k_max) column-major and d with the first *out_k_selected columns / values written; *out_k_computed
+ * factors were computed, out_test_loss and out_iters_per_factor (each *k_max long) hold that many values; *out_n_test test entries;
+ * *out_n_masked stored entries (dense: positions) the obs_mask zeroed; out_row_means (m) when *center.
+ * Refused with *out_status = -1 (rcppml_gpu_last_error), nothing written: a null pointer, *precision not RCPPML_F32 / RCPPML_F64, *k_max
+ * outside [1, min(m, n)] or above 4094, *max_iter < 1, *patience < 1, *test_fraction outside [0, 1), negative *tol, a malformed matrix
+ * or mask CSC, mask dimensions that differ from A's, more device memory than is free, no device. */
+RCPPML_GPU_API void rcppml_gpu_svd_cv_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+        int* precision, int* k_max, double* tol, int* max_iter, int* center, int* seed, double* L1_u, double* L1_v, double* L2_u,
+        double* L2_v, int* nonneg_u, int* nonneg_v, double* ub_u, double* ub_v, double* test_fraction, int* cv_seed, int* patience,
+        int* mask_zeros, const int* obs_mask_p, const int* obs_mask_i, int* obs_mask_rows, int* obs_mask_cols, int* obs_mask_nnz,
+        double* U, double* d, double* V, int* out_k_selected, int* out_k_computed, double* out_test_loss, int* out_n_test,
+        int* out_n_masked, int* out_iters_per_factor, double* out_frobenius_norm_sq, double* out_row_means,
+        double* out_wall_time_ms, int* out_status);
+RCPPML_GPU_API void rcppml_gpu_svd_cv_dense_ex(const double* A_data, int* m, int* n,
+        int* precision, int* k_max, double* tol, int* max_iter, int* center, int* seed, double* L1_u, double* L1_v, double* L2_u,
+        double* L2_v, int* nonneg_u, int* nonneg_v, double* ub_u, double* ub_v, double* test_fraction, int* cv_seed, int* patience,
+        int* mask_zeros, const int* obs_mask_p, const int* obs_mask_i, int* obs_mask_rows, int* obs_mask_cols, int* obs_mask_nnz,
+        double* U, double* d, double* V, int* out_k_selected, int* out_k_computed, double* out_test_loss, int* out_n_test,
+        int* out_n_masked, int* out_iters_per_factor, double* out_frobenius_norm_sq, double* out_row_means,
+        double* out_wall_time_ms, int* out_status);
+
 /* Embedding assessment (rcppml_amd/csrc/ops_assess.hip): the reference plugin's rcppml_gpu_assess (src/gpu_bridge_assess.cu:358-753)
  * with its 26 pointers, called by R's assess() (R/assess.R:708-769).  embedding: n x dim row-major doubles, cast to fp32.  Seeds are
  * (unsigned)*seed plus an offset (restart r: + r; silhouette: + 100; folds: + 200), each driving std::mt19937 + std::shuffle.

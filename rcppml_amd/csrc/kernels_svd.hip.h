@@ -134,17 +134,20 @@ __global__ __launch_bounds__(WG) void dots_kernel(const T* __restrict__ x, long 
 enum { M_LOOP = 0, M_WARM = 1, M_PLAIN = 2 };
 
 // v-update epilogue (n): h = finalised m-side partials [U_k' u_hat (k), mu . u_hat, |u_hat|^2];
-//   s = y - center * (mu . u_hat) - V_k diag(d) (U_k' u_hat);  LOOP: v = regularize(s / |u_hat|^2);  WARM: v = s.
+//   s = y - center * (mu . u_hat) - V_k diag(d) (U_k' u_hat);  LOOP: v = regularize(s / (dc |u_hat|^2));  WARM: v = s.
+// dc: the cross-validation denominator correction (deflation.hpp:552-559, :724-739), 1 without CV; it scales |u_hat|^2 where it
+// divides the update and where regularize() takes it, and nowhere else.
 // Writes vraw and the n-side partials [V_k' v (k), sum v, |v|^2].
 template <class T>
 __global__ __launch_bounds__(WG) void defl_v_kernel(const T* __restrict__ y, int n, const T* __restrict__ V, int k,
                                                     const T* __restrict__ d, const T* __restrict__ Pm, int nbm, int center, T l1, T l2,
-                                                    int nonneg, T ub, int mode, T* __restrict__ vraw, T* __restrict__ Pn, int* st, int it) {
+                                                    int nonneg, T ub, T dc, int mode, T* __restrict__ vraw, T* __restrict__ Pn, int* st,
+                                                    int it) {
     if (idle(st, it)) return;
     __shared__ T h[NPMAX];
     __shared__ T xs[CH];
     finalize(Pm, nbm, k + 2, h);
-    const T c = center ? h[k] : T(0), usq = h[k + 1];
+    const T c = center ? h[k] : T(0), usq = h[k + 1] * dc;
     const bool brk = mode == M_LOOP && !(usq > T(0));
     if (brk && blockIdx.x == 0 && threadIdx.x == 0) st[S_BRKV] = 1;
     const long r0 = (long)blockIdx.x * CH;
@@ -166,11 +169,11 @@ __global__ __launch_bounds__(WG) void defl_v_kernel(const T* __restrict__ y, int
 // u-update epilogue (m): hv = finalised n-side partials [V_k' vraw, sum vraw, |vraw|^2], sv = |vraw|.
 //   LOOP / WARM: v = vraw / sv (grid-stride over n); t = t / sv - center * mu * sum / sv - U_k diag(d) (V_k' vraw) / sv
 //   PLAIN (Rayleigh quotient): t - center * mu * sum - U_k diag(d) (V_k' v), nothing normalised.
-//   LOOP: u_raw = regularize(t / |v|^2).  Writes u_raw and the partials [|u_raw|^2, u_raw . u_cur].
+//   LOOP: u_raw = regularize(t / (dc |v|^2)), dc as in defl_v_kernel.  Writes u_raw and the partials [|u_raw|^2, u_raw . u_cur].
 template <class T>
 __global__ __launch_bounds__(WG) void defl_u_kernel(const T* __restrict__ t, int m, const T* __restrict__ U, int k,
                                                     const T* __restrict__ d, const T* __restrict__ Pn, int nbn, const T* __restrict__ mu,
-                                                    T l1, T l2, int nonneg, T ub, int mode, const T* __restrict__ vraw,
+                                                    T l1, T l2, int nonneg, T ub, T dc, int mode, const T* __restrict__ vraw,
                                                     T* __restrict__ v, int n, T* __restrict__ uraw, const T* __restrict__ ucur,
                                                     T* __restrict__ Pu, int* st, int it) {
     if (idle(st, it)) return;
@@ -196,7 +199,7 @@ __global__ __launch_bounds__(WG) void defl_u_kernel(const T* __restrict__ t, int
         }
         for (long j = (long)blockIdx.x * WG + threadIdx.x; j < n; j += (long)gridDim.x * WG) v[j] = vraw[j] * inv;
     }
-    const T vsq = h[k + 1] * inv * inv;
+    const T vsq = h[k + 1] * inv * inv * dc;
     const T sm = mu ? h[k] * inv : T(0);
     const long r0 = (long)blockIdx.x * CH;
     const int cnt = (int)min((long)CH, (long)m - r0);

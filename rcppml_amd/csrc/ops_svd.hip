@@ -11,9 +11,16 @@
 //   small bidiagonal problem is solved on the host in fp64.
 // Anything else is refused (status -1, reason in rcppml_gpu_last_error, no output written).
 //
+// Cross-validation / auto-rank and obs_mask (deflation.hpp:431-565, :713-781, :869-896; kernels: kernels_svd_cv.hip.h) run through
+// the build-defined entries rcppml_gpu_svd_cv_ex / rcppml_gpu_svd_cv_dense_ex at the end of this file, deflation only: the engine
+// factors a training copy of A (held-out and masked values zeroed, same pattern), scales the two update denominators by the
+// reference's correction, and after each stored factor updates the held-out residuals in one launch and applies the patience
+// rule on the host, at the synchronisation the factor's sigma already needs.  The four reference entries keep refusing both.
+//
 // Centering never densifies: A'u - (mu . u) 1 and A v - mu sum(v) are scalar corrections inside the epilogues.
 #include "entry_common.hip.h"
 #include "kernels_svd.hip.h"
+#include "kernels_svd_cv.hip.h"
 
 #include <chrono>
 #include <climits>
@@ -35,6 +42,11 @@ struct Opts {
     const double* dense = nullptr;                                              // or column-major dense
     double tol; int max_iter; int center; unsigned seed; int algorithm;
     double L1_u, L1_v, L2_u, L2_v, ub_u, ub_v; int nonneg_u, nonneg_v;
+    // the cv entries only: hold-out fraction (0: no CV), effective mask seed, patience, mask_zeros, obs-mask pattern CSC (or null)
+    double test_fraction = 0; uint64_t cv_seed = 0; int patience = 0; int mask_zeros = 0;
+    const int* mp = nullptr; const int* mi = nullptr; int64_t mnnz = 0;
+    bool cv() const { return test_fraction > 0; }
+    bool trains() const { return cv() || mp; }      // the products read a training copy of A
 };
 
 struct Result {
@@ -42,6 +54,9 @@ struct Result {
     std::vector<int> iters;
     int k_sel = 0;
     double frob = 0;
+    std::vector<double> test_loss;          // one value per computed factor (CV only)
+    int k_computed = 0, n_test = 0;
+    int64_t n_masked = 0;
 };
 
 bool has_constraints(const Opts& o) {
@@ -134,6 +149,9 @@ template <class T> struct Engine {
     hipStream_t s;
     int m, n;
     DevBuf Ap, Ai, Ax, Tp, Ti, Tx, Ad, mu;
+    DevBuf Xt, Mp, Mi, te_rows, te_cols, te_res, te_P;      // training values (CSC order or dense), obs-mask, test entries
+    long n_test = 0;
+    int64_t n_masked = 0;
     std::vector<double> mu_h;
 
     Engine(const Opts& o_) : o(o_), g(env_device()), s(g.s), m(o_.m), n(o_.n) {
@@ -147,10 +165,6 @@ template <class T> struct Engine {
             upload_ints(o.p, (size_t)n + 1, Ap, s);
             upload_ints(o.i, nz, Ai, s);
             upload_cast<T>(g.c, o.x, nz, Ax, s);
-            grow<int>(Tp, (size_t)m + 1);
-            grow<int>(Ti, nz);
-            grow<T>(Tx, nz);
-            OPCHK(rcppml_hip_transpose_csc(g.c, DT<T>::id, m, n, Ap.as<int>(), Ai.as<int>(), Ax.p, Tp.as<int>(), Ti.as<int>(), Tx.p));
             for (int64_t e = 0; e < o.nnz; ++e) mu_h[o.i[e]] += o.x[e];
         }
         for (auto& v : mu_h) v /= (double)n;
@@ -158,19 +172,72 @@ template <class T> struct Engine {
             std::vector<double> tmp(mu_h);
             upload_cast<T>(g.c, tmp.data(), (size_t)m, mu, s);
         }
+        if (o.trains()) hold_out();
+        if (!o.dense) {
+            const size_t nz = (size_t)std::max<int64_t>(o.nnz, 1);
+            grow<int>(Tp, (size_t)m + 1);
+            grow<int>(Ti, nz);
+            grow<T>(Tx, nz);
+            OPCHK(rcppml_hip_transpose_csc(g.c, DT<T>::id, m, n, Ap.as<int>(), Ai.as<int>(), (const void*)xa(), Tp.as<int>(), Ti.as<int>(),
+                                           Tx.p));
+        }
     }
     const T* mup() const { return o.center ? mu.as<T>() : nullptr; }
+    // the values the products read: the training copy when there is one
+    const T* xa() const { return o.trains() ? Xt.as<T>() : (o.dense ? Ad.as<T>() : Ax.as<T>()); }
+    // The test entries from the original A (row means subtracted when centred) and the training values, deflation.hpp:452-545.
+    void hold_out() {
+        const uint64_t thr = o.cv() ? UINT64_MAX / (uint64_t)(1.0 / o.test_fraction) : 0;
+        const int* p = o.dense ? nullptr : Ap.as<int>();
+        const int* ri = o.dense ? nullptr : Ai.as<int>();
+        const T* x = o.dense ? Ad.as<T>() : Ax.as<T>();
+        const size_t len = o.dense ? (size_t)m * n : (size_t)std::max<int64_t>(o.nnz, 1);
+        DevBuf cnt, off;
+        int* dcnt = grow<int>(cnt, (size_t)n);
+        if (o.cv()) {
+            hipLaunchKernelGGL(test_entries<T>, dim3(wblk(n)), dim3(WG), 0, s, p, ri, x, m, n, (unsigned long long)o.cv_seed,
+                               (unsigned long long)thr, mup(), (const int*)nullptr, dcnt, (int*)nullptr, (int*)nullptr, (T*)nullptr);
+            HIPCHK(hipGetLastError());
+            const std::vector<int> ch = read<int>(dcnt, (size_t)n);
+            std::vector<int> oh((size_t)n + 1, 0);
+            int64_t tot = 0;
+            for (int j = 0; j < n; ++j) { oh[j] = (int)tot; tot += ch[j]; if (tot >= INT_MAX) throw std::invalid_argument("too many test entries"); }
+            oh[n] = (int)tot;
+            n_test = (long)tot;
+            upload_ints(oh.data(), (size_t)n + 1, off, s);
+            grow<int>(te_rows, (size_t)std::max<long>(n_test, 1));
+            grow<int>(te_cols, (size_t)std::max<long>(n_test, 1));
+            grow<T>(te_res, (size_t)std::max<long>(n_test, 1));
+            grow<T>(te_P, (size_t)std::max(nblk(n_test), 1));
+            if (n_test > 0)
+                hipLaunchKernelGGL(test_entries<T>, dim3(wblk(n)), dim3(WG), 0, s, p, ri, x, m, n, (unsigned long long)o.cv_seed,
+                                   (unsigned long long)thr, mup(), (const int*)off.as<int>(), (int*)nullptr, te_rows.as<int>(),
+                                   te_cols.as<int>(), te_res.as<T>());
+        }
+        if (o.mp) {
+            upload_ints(o.mp, (size_t)n + 1, Mp, s);
+            upload_ints(o.mi, (size_t)std::max<int64_t>(o.mnnz, 1), Mi, s);
+        }
+        grow<T>(Xt, len);
+        hipLaunchKernelGGL(train_values<T>, dim3(wblk(n)), dim3(WG), 0, s, p, ri, x, m, n, (unsigned long long)o.cv_seed,
+                           (unsigned long long)thr, o.mp ? (const int*)Mp.as<int>() : nullptr, o.mp ? (const int*)Mi.as<int>() : nullptr,
+                           Xt.as<T>(), dcnt);
+        HIPCHK(hipGetLastError());
+        const std::vector<int> mh = read<int>(dcnt, (size_t)n);      // also orders the off / cnt buffers' release after the kernels
+        n_masked = 0;
+        for (int c : mh) n_masked += c;
+    }
     // y = A' x (n);  brk: a state word that skips the launch when set (0: none)
     void at(const T* x, T* y, const int* st, int it, int brk) {
         if (o.dense)
-            hipLaunchKernelGGL(spmv_t_dense<T>, dim3(wblk(n)), dim3(WG), 0, s, Ad.as<T>(), m, n, x, y, st, it, brk);
+            hipLaunchKernelGGL(spmv_t_dense<T>, dim3(wblk(n)), dim3(WG), 0, s, xa(), m, n, x, y, st, it, brk);
         else
-            hipLaunchKernelGGL(spmv_t_csc<T>, dim3(wblk(n)), dim3(WG), 0, s, Ap.as<int>(), Ai.as<int>(), Ax.as<T>(), n, x, y, st, it, brk);
+            hipLaunchKernelGGL(spmv_t_csc<T>, dim3(wblk(n)), dim3(WG), 0, s, Ap.as<int>(), Ai.as<int>(), xa(), n, x, y, st, it, brk);
     }
     // y = A x (m)
     void ax(const T* x, T* y, const int* st, int it, int brk) {
         if (o.dense)
-            hipLaunchKernelGGL(spmv_dense<T>, dim3((m + WG - 1) / WG), dim3(WG), 0, s, Ad.as<T>(), m, n, x, y, st, it, brk);
+            hipLaunchKernelGGL(spmv_dense<T>, dim3((m + WG - 1) / WG), dim3(WG), 0, s, xa(), m, n, x, y, st, it, brk);
         else
             hipLaunchKernelGGL(spmv_csr<T>, dim3(wblk(m)), dim3(WG), 0, s, Tp.as<int>(), Ti.as<int>(), Tx.as<T>(), m, x, y, st, it, brk);
     }
@@ -189,6 +256,12 @@ template <class T> struct Engine {
         const int K = o.k, nbm = nblk(m), nbn = nblk(n);
         const T eps100 = std::numeric_limits<T>::epsilon() * T(100);
         const T l1u = (T)o.L1_u, l1v = (T)o.L1_v, l2u = (T)o.L2_u, l2v = (T)o.L2_v, ubu = (T)o.ub_u, ubv = (T)o.ub_v;
+        // deflation.hpp:552-559: the denominators |u_hat|^2 and |v|^2 count the held-out positions too
+        T dc = T(1);
+        if (o.cv()) dc = T(1) - (T)o.test_fraction * (o.mask_zeros ? (T)o.nnz / ((T)m * (T)n) : T(1));
+        T best = std::numeric_limits<T>::max();
+        int best_k = 0, waited = 0;
+        R.test_loss.clear();
         DevBuf dU, dV, dd, uraw, uhat, vraw, y, t, Pm, Pn, Pu, st, nrm;
         T* U = grow<T>(dU, (size_t)m * K);
         T* V = grow<T>(dV, (size_t)n * K);
@@ -231,11 +304,11 @@ template <class T> struct Engine {
                     dots(u, m, Cm, Pm.as<T>());
                     at(u, y.as<T>(), nullptr, 0, 0);
                     hipLaunchKernelGGL(defl_v_kernel<T>, dim3(nbn), dim3(WG), 0, s, (const T*)y.as<T>(), n, (const T*)V, k, (const T*)d,
-                                       (const T*)Pm.as<T>(), nbm, o.center, T(0), T(0), 0, T(0), (int)M_WARM, vraw.as<T>(),
+                                       (const T*)Pm.as<T>(), nbm, o.center, T(0), T(0), 0, T(0), T(1), (int)M_WARM, vraw.as<T>(),
                                        Pn.as<T>(), (int*)nullptr, 0);
                     ax(vraw.as<T>(), t.as<T>(), nullptr, 0, 0);
                     hipLaunchKernelGGL(defl_u_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)t.as<T>(), m, (const T*)U, k, (const T*)d,
-                                       (const T*)Pn.as<T>(), nbn, mup(), T(0), T(0), 0, T(0), (int)M_WARM, (const T*)vraw.as<T>(), v, n,
+                                       (const T*)Pn.as<T>(), nbn, mup(), T(0), T(0), 0, T(0), T(1), (int)M_WARM, (const T*)vraw.as<T>(), v, n,
                                        u, (const T*)nullptr, Pu.as<T>(), (int*)nullptr, 0);
                     hipLaunchKernelGGL(gs_kernel<T>, dim3(1), dim3(WG), 0, s, u, (long)m, (const T*)U, k, 1, T(0), (T*)nullptr);
                 } else {
@@ -260,11 +333,11 @@ template <class T> struct Engine {
                     const int it = done + q;
                     at(uhat.as<T>(), y.as<T>(), S, it, 0);
                     hipLaunchKernelGGL(defl_v_kernel<T>, dim3(nbn), dim3(WG), 0, s, (const T*)y.as<T>(), n, (const T*)V, k, (const T*)d,
-                                       (const T*)Pm.as<T>(), nbm, o.center, l1v, l2v, o.nonneg_v, ubv, (int)M_LOOP, vraw.as<T>(),
+                                       (const T*)Pm.as<T>(), nbm, o.center, l1v, l2v, o.nonneg_v, ubv, dc, (int)M_LOOP, vraw.as<T>(),
                                        Pn.as<T>(), S, it);
                     ax(vraw.as<T>(), t.as<T>(), S, it, S_BRKV);
                     hipLaunchKernelGGL(defl_u_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)t.as<T>(), m, (const T*)U, k, (const T*)d,
-                                       (const T*)Pn.as<T>(), nbn, mup(), l1u, l2u, o.nonneg_u, ubu, (int)M_LOOP, (const T*)vraw.as<T>(),
+                                       (const T*)Pn.as<T>(), nbn, mup(), l1u, l2u, o.nonneg_u, ubu, dc, (int)M_LOOP, (const T*)vraw.as<T>(),
                                        v, n, uraw.as<T>(), (const T*)u, Pu.as<T>(), S, it);
                     hipLaunchKernelGGL(defl_finish_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)uraw.as<T>(), u, uhat.as<T>(), m,
                                        (const T*)Pu.as<T>(), nbm, (const T*)U, k, mup(), Pm.as<T>(), tol_k, S, it);
@@ -284,7 +357,7 @@ template <class T> struct Engine {
             dots(v, n, Cn, Pn.as<T>());
             ax(v, t.as<T>(), nullptr, 0, 0);
             hipLaunchKernelGGL(defl_u_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)t.as<T>(), m, (const T*)U, k, (const T*)d,
-                               (const T*)Pn.as<T>(), nbn, mup(), T(0), T(0), 0, T(0), (int)M_PLAIN, (const T*)v, (T*)nullptr, n,
+                               (const T*)Pn.as<T>(), nbn, mup(), T(0), T(0), 0, T(0), T(1), (int)M_PLAIN, (const T*)v, (T*)nullptr, n,
                                uraw.as<T>(), (const T*)u, Pu.as<T>(), (int*)nullptr, 0);
             HIPCHK(hipGetLastError());
             const std::vector<T> pu = read<T>(Pu.p, (size_t)nbm * 2);
@@ -294,9 +367,27 @@ template <class T> struct Engine {
             dh[k] = sg;
             HIPCHK(hipMemcpyAsync(d + k, &dh[k], sizeof(T), hipMemcpyHostToDevice, s));
             HIPCHK(hipStreamSynchronize(s));
+            if (o.cv()) {                                       // deflation.hpp:869-896
+                T mse = 0;
+                if (n_test > 0) {
+                    const int nbt = nblk(n_test);
+                    hipLaunchKernelGGL(test_loss<T>, dim3(nbt), dim3(WG), 0, s, (const int*)te_rows.as<int>(), (const int*)te_cols.as<int>(),
+                                       te_res.as<T>(), n_test, (const T*)u, (const T*)v, sg, te_P.as<T>());
+                    HIPCHK(hipGetLastError());
+                    const std::vector<T> pt = read<T>(te_P.p, (size_t)nbt);
+                    for (int b = 0; b < nbt; ++b) mse += pt[b];
+                    mse /= (T)n_test;
+                }
+                R.test_loss.push_back((double)mse);
+                if (mse < best) { best = mse; best_k = k + 1; waited = 0; }
+                else if (++waited >= o.patience) { ++k; break; }
+            } else {
+                best_k = k + 1;
+            }
             if (sg < eps100) { ++k; break; }
         }
-        R.k_sel = std::min(k, K);
+        R.k_computed = std::min(k, K);
+        R.k_sel = best_k;
         R.U.resize((size_t)m * R.k_sel);
         R.V.resize((size_t)n * R.k_sel);
         download_cast<T>(g.c, dU, (size_t)m * R.k_sel, R.U.data(), s);
@@ -437,6 +528,8 @@ template <class T> struct Engine {
             f -= (double)n * q;
         }
         R.frob = f;
+        R.n_test = (int)n_test;
+        R.n_masked = n_masked;          // masked stored entries; every mask entry on a dense input (deflation.hpp:452-487)
         if (o.algorithm == 0) deflation(R);
         else lanczos(R);
     }
@@ -555,4 +648,120 @@ extern "C" void rcppml_gpu_svd_pca_dense_double(const double* A_data, int* m, in
 extern "C" void rcppml_gpu_svd_pca_dense_float(const double* A_data, int* m, int* n, RCPPML_SVD_PARAMS) {
     (void)out_test_loss; (void)irls_max_iter; (void)irls_tol;
     svd_dense<float>(A_data, m, n, RCPPML_SVD_RAW, out_status);
+}
+
+// ------------------------------------------------------------------------------------------------------------ cv entries
+// Build-defined: cross-validated / auto-rank and obs-masked deflation (the four entries above refuse both).  Every check runs
+// before any device work, and nothing is written on a refusal.
+namespace {
+struct CvRaw {
+    int* precision; int* k_max; double* tol; int* max_iter; int *center, *seed;
+    double *L1_u, *L1_v, *L2_u, *L2_v; int *nonneg_u, *nonneg_v; double *ub_u, *ub_v;
+    double* test_fraction; int *cv_seed, *patience, *mask_zeros;
+    const int *obs_mask_p, *obs_mask_i; int *obs_mask_rows, *obs_mask_cols, *obs_mask_nnz;
+    double *U, *d, *V; int *out_k_selected, *out_k_computed; double* out_test_loss; int *out_n_test, *out_n_masked;
+    int* out_iters_per_factor; double *out_frobenius_norm_sq, *out_row_means, *out_wall_time_ms;
+};
+
+Opts make_cv_opts(const CvRaw& a, const int* m, const int* n) {
+    if (!m || !n || !a.precision || !a.k_max || !a.tol || !a.max_iter || !a.center || !a.seed || !a.L1_u || !a.L1_v || !a.L2_u ||
+        !a.L2_v || !a.nonneg_u || !a.nonneg_v || !a.ub_u || !a.ub_v || !a.test_fraction || !a.cv_seed || !a.patience || !a.mask_zeros ||
+        !a.U || !a.d || !a.V || !a.out_k_selected || !a.out_k_computed || !a.out_test_loss || !a.out_n_test || !a.out_n_masked ||
+        !a.out_iters_per_factor || !a.out_frobenius_norm_sq || !a.out_row_means || !a.out_wall_time_ms)
+        throw std::invalid_argument("null pointer");
+    if (*a.precision != RCPPML_F32 && *a.precision != RCPPML_F64) throw std::invalid_argument("precision must be RCPPML_F32 or RCPPML_F64");
+    Opts o;
+    o.m = *m; o.n = *n; o.k = *a.k_max;
+    o.tol = *a.tol; o.max_iter = *a.max_iter; o.center = *a.center != 0; o.seed = (unsigned)(uint32_t)*a.seed;
+    o.algorithm = 0;
+    o.L1_u = *a.L1_u; o.L1_v = *a.L1_v; o.L2_u = *a.L2_u; o.L2_v = *a.L2_v; o.ub_u = *a.ub_u; o.ub_v = *a.ub_v;
+    o.nonneg_u = *a.nonneg_u != 0; o.nonneg_v = *a.nonneg_v != 0;
+    o.test_fraction = *a.test_fraction; o.patience = *a.patience; o.mask_zeros = *a.mask_zeros != 0;
+    // core/svd_config.hpp:149-151
+    const uint32_t cs = (uint32_t)*a.cv_seed;
+    o.cv_seed = cs != 0 ? cs : (o.seed != 0 ? (uint32_t)(o.seed ^ 0xBEEFu) : 42u);
+    if (o.m < 1 || o.n < 1) throw std::invalid_argument("the matrix must have at least one row and one column");
+    if (o.k < 1 || o.k > std::min(o.m, o.n)) throw std::invalid_argument("k_max must be in [1, min(m, n)]");
+    if (o.k + 2 > NPMAX) throw std::invalid_argument("k_max above " + std::to_string(NPMAX - 2) + " is not supported");
+    if (o.max_iter < 1) throw std::invalid_argument("deflation needs max_iter >= 1");
+    if (o.patience < 1) throw std::invalid_argument("patience must be >= 1");
+    if (!(o.test_fraction >= 0 && o.test_fraction < 1)) throw std::invalid_argument("test_fraction must be in [0, 1)");
+    if (!(o.tol >= 0)) throw std::invalid_argument("tol must be non-negative");
+    if (a.obs_mask_p) {
+        if (!a.obs_mask_rows || !a.obs_mask_cols || !a.obs_mask_nnz) throw std::invalid_argument("null pointer");
+        if (*a.obs_mask_rows != o.m || *a.obs_mask_cols != o.n) throw std::invalid_argument("obs_mask dimensions must match the matrix");
+        o.mnnz = *a.obs_mask_nnz;
+        if (o.mnnz < 0 || (o.mnnz > 0 && !a.obs_mask_i)) throw std::invalid_argument("null obs_mask array");
+        check_csc_strict(a.obs_mask_p, a.obs_mask_i, o.m, o.n, o.mnnz);
+        o.mp = a.obs_mask_p; o.mi = a.obs_mask_i;
+    }
+    return o;
+}
+
+// device bytes of a fit, generously: A, its transpose or training copy, the fp32 staging copy, twice the expected test entries,
+// the factors and the partial buffers
+size_t cv_bytes(const Opts& o, size_t ts) {
+    const size_t len = o.dense ? (size_t)o.m * o.n : (size_t)o.nnz;
+    size_t b = len * (o.dense ? 2 * ts : 2 * (sizeof(int) + ts) + ts) + len * sizeof(double);
+    b += (size_t)(std::min(1.0, 2 * o.test_fraction) * (double)len) * (2 * sizeof(int) + ts);
+    b += ((size_t)o.m + o.n) * ((size_t)o.k + 8) * ts + ((size_t)nblk(o.m) + nblk(o.n)) * ((size_t)o.k + 4) * ts;
+    b += ((size_t)o.n + 1) * 3 * sizeof(int) + (size_t)o.mnnz * sizeof(int);
+    return b;
+}
+
+void run_cv_entry(const CvRaw& a, const Opts& o) {
+    const bool f32 = *a.precision == RCPPML_F32;
+    device_ready(cv_bytes(o, f32 ? sizeof(float) : sizeof(double)), "the SVD");
+    const auto t0 = std::chrono::steady_clock::now();
+    Result R;
+    if (f32) { Engine<float> E(o); E.run(R); }
+    else { Engine<double> E(o); E.run(R); }
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::copy(R.U.begin(), R.U.end(), a.U);           // the first k_selected columns
+    std::copy(R.V.begin(), R.V.end(), a.V);
+    std::copy(R.d.begin(), R.d.end(), a.d);
+    std::copy(R.iters.begin(), R.iters.end(), a.out_iters_per_factor);
+    std::copy(R.test_loss.begin(), R.test_loss.end(), a.out_test_loss);
+    *a.out_k_selected = R.k_sel;
+    *a.out_k_computed = R.k_computed;
+    *a.out_n_test = R.n_test;
+    *a.out_n_masked = (int)R.n_masked;
+    *a.out_frobenius_norm_sq = R.frob;
+    if (o.center) std::copy(R.row_means.begin(), R.row_means.end(), a.out_row_means);
+    *a.out_wall_time_ms = ms;
+}
+}  // namespace
+
+#define RCPPML_SVD_CV_PARAMS                                                                                                      \
+    int *precision, int *k_max, double *tol, int *max_iter, int *center, int *seed, double *L1_u, double *L1_v, double *L2_u,       \
+        double *L2_v, int *nonneg_u, int *nonneg_v, double *ub_u, double *ub_v, double *test_fraction, int *cv_seed, int *patience, \
+        int *mask_zeros, const int *obs_mask_p, const int *obs_mask_i, int *obs_mask_rows, int *obs_mask_cols, int *obs_mask_nnz,   \
+        double *U, double *d, double *V, int *out_k_selected, int *out_k_computed, double *out_test_loss, int *out_n_test,          \
+        int *out_n_masked, int *out_iters_per_factor, double *out_frobenius_norm_sq, double *out_row_means,                         \
+        double *out_wall_time_ms, int *out_status
+#define RCPPML_SVD_CV_RAW                                                                                                         \
+    CvRaw{precision, k_max, tol, max_iter, center, seed, L1_u, L1_v, L2_u, L2_v, nonneg_u, nonneg_v, ub_u, ub_v, test_fraction,   \
+          cv_seed, patience, mask_zeros, obs_mask_p, obs_mask_i, obs_mask_rows, obs_mask_cols, obs_mask_nnz, U, d, V,              \
+          out_k_selected, out_k_computed, out_test_loss, out_n_test, out_n_masked, out_iters_per_factor, out_frobenius_norm_sq,    \
+          out_row_means, out_wall_time_ms}
+
+extern "C" void rcppml_gpu_svd_cv_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+                                     RCPPML_SVD_CV_PARAMS) {
+    entry_guard(out_status, [&] {
+        const CvRaw a = RCPPML_SVD_CV_RAW;
+        Opts o = make_cv_opts(a, m, n);
+        if (!nnz) throw std::invalid_argument("null pointer");
+        o.nnz = *nnz; o.p = col_ptr; o.i = row_idx; o.x = values;
+        check_csc_lenient(o.p, o.i, o.x, o.m, o.n, o.nnz);
+        run_cv_entry(a, o);
+    });
+}
+extern "C" void rcppml_gpu_svd_cv_dense_ex(const double* A_data, int* m, int* n, RCPPML_SVD_CV_PARAMS) {
+    entry_guard(out_status, [&] {
+        const CvRaw a = RCPPML_SVD_CV_RAW;
+        Opts o = make_cv_opts(a, m, n);
+        if (!A_data) throw std::invalid_argument("null matrix");
+        o.nnz = (int64_t)o.m * o.n; o.dense = A_data;
+        run_cv_entry(a, o);
+    });
 }

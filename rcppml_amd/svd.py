@@ -1,7 +1,9 @@
 """svd() and pca(): host-side mirror of the reference R surface (R/svd.R) on the HIP SVD path (csrc/ops_svd.hip).  Method
 resolution, per-method maxit defaults and the validation messages are R's (R/svd.R:118-406) for the arguments this surface takes;
-the GPU runs deflation (method "deflation") or Golub-Kahan-Lanczos (every other method, unconstrained).  No CPU fallback: without
-a device the calls raise BackendError."""
+the GPU runs deflation (method "deflation") or Golub-Kahan-Lanczos (every other method, unconstrained).  Cross-validation,
+auto-rank (k = "auto") and a mask matrix run the deflation of the build-defined rcppml_gpu_svd_cv_ex entries (_abi.svd_cv);
+everything else stays on the reference-shaped entries (_abi.svd_pca).  No CPU fallback: without a device the calls raise
+BackendError."""
 import numpy as np
 
 from . import _abi
@@ -54,17 +56,95 @@ def resolve_method(k, method="auto", maxit=_MISSING, tol=1e-5, L1=0, L2=0, nonne
     return method, int(maxit), float(tol), (L1, L2, nonneg, upper_bound)
 
 
+def resolve_mask(mask, shape):
+    """R/svd.R:233-269: mask is None, "zeros", a sparse matrix or ("zeros", matrix).  Returns (mask_zeros, (p, i, rows, cols) or
+    None) -- the pattern of the mask's nonzero entries, rows ascending -- or raises ValueError with R's message."""
+    import scipy.sparse as sp
+    mask_zeros, mat = False, None
+    if mask is None:
+        return False, None
+    if isinstance(mask, (list, tuple)):
+        if len(mask) < 2 or not isinstance(mask[0], str) or mask[0] != "zeros":
+            raise ValueError("'mask' list must be list(\"zeros\", <matrix>)")
+        mask_zeros, mat = True, mask[1]
+    elif isinstance(mask, str):
+        if mask != "zeros":
+            raise ValueError("'mask' string must be \"zeros\". Got: '%s'" % mask)
+        mask_zeros = True
+    else:
+        mat = mask
+    if mat is None:
+        return mask_zeros, None
+    if not sp.issparse(mat):
+        raise ValueError("'mask' must be NULL, 'zeros', a dgCMatrix, or list(\"zeros\", <dgCMatrix>)")
+    mat = sp.csc_matrix(mat)
+    mat.eliminate_zeros()
+    mat.sum_duplicates()
+    mat.sort_indices()
+    if mat.shape != tuple(shape):
+        raise ValueError("'mask' dimensions (%d x %d) must match 'A' (%d x %d)" % (mat.shape[0], mat.shape[1], shape[0], shape[1]))
+    return mask_zeros, (mat.indptr.astype(np.int32), mat.indices.astype(np.int32), mat.shape[0], mat.shape[1])
+
+
+def resolve_cv(k, method="auto", test_fraction=0, patience=3, k_max=50, L1=0, L2=0, nonneg=False, upper_bound=0):
+    """The cross-validation rules of R/svd.R beside resolve_method(): :177-186 (k = "auto" sets k = k_max and test_fraction = 0.05
+    when it is <= 0), :216-217 (ranges), :313-321 (a method without CV raises under auto-rank and drops CV silently under a fixed
+    k), :377-385 (method "auto" under CV is deflation, or krylov for a constrained k >= 8).  Returns (k, method, test_fraction,
+    auto_rank); the method goes through resolve_method() afterwards."""
+    auto_rank = isinstance(k, str) and k == "auto"
+    if auto_rank:
+        k = int(k_max)
+        if test_fraction <= 0:
+            test_fraction = 0.05
+    else:
+        k = int(k)
+        if k < 1:
+            raise ValueError("'k' must be >= 1")
+    if test_fraction < 0 or test_fraction >= 1:
+        raise ValueError("'test_fraction' must be in [0, 1)")
+    if patience < 1:
+        raise ValueError("'patience' must be >= 1")
+    has_cv = auto_rank or 0 < test_fraction < 1
+    if method not in VALID_METHODS:
+        raise ValueError("method must be one of: %s" % ", ".join(VALID_METHODS))
+    constrained = any(bool(np.any(np.asarray(v, float) > 0)) for v in (L1, L2, nonneg, upper_bound))
+    if method == "auto":
+        if has_cv:
+            method = "krylov" if constrained and k >= 8 else "deflation"
+    elif has_cv and method not in ("deflation", "krylov") and not constrained:   # constrained: resolve_method() raises first, as R
+        if auto_rank:
+            raise ValueError("method '%s' does not support auto-rank. Use 'deflation' or 'krylov'." % method)
+        test_fraction = 0
+    return k, method, float(test_fraction), auto_rank
+
+
 def svd(A, k=10, tol=1e-5, maxit=_MISSING, center=False, seed=None, L1=0, L2=0, nonneg=False, upper_bound=0, method="auto",
-        precision="float"):
+        precision="float", test_fraction=0, mask=None, cv_seed=None, patience=3, k_max=50):
     """Truncated SVD on the GPU (R/svd.R with resource = "gpu").  A: scipy sparse / CSC (the sparse entries) or a dense matrix (the
     dense entries).  precision: "float" (fp32 on the device, R's default) or "double".  Constrained fits with k >= 8 resolve to
-    krylov, as in R, which the GPU refuses (BackendError); pass method="deflation" for them.  Returns dict(u, d, v, misc) with
-    misc = dict(iters_per_factor, frobenius_norm_sq, row_means (or None), method, wall_time_ms)."""
+    krylov, as in R, which the GPU refuses (BackendError); pass method="deflation" for them.
+
+    k = "auto" (rank up to k_max, default 50) or test_fraction > 0 holds out a speckled set of entries and stops adding factors
+    when their error has not improved for `patience` factors, with a fixed k too, so fewer than k factors may come back; the
+    result is trimmed to the best rank.  mask: None, "zeros" (only stored entries are held out), a sparse matrix whose nonzero
+    entries are unobserved, or ("zeros", matrix).  cv_seed: seed of the hold-out set (None: derived from seed).  These run
+    deflation; under CV krylov is refused on the GPU, and so is a mask matrix with any method but deflation.  A rank above
+    min(m, n) is clamped here (the reference's gateway passes k_max on unchanged and its loop then ends on sigma ~ 0).
+
+    Returns dict(u, d, v, misc) with misc = dict(iters_per_factor, frobenius_norm_sq, row_means (or None), method, wall_time_ms,
+    auto_rank, k_selected, test_loss (one value per computed factor; empty without CV), n_test, cv_seed_effective)."""
     M, dense = as_matrix(A, what="'A' must be a matrix, dgCMatrix, or path to a .spz file")
+    shape = dense.shape if dense is not None else (M.rows, M.cols)
+    k, method, test_fraction, auto_rank = resolve_cv(k, method, test_fraction, patience, k_max, L1, L2, nonneg, upper_bound)
     method, maxit, tol, (L1v, L2v, nn, ub) = resolve_method(k, method, maxit, tol, L1, L2, nonneg, upper_bound)
+    mask_zeros, obs = resolve_mask(mask, shape)
     if precision not in ("float", "double"):
         raise ValueError("precision must be 'float' or 'double'")
     s = 0 if seed is None else int(seed)
+    cs = 0 if cv_seed is None else int(cv_seed)
+    if test_fraction > 0 or obs is not None:
+        return _svd_cv(M, dense, min(k, min(shape)), method, maxit, tol, center, s, (L1v, L2v, nn, ub), precision, test_fraction, cs,
+                       int(patience), mask_zeros, obs, auto_rank)
     kw = dict(precision=precision, tol=tol, max_iter=maxit, center=center, seed=s, L1=L1v, L2=L2v, nonneg=nn, upper_bound=ub,
               algorithm=_abi.SVD_ALGORITHMS[method])
     if dense is not None:
@@ -79,7 +159,31 @@ def svd(A, k=10, tol=1e-5, maxit=_MISSING, center=False, seed=None, L1=0, L2=0, 
     iters = r["iters"]
     nz = int(np.sum(iters > 0)) or ks
     misc = dict(iters_per_factor=iters[:nz].copy(), frobenius_norm_sq=r["frob"],
-                row_means=r["row_means"][:m].copy() if center else None, method=method, wall_time_ms=r["wall_ms"])
+                row_means=r["row_means"][:m].copy() if center else None, method=method, wall_time_ms=r["wall_ms"],
+                auto_rank=False, k_selected=ks, test_loss=np.zeros(0), n_test=0, cv_seed_effective=None)
+    return dict(u=r["U"][:, :ks].copy(), d=r["d"][:ks].copy(), v=r["V"][:, :ks].copy(), misc=misc)
+
+
+def _svd_cv(M, dense, k, method, maxit, tol, center, seed, cons, precision, test_fraction, cv_seed, patience, mask_zeros, obs, auto_rank):
+    """The cross-validated / masked call: deflation through _abi.svd_cv."""
+    if method != "deflation":
+        raise _abi.BackendError("GPU SVD/PCA failed: cross-validation, auto-rank and a mask matrix need method 'deflation' on the GPU "
+                                "(got '%s')" % method)
+    L1v, L2v, nn, ub = cons
+    src = dense if dense is not None else (M.p, M.i, M.x, M.rows, M.cols)
+    r = _abi.svd_cv(src, k, dense=dense is not None, precision=precision, tol=tol, max_iter=maxit, center=center, seed=seed, L1=L1v,
+                    L2=L2v, nonneg=nn, upper_bound=ub, test_fraction=test_fraction, cv_seed=cv_seed, patience=patience,
+                    mask_zeros=mask_zeros, obs_mask=obs)
+    if r["status"] != 0:
+        raise _abi.BackendError("GPU SVD/PCA failed: %s" % r["error"])
+    ks, kc = r["k"], r["k_computed"]
+    m = dense.shape[0] if dense is not None else M.rows
+    s32, c32 = seed & 0xFFFFFFFF, cv_seed & 0xFFFFFFFF
+    eff = (c32 if c32 != 0 else ((s32 ^ 0xBEEF) if s32 != 0 else 42)) if test_fraction > 0 else None    # core/svd_config.hpp:149-151
+    misc = dict(iters_per_factor=r["iters"][:kc].copy(), frobenius_norm_sq=r["frob"],
+                row_means=r["row_means"][:m].copy() if center else None, method=method, wall_time_ms=r["wall_ms"],
+                auto_rank=auto_rank, k_selected=ks, test_loss=r["test_loss"][:kc].copy() if test_fraction > 0 else np.zeros(0),
+                n_test=r["n_test"], cv_seed_effective=eff)
     return dict(u=r["U"][:, :ks].copy(), d=r["d"][:ks].copy(), v=r["V"][:, :ks].copy(), misc=misc)
 
 

@@ -8,7 +8,11 @@ each in fp32 and fp64.  Per workload, after one warm-up call: the best and all o
 checks, upload, device transpose, the solve, the download), iterations (deflation: per factor; Lanczos: steps), and the entry's own
 out_wall_time_ms.  --cpu also times the numpy restatement of the reference's CPU deflation (tests/svd_ref.py, dense numpy on the
 machine's BLAS threads -- not the reference's C++) and, for Lanczos, numpy's dense LAPACK SVD of the centered matrix; both are
-labelled as such.  Prints one JSON line per workload."""
+labelled as such.  Prints one JSON line per workload.
+
+--auto runs one leg only: pca(k = "auto") through the Python surface (rcppml_gpu_svd_cv_ex: cross-validated deflation, k_max 50,
+test_fraction 0.05, patience 3, fp64), and prints one JSON line with the call's wall time (best of three after a warm-up),
+k_selected, the factors computed, and the time and rank of the numpy restatement (tests/svd_cv_ref.py; not the reference's C++)."""
 import argparse
 import json
 import os
@@ -40,11 +44,34 @@ def timed(fn, reps=3):
     return out, ts
 
 
+def auto_leg(A):
+    import scipy.sparse as sp
+    import svd_cv_ref
+    from rcppml_amd import svd as S
+    r, ts = timed(lambda: S.pca(A, k="auto", precision="double"))
+    mi = r["misc"]
+    M = sp.csc_matrix((A.x, A.i, A.p), shape=(A.rows, A.cols))
+    t0 = time.perf_counter()
+    ref = svd_cv_ref.cv_deflation_svd(M.toarray(), min(50, A.rows, A.cols), stored=(M != 0).toarray(), center=True,
+                                      test_fraction=0.05, patience=3)
+    cpu_s = time.perf_counter() - t0
+    print(json.dumps(dict(workload="pca k=auto deflation cv", precision="double", m=A.rows, n=A.cols, nnz=int(A.x.shape[0]),
+                          wall_s=min(ts), wall_s_all=ts, entry_wall_ms=mi["wall_time_ms"], k_selected=int(mi["k_selected"]),
+                          k_computed=int(len(mi["test_loss"])), n_test=int(mi["n_test"]), test_loss=mi["test_loss"].tolist(),
+                          cpu_s=cpu_s, cpu_k_selected=int(ref["k_selected"]), cpu_k_computed=int(ref["k_computed"]),
+                          cpu_label="numpy restatement of the reference CPU deflation with CV (tests/svd_cv_ref.py), not the "
+                                    "reference's C++")), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cpu", action="store_true", help="also time the numpy restatements (slow)")
+    ap.add_argument("--auto", action="store_true", help="only the pca(k = \"auto\") leg")
     args = ap.parse_args()
     A = pbmc3k()
+    if args.auto:
+        auto_leg(A)
+        return
     parts = (A.p, A.i, A.x, A.rows, A.cols)
     work = [("pca k=10 lanczos", dict(k=10, center=True, algorithm=2, max_iter=0)),
             ("svd k=5 nonneg deflation", dict(k=5, center=False, algorithm=0, max_iter=200, nonneg=(True, True)))]
