@@ -1583,6 +1583,38 @@ ORACLE_API int oracle_cv_is_holdout(double frac, uint64_t cv_seed, int i, int j)
         cv_explicit_loss(mk(m, n, p, i, x), Wd.data(), H, k, SpeckledMask(frac, cv_seed, mask_zeros != 0), c, theta, 1, out_train, \
                          n_train, out_test, n_test);                                                               \
     }                                                                                                              \
+    /* the same three with the user mask (pattern CSC in the orientation of the data matrix; mask_p = NULL: none) */ \
+    ORACLE_API void oracle_cv_half_update_masked_##SUF(int rows, int cols, const int* p, const int* i, const S* x, const S* F, \
+                                                       const S* G, S* X, int k, double frac, uint64_t cv_seed, int mask_zeros, \
+                                                       int transposed, S L1, int nonneg, int cd_maxit, int solver_mode,   \
+                                                       int threads, const int* mask_p, const int* mask_i) {               \
+        const Csc<S> um = mk(rows, cols, mask_p, mask_i, (const S*)nullptr);                                       \
+        cv_half_update(mk(rows, cols, p, i, x), F, G, X, k, SpeckledMask(frac, cv_seed, mask_zeros != 0),          \
+                       transposed != 0, L1, nonneg != 0, cd_maxit, solver_mode, threads, mask_p ? &um : nullptr);  \
+    }                                                                                                              \
+    ORACLE_API void oracle_cv_irls_half_update_masked_##SUF(int rows, int cols, const int* p, const int* i, const S* x, const S* F, \
+                                                     const S* G_add, S* X, int k, double frac, uint64_t cv_seed, int mask_zeros, \
+                                                     int transposed, S L1, int nonneg, int cd_maxit, int solver_mode, int loss_type, \
+                                                     int irls_max_iter, S irls_tol, S power, S robust, int threads,  \
+                                                     const int* mask_p, const int* mask_i) {                        \
+        FitConfig<S> c;                                                                                            \
+        c.k = k; c.cd_maxit = cd_maxit; c.solver_mode = solver_mode; c.loss_type = loss_type; c.irls_max_iter = irls_max_iter; \
+        c.irls_tol = irls_tol; c.tweedie_power = power; c.robust_delta = robust;                                   \
+        const Csc<S> um = mk(rows, cols, mask_p, mask_i, (const S*)nullptr);                                       \
+        cv_irls_half_update(mk(rows, cols, p, i, x), F, X, k, SpeckledMask(frac, cv_seed, mask_zeros != 0), transposed != 0, L1, \
+                            nonneg != 0, c, G_add, threads, mask_p ? &um : nullptr);                               \
+    }                                                                                                              \
+    ORACLE_API void oracle_cv_explicit_loss_masked_##SUF(int m, int n, const int* p, const int* i, const S* x, const S* W_T, const S* d, \
+                                                  const S* H, int k, double frac, uint64_t cv_seed, int mask_zeros, int loss_type, \
+                                                  S power, const S* theta, S* out_train, int64_t* n_train, S* out_test, int64_t* n_test, \
+                                                  const int* mask_p, const int* mask_i) {                           \
+        std::vector<S> Wd((size_t)k * m);                                                                          \
+        for (int r = 0; r < m; ++r) for (int f = 0; f < k; ++f) Wd[(size_t)r * k + f] = W_T[(size_t)r * k + f] * d[f]; \
+        FitConfig<S> c; c.k = k; c.loss_type = loss_type; c.tweedie_power = power;                                 \
+        const Csc<S> um = mk(m, n, mask_p, mask_i, (const S*)nullptr);                                             \
+        cv_explicit_loss(mk(m, n, p, i, x), Wd.data(), H, k, SpeckledMask(frac, cv_seed, mask_zeros != 0), c, theta, 1, out_train, \
+                         n_train, out_test, n_test, mask_p ? &um : nullptr);                                       \
+    }                                                                                                              \
     ORACLE_API void oracle_cv_gp_theta_update_##SUF(int m, int n, const int* p, const int* i, const S* x, const S* W_T, const S* d, \
                                                     const S* H, int k, double frac, uint64_t cv_seed, int mode, S theta_max, S* theta) { \
         FitConfig<S> c; c.k = k; c.dispersion_mode = mode; c.gp_theta_max = theta_max;                             \

@@ -461,17 +461,26 @@ def cv_hash(seed, i, j):
     return int(fn(C.c_uint64(seed), C.c_uint32(i), C.c_uint32(j)))
 
 
+def _mask_args(mask):
+    """The trailing (mask_p, mask_i) of the oracle_cv_*_masked exports: mask = a pattern (p, i) in the orientation of the data matrix."""
+    return (_p(np.ascontiguousarray(mask.p, np.int32)), _p(np.ascontiguousarray(mask.i, np.int32)))
+
+
 def cv_half_update(A, F, G, X, k, frac, cv_seed, mask_zeros=False, transposed=False, L1=0.0, nonneg=True, cd_maxit=100,
-                   solver_mode=0, threads=1, dtype=np.float64):
-    """One CV half-update over the columns of A (the W side passes A^T with transposed=True)."""
+                   solver_mode=0, threads=1, dtype=np.float64, mask=None):
+    """One CV half-update over the columns of A (the W side passes A^T with transposed=True).  mask: the user mask, a pattern
+    (p, i) in the orientation of A as passed (None: the export without a mask)."""
     suf, ct = _suf(dtype)
     F, G = _f(F, dtype), _f(G, dtype)
     X = _f(X, dtype).copy()
     x = A.values(dtype)
-    getattr(lib(), "oracle_cv_half_update_" + suf)(C.c_int(A.rows), C.c_int(A.cols), _p(A.p), _p(A.i), _p(x), _p(F), _p(G), _p(X),
-                                                   C.c_int(k), C.c_double(frac), C.c_uint64(cv_seed), C.c_int(int(mask_zeros)),
-                                                   C.c_int(int(transposed)), ct(L1), C.c_int(int(nonneg)), C.c_int(cd_maxit),
-                                                   C.c_int(solver_mode), C.c_int(threads))
+    args = (C.c_int(A.rows), C.c_int(A.cols), _p(A.p), _p(A.i), _p(x), _p(F), _p(G), _p(X), C.c_int(k), C.c_double(frac),
+            C.c_uint64(cv_seed), C.c_int(int(mask_zeros)), C.c_int(int(transposed)), ct(L1), C.c_int(int(nonneg)), C.c_int(cd_maxit),
+            C.c_int(solver_mode), C.c_int(threads))
+    if mask is None:
+        getattr(lib(), "oracle_cv_half_update_" + suf)(*args)
+    else:
+        getattr(lib(), "oracle_cv_half_update_masked_" + suf)(*args, *_mask_args(mask))
     return X
 
 
@@ -487,32 +496,35 @@ def cv_test_error(A, W_T, d, H, frac, cv_seed, mask_zeros=False, dtype=np.float6
 
 
 def cv_irls_half_update(A, F, X, k, frac, cv_seed, loss_type, G_add=None, mask_zeros=False, transposed=False, L1=0.0, nonneg=True,
-                        cd_maxit=100, solver_mode=0, irls_max_iter=5, irls_tol=1e-4, power=1.5, robust=0.0, threads=1, dtype=np.float64):
-    """One CV half-update with an IRLS loss (reference nmf/cv_detail.hpp:101-292) over the columns of A (W side: A^T, transposed)."""
+                        cd_maxit=100, solver_mode=0, irls_max_iter=5, irls_tol=1e-4, power=1.5, robust=0.0, threads=1, dtype=np.float64,
+                        mask=None):
+    """One CV half-update with an IRLS loss (reference nmf/cv_detail.hpp:101-292) over the columns of A (W side: A^T, transposed).
+    mask: as in cv_half_update."""
     suf, ct = _suf(dtype)
     F = _f(F, dtype)
     X = _f(X, dtype).copy()
     Ga = _f(G_add, dtype) if G_add is not None else None
     x = A.values(dtype)
-    getattr(lib(), "oracle_cv_irls_half_update_" + suf)(
+    getattr(lib(), "oracle_cv_irls_half_update_" + ("masked_" if mask is not None else "") + suf)(
         C.c_int(A.rows), C.c_int(A.cols), _p(A.p), _p(A.i), _p(x), _p(F), _p(Ga) if Ga is not None else None, _p(X), C.c_int(k),
         C.c_double(frac), C.c_uint64(cv_seed), C.c_int(int(mask_zeros)), C.c_int(int(transposed)), ct(L1), C.c_int(int(nonneg)),
         C.c_int(cd_maxit), C.c_int(solver_mode), C.c_int(loss_type), C.c_int(irls_max_iter), ct(irls_tol), ct(power), ct(robust),
-        C.c_int(threads))
+        C.c_int(threads), *(_mask_args(mask) if mask is not None else ()))
     return X
 
 
-def cv_explicit_loss(A, W_T, d, H, frac, cv_seed, loss_type, theta=None, mask_zeros=False, power=1.5, dtype=np.float64):
-    """(train sum, n_train, test sum, n_test) of the per-element losses (reference nmf/fit_cv.hpp:1377-1443)."""
+def cv_explicit_loss(A, W_T, d, H, frac, cv_seed, loss_type, theta=None, mask_zeros=False, power=1.5, dtype=np.float64, mask=None):
+    """(train sum, n_train, test sum, n_test) of the per-element losses (reference nmf/fit_cv.hpp:1377-1443).  mask: the user
+    mask, a pattern (p, i) of A's shape, whose entries are left out of both sums (None: the export without a mask)."""
     suf, ct = _suf(dtype)
     W_T, H, d = _f(W_T, dtype), _f(H, dtype), _f(d, dtype)
     th = _f(theta if theta is not None else np.zeros(A.rows), dtype)
     x = A.values(dtype)
     tr, te, ntr, nte = ct(0), ct(0), C.c_int64(0), C.c_int64(0)
-    getattr(lib(), "oracle_cv_explicit_loss_" + suf)(
+    getattr(lib(), "oracle_cv_explicit_loss_" + ("masked_" if mask is not None else "") + suf)(
         C.c_int(A.rows), C.c_int(A.cols), _p(A.p), _p(A.i), _p(x), _p(W_T), _p(d), _p(H), C.c_int(W_T.shape[1]), C.c_double(frac),
         C.c_uint64(cv_seed), C.c_int(int(mask_zeros)), C.c_int(loss_type), ct(power), _p(th), C.byref(tr), C.byref(ntr), C.byref(te),
-        C.byref(nte))
+        C.byref(nte), *(_mask_args(mask) if mask is not None else ()))
     return float(tr.value), int(ntr.value), float(te.value), int(nte.value)
 
 

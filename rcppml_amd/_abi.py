@@ -599,6 +599,11 @@ class Context:
                                        C.c_ulonglong(cv_seed), C.c_int(mask_zeros), C.c_int(transposed), C.c_double(l1),
                                        C.c_int(nonneg), C.c_int(cd_maxit), C.c_int(solver_mode)), "solve_cv")
 
+    def set_cv_mask(self, mask_p=None, mask_i=None, maskT_p=None, maskT_i=None):
+        """The user mask of a cross-validation fit: pattern CSC (int32 device arrays) of the mask and of its transpose, which must stay
+        alive until the mask is cleared -- all four None.  While set, solve_cv, solve_cv_irls and cv_irls_loss honour it."""
+        _chk(lib().rcppml_hip_ctx_set_cv_mask(self._h, _dptr(mask_p), _dptr(mask_i), _dptr(maskT_p), _dptr(maskT_i)), "ctx_set_cv_mask")
+
     def cv_test_error(self, dt, col_ptr, row_idx, values, ncols, nrows, W_T, d, H, k, frac, cv_seed, mask_zeros, out2):
         _chk(lib().rcppml_hip_cv_test_error(self._h, C.c_int(dt), _dptr(col_ptr), _dptr(row_idx), _dptr(values), C.c_int64(ncols),
                                             C.c_int(nrows), _dptr(W_T), _dptr(d), _dptr(H), C.c_int(k), C.c_double(frac),
