@@ -1621,653 +1621,6 @@ __global__ __launch_bounds__(256) void loss_mse_final(const double* __restrict__
 }
 
 // ---------------------------------------------------------------------------
-// Explicit-mask per-column NNLS (reference nmf/masked_nnls.hpp:96-154 / 177-242).
-// One wavefront per column; lane r owns feature r (k <= 64).  The per-column Gram
-//   G_loc = G_full - sum_{r in masked(j)} f_r f_r^T  (+ l2 on the diagonal)
-// lives in LDS (one k x k tile per wave); b skips masked rows of A (two-pointer merge: both row
-// lists are sorted).  Solve: CD exactly as the wave variant above (sequential visit, in-order), or
-// in-LDS Cholesky + clip for solver_mode 1.
-// ---------------------------------------------------------------------------
-// ---------------------------------------------------------------------------
-// Cross-validation half-update (reference nmf/fit_cv.hpp:420-478 / :591-830, nmf/cv_detail.hpp:66-85,304-405,
-// nmf/speckled_cv.hpp): speckled holdout mask defined by SplitMix64::hash(seed, i, j) < UINT64_MAX / inv_prob
-// (rng/rng.hpp:129-170), no mask matrix.  One wavefront per column j of D (D = A on the H side, A^T with
-// transposed = 1 on the W side; the mask is always asked in the coordinates of A):
-//   b       = sum over the column's TRAIN nonzeros  a F(row, :)
-//   G_local = G - sum over the column's TEST rows  F(row, :) F(row, :)^T   (mask_zeros: held-out nonzeros only;
-//             otherwise every held-out row, zeros included -- the 64 lanes hash 64 rows at a time)
-//   x       = cholesky_clip(G_local, b - L1) or CD(G_local, b, x; L1 inside, cd_maxit sweeps, no tolerance), started from
-//             the current column without a warm-start correction of b, exactly as the reference does.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long cv_hash_dev(unsigned long long seed, unsigned i, unsigned j) {
-    unsigned long long h = seed + (unsigned long long)i * 0x9e3779b97f4a7c15ULL + (unsigned long long)j * 0x6c62272e07bb0142ULL;
-    h = (h ^ (h >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    h = (h ^ (h >> 27)) * 0x94d049bb133111ebULL;
-    return h ^ (h >> 31);
-}
-
-// user mask of a CV fit (fit_cv.hpp:327-331; cv_detail.hpp:408-415 is_user_masked_h): pattern CSC in the orientation of the CSC the
-// kernel walks, rows ascending inside a column; NULL = none.  Bisection: masks are sparse and the question is asked per entry.
-__device__ __forceinline__ bool cv_user_masked(const int* __restrict__ mp, const int* __restrict__ mi, int64_t j, int row) {
-    if (!mp) return false;
-    int lo = mp[j];
-    const int end = mp[j + 1];
-    int hi = end;
-    while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (mi[mid] < row) lo = mid + 1; else hi = mid; }
-    return lo < end && mi[lo] == row;
-}
-// is `row` one of the stored rows of column [ts, te) of a CSC with ascending rows?
-__device__ __forceinline__ bool cv_row_stored(const int* __restrict__ rowidx, int ts, int te, int row) {
-    int lo = ts, hi = te;
-    while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (rowidx[mid] < row) lo = mid + 1; else hi = mid; }
-    return lo < te && rowidx[lo] == row;
-}
-
-// (mp, mi: optional user mask, cv_detail.hpp:433-505 -- a masked row that is not already a test row leaves b and joins the rows of
-// the Gram correction, whether its entry is a nonzero or not)
-template <class T, int KP>   // KP in {32, 64}
-__global__ __launch_bounds__(256) void cv_solve_kernel(
-    const int* __restrict__ colptr, const int* __restrict__ rowidx, const T* __restrict__ vals, int64_t ncols, int nrows,
-    const T* __restrict__ F, const T* __restrict__ Gfull, T* __restrict__ X, int k, unsigned long long seed,
-    unsigned long long threshold, int mask_zeros, int transposed, T l1, int nonneg, int maxit, int solver_mode,
-    const int* __restrict__ mp = nullptr, const int* __restrict__ mi = nullptr) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    T* Gl = reinterpret_cast<T*>(smem_raw) + (size_t)wave * KP * KP;   // [c][r]
-    const int64_t j = (int64_t)blockIdx.x * 4 + wave;
-    if (j >= ncols) return;
-    const bool fok = lane < k;
-    const bool lin = lane < KP;
-    const int ll = lin ? lane : 0;
-    for (int c = 0; c < KP; ++c) {
-        T v = (fok && c < k) ? Gfull[(int64_t)c * k + lane] : (c == lane ? T(1) : T(0));
-        if (lin) Gl[c * KP + lane] = v;
-    }
-    const unsigned col = (unsigned)j;
-    // train right-hand side (and, with mask_zeros, the Gram correction of the held-out nonzeros)
-    T b = T(0);
-    for (int t = colptr[j]; t < colptr[j + 1]; ++t) {
-        const int row = rowidx[t];
-        const bool held = (transposed ? cv_hash_dev(seed, col, (unsigned)row) : cv_hash_dev(seed, (unsigned)row, col)) < threshold;
-        const T fr = fok ? F[(int64_t)row * k + lane] : T(0);
-        if (!held) {
-            if (!cv_user_masked(mp, mi, j, row)) b = tfma(vals[t], fr, b);
-        } else if (mask_zeros) {
-            for (int c = 0; c < k; ++c) {
-                const T fc = __shfl(fr, c, 64);
-                if (lin) Gl[c * KP + lane] -= fr * fc;
-            }
-        }
-    }
-    if (!mask_zeros) {      // every held-out row of this column, zeros included
-        for (int r0 = 0; r0 < nrows; r0 += 64) {
-            const int r = r0 + lane;
-            const bool held = r < nrows &&
-                (transposed ? cv_hash_dev(seed, col, (unsigned)r) : cv_hash_dev(seed, (unsigned)r, col)) < threshold;
-            unsigned long long m = __ballot(held);
-            while (m) {
-                const int bit = __builtin_ctzll(m);
-                m &= m - 1;
-                const int row = r0 + bit;
-                const T fr = fok ? F[(int64_t)row * k + lane] : T(0);
-                for (int c = 0; c < k; ++c) {
-                    const T fc = __shfl(fr, c, 64);
-                    if (lin) Gl[c * KP + lane] -= fr * fc;
-                }
-            }
-        }
-    }
-    if (mp) {               // user-masked rows that are not test rows: out of the Gram as well
-        const int ts = colptr[j], te = colptr[j + 1];
-        for (int t = mp[j]; t < mp[j + 1]; ++t) {
-            const int row = mi[t];
-            const bool held = (transposed ? cv_hash_dev(seed, col, (unsigned)row) : cv_hash_dev(seed, (unsigned)row, col)) < threshold;
-            if (held && (!mask_zeros || cv_row_stored(rowidx, ts, te, row))) continue;      // already corrected above
-            const T fr = fok ? F[(int64_t)row * k + lane] : T(0);
-            for (int c = 0; c < k; ++c) {
-                const T fc = __shfl(fr, c, 64);
-                if (lin) Gl[c * KP + lane] -= fr * fc;
-            }
-        }
-    }
-    RK_WAVE_SYNC();
-    T x = fok ? X[j * (int64_t)k + lane] : T(0);
-    if (solver_mode == 1) {
-        if (l1 > T(0) && fok) b -= l1;
-        for (int c = 0; c < KP; ++c) {
-            T s = Gl[c * KP + ll];
-            for (int p = 0; p < c; ++p) s -= Gl[p * KP + ll] * Gl[p * KP + c];
-            T dcc = __shfl(s, c, 64);
-            if (!(dcc > T(0))) dcc = tabs(dcc) + T(1e-30);
-            const T lcc = sqrt(dcc);
-            if (lin) Gl[c * KP + lane] = lane == c ? lcc : (lane > c ? s / lcc : T(0));
-            RK_WAVE_SYNC();
-        }
-        T y = b;
-        for (int i = 0; i < k; ++i) {
-            const T yi = __shfl(y, i, 64) / Gl[i * KP + i];
-            if (lane == i) y = yi;
-            else if (lane > i) y -= Gl[i * KP + ll] * yi;
-        }
-        for (int i = k - 1; i >= 0; --i) {
-            const T xi = __shfl(y, i, 64) / Gl[i * KP + i];
-            if (lane == i) y = xi;
-            else if (lane < i) y -= Gl[ll * KP + i] * xi;
-        }
-        x = y;
-        if (nonneg) x = x > T(0) ? x : T(0);
-    } else {
-        const T gd = Gl[ll * KP + ll];
-        // static coordinate sweeps (cd_static_sweeps, kernels.hip.h): the lane's Gram column read from the wave's LDS tile at
-        // compile-time offsets
-        cd_static_sweeps<T, KP>(b, x, gd, fok, l1, nonneg, maxit, [&](auto IC) { return Gl[decltype(IC)::value * KP + ll]; });
-    }
-    if (fok) X[j * (int64_t)k + lane] = x;
-}
-
-// fp32, k <= 32 (k % 4 == 0): the same half-update with the Gram correction on the MATRIX cores.  Held-out rows are
-// collected in a small LDS queue (ballot + prefix popcount); every 32 of them are gathered with 16-byte loads (lane =
-// row t, feature half hh), parked in LDS and applied as 16 rank-2 updates  G_local -= f f^T  with
-// v_mfma_f32_32x32x2_f32 (A operand = -f, B operand = f; accumulator tile initialised with G) -- against 32 shuffles
-// and 32 LDS read-modify-writes per held-out row in cv_solve_kernel.  With zeros held out a column of a 20 000-row
-// matrix has ~2 000 such rows.
-static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void cv_solve_mfma32_kernel(
-    const int* __restrict__ colptr, const int* __restrict__ rowidx, const float* __restrict__ vals, int64_t ncols, int nrows,
-    const float* __restrict__ F, const float* __restrict__ Gfull, float* __restrict__ X, int k, unsigned long long seed,
-    unsigned long long threshold, int mask_zeros, int transposed, float l1, int nonneg, int maxit, int solver_mode) {
-    constexpr int KP = 32, FS = 36, QCAP = 96;
-    constexpr int WAVE_FLOATS = 32 * FS + QCAP;       // staged rows (aliased by G_local afterwards) | row queue
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float* Fst = reinterpret_cast<float*>(smem_raw) + (size_t)wave * WAVE_FLOATS;
-    int* hq = reinterpret_cast<int*>(Fst + 32 * FS);
-    float* Gl = Fst;                                  // [c][r]
-    const int64_t j = (int64_t)blockIdx.x * 4 + wave;
-    if (j >= ncols) return;
-    const int r = lane & 31, hh = lane >> 5;
-    const bool fok = lane < k;
-    const bool lin = lane < KP;
-    const int ll = lin ? lane : 0;
-    const unsigned col = (unsigned)j;
-    f32x16 acc;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int gi = (v & 3) + 8 * (v >> 2) + 4 * hh, gj = r;
-        acc[v] = (gi < k && gj < k) ? Gfull[(int64_t)gj * k + gi] : (gi == gj ? 1.f : 0.f);
-    }
-    int qn = 0;                                       // rows waiting in hq (wave-uniform)
-    // apply the first `cnt` (<= 32) queued rows to the accumulator tile
-    auto flush = [&](int cnt) {
-        const bool ok = r < cnt;
-        const int row = ok ? hq[r] : 0;
-        const float* fsrc = F + (int64_t)row * k + 16 * hh;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int c0 = 16 * hh + 4 * q;
-            const float4 v = (ok && c0 < k) ? *reinterpret_cast<const float4*>(fsrc + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-            *reinterpret_cast<float4*>(Fst + r * FS + c0) = v;
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int nst = (cnt + 1) >> 1;
-#pragma unroll 4
-        for (int s2 = 0; s2 < nst; ++s2) {
-            const float fv = Fst[(2 * s2 + hh) * FS + r];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(-fv, fv, acc, 0, 0, 0);
-        }
-        __builtin_amdgcn_wave_barrier();
-    };
-    // append the rows flagged in `held` (one per lane, row index `row`) to the queue; flush while >= 32 are waiting
-    auto push = [&](bool held, int row) {
-        const unsigned long long m = __ballot(held);
-        if (m == 0ull) return;
-        const int rank = __popcll(m & ((1ull << lane) - 1ull));
-        if (held) hq[qn + rank] = row;
-        qn += __popcll(m);
-        __builtin_amdgcn_wave_barrier();
-        while (qn >= 32) {
-            flush(32);
-            const int rest = qn - 32;
-            const int moved = lane < rest ? hq[32 + lane] : 0;      // rest <= 63
-            __builtin_amdgcn_wave_barrier();
-            if (lane < rest) hq[lane] = moved;
-            __builtin_amdgcn_wave_barrier();
-            qn = rest;
-        }
-    };
-    float b = 0.f;
-    for (int t0 = colptr[j]; t0 < colptr[j + 1]; t0 += 64) {       // 64 nonzeros per step: lane-parallel hashing
-        const int t = t0 + lane;
-        const bool valid = t < colptr[j + 1];
-        const int row = valid ? rowidx[t] : 0;
-        const float a = valid ? vals[t] : 0.f;
-        const bool held = valid && (transposed ? cv_hash_dev(seed, col, (unsigned)row) : cv_hash_dev(seed, (unsigned)row, col)) < threshold;
-        // train right-hand side: lane = feature again, one nonzero at a time
-        unsigned long long tm = __ballot(valid && !held);
-        while (tm) {
-            const int bit = __builtin_ctzll(tm);
-            tm &= tm - 1;
-            const int rw = __builtin_amdgcn_readlane(row, bit);
-            const float av = lane_value(a, bit);
-            if (fok) b = tfma(av, F[(int64_t)rw * k + lane], b);
-        }
-        if (mask_zeros) push(held, row);
-    }
-    if (!mask_zeros) {
-        for (int r0 = 0; r0 < nrows; r0 += 64) {
-            const int rw = r0 + lane;
-            const bool held = rw < nrows &&
-                (transposed ? cv_hash_dev(seed, col, (unsigned)rw) : cv_hash_dev(seed, (unsigned)rw, col)) < threshold;
-            push(held, rw);
-        }
-    }
-    if (qn > 0) flush(qn);
-    // park G_local in LDS ([c][r]; symmetric)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int gi = (v & 3) + 8 * (v >> 2) + 4 * hh;
-        Gl[gi * KP + r] = acc[v];
-    }
-    __builtin_amdgcn_wave_barrier();
-    float x = fok ? X[j * (int64_t)k + lane] : 0.f;
-    if (solver_mode == 1) {
-        if (l1 > 0.f && fok) b -= l1;
-        for (int c = 0; c < KP; ++c) {
-            float s = Gl[c * KP + ll];
-            for (int p = 0; p < c; ++p) s -= Gl[p * KP + ll] * Gl[p * KP + c];
-            float dcc = __shfl(s, c, 64);
-            if (!(dcc > 0.f)) dcc = tabs(dcc) + 1e-30f;
-            const float lcc = sqrt(dcc);
-            if (lin) Gl[c * KP + lane] = lane == c ? lcc : (lane > c ? s / lcc : 0.f);
-            RK_WAVE_SYNC();
-        }
-        float y = b;
-        for (int i = 0; i < k; ++i) {
-            const float yi = __shfl(y, i, 64) / Gl[i * KP + i];
-            if (lane == i) y = yi;
-            else if (lane > i) y -= Gl[i * KP + ll] * yi;
-        }
-        for (int i = k - 1; i >= 0; --i) {
-            const float xi = __shfl(y, i, 64) / Gl[i * KP + i];
-            if (lane == i) y = xi;
-            else if (lane < i) y -= Gl[ll * KP + i] * xi;
-        }
-        x = y;
-        if (nonneg) x = x > 0.f ? x : 0.f;
-    } else {
-        const float gd = Gl[ll * KP + ll];
-        // the lane's column of the corrected Gram in registers: the sweep picks row i with a wave-uniform register-indexed
-        // move instead of an LDS read on the dependent chain of every step (as irls_nb_mfma32_kernel does)
-        typedef float f32x32 __attribute__((ext_vector_type(32)));
-        f32x32 gcol;
-#pragma unroll
-        for (int c = 0; c < KP; ++c) gcol[c] = Gl[c * KP + ll];
-        {
-            float gg[KP];
-#pragma unroll
-            for (int c = 0; c < KP; ++c) gg[c] = gcol[c];
-            cd_static_sweeps_scaled_f32<KP>(b, x, gd, fok, l1, nonneg, maxit, gg);
-        }
-    }
-    if (fok) X[j * (int64_t)k + lane] = x;
-}
-
-// fp32, 32 < k <= 64 (k % 4 == 0): the same on a 2 x 2 grid of 32 x 32 accumulator tiles (three MFMAs per pair of held-out
-// rows), lane = feature over the whole wave in the solve; 16 KiB of LDS per wave for G_local (two blocks per CU).
-static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void cv_solve_mfma32x2_kernel(
-    const int* __restrict__ colptr, const int* __restrict__ rowidx, const float* __restrict__ vals, int64_t ncols, int nrows,
-    const float* __restrict__ F, const float* __restrict__ Gfull, float* __restrict__ X, int k, unsigned long long seed,
-    unsigned long long threshold, int mask_zeros, int transposed, float l1, int nonneg, int maxit, int solver_mode) {
-    constexpr int KP = 64, FS = 68, QCAP = 96;
-    constexpr int WAVE_FLOATS = KP * KP + QCAP;       // G_local (its head doubles as the 32 x FS staging area) | row queue
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float* Fst = reinterpret_cast<float*>(smem_raw) + (size_t)wave * WAVE_FLOATS;
-    int* hq = reinterpret_cast<int*>(Fst + KP * KP);
-    float* Gl = Fst;                                  // [c][r]
-    const int64_t j = (int64_t)blockIdx.x * 4 + wave;
-    if (j >= ncols) return;
-    const int r = lane & 31, hh = lane >> 5;
-    const bool fok = lane < k;
-    const bool lin = lane < KP;
-    const int ll = lin ? lane : 0;
-    const unsigned col = (unsigned)j;
-    // 2 x 2 tiles of 32 x 32; the lower-left one is the transpose of the upper-right one and is never computed
-    f32x16 a00, a01, a11;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int gi = (v & 3) + 8 * (v >> 2) + 4 * hh, gj = r;
-        auto base = [&](int i2, int j2) { return (i2 < k && j2 < k) ? Gfull[(int64_t)j2 * k + i2] : (i2 == j2 ? 1.f : 0.f); };
-        a00[v] = base(gi, gj); a01[v] = base(gi, gj + 32); a11[v] = base(gi + 32, gj + 32);
-    }
-    int qn = 0;                                       // rows waiting in hq (wave-uniform)
-    // apply the first `cnt` (<= 32) queued rows to the accumulator tile
-    auto flush = [&](int cnt) {
-        const bool ok = r < cnt;
-        const int row = ok ? hq[r] : 0;
-        const float* fsrc = F + (int64_t)row * k + 32 * hh;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int c0 = 32 * hh + 4 * q;
-            const float4 v = (ok && c0 < k) ? *reinterpret_cast<const float4*>(fsrc + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-            *reinterpret_cast<float4*>(Fst + r * FS + c0) = v;
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int nst = (cnt + 1) >> 1;
-#pragma unroll 2
-        for (int s2 = 0; s2 < nst; ++s2) {
-            const float f0 = Fst[(2 * s2 + hh) * FS + r], f1 = Fst[(2 * s2 + hh) * FS + 32 + r];
-            a00 = __builtin_amdgcn_mfma_f32_32x32x2f32(-f0, f0, a00, 0, 0, 0);
-            a01 = __builtin_amdgcn_mfma_f32_32x32x2f32(-f0, f1, a01, 0, 0, 0);
-            a11 = __builtin_amdgcn_mfma_f32_32x32x2f32(-f1, f1, a11, 0, 0, 0);
-        }
-        __builtin_amdgcn_wave_barrier();
-    };
-    // append the rows flagged in `held` (one per lane, row index `row`) to the queue; flush while >= 32 are waiting
-    auto push = [&](bool held, int row) {
-        const unsigned long long m = __ballot(held);
-        if (m == 0ull) return;
-        const int rank = __popcll(m & ((1ull << lane) - 1ull));
-        if (held) hq[qn + rank] = row;
-        qn += __popcll(m);
-        __builtin_amdgcn_wave_barrier();
-        while (qn >= 32) {
-            flush(32);
-            const int rest = qn - 32;
-            const int moved = lane < rest ? hq[32 + lane] : 0;      // rest <= 63
-            __builtin_amdgcn_wave_barrier();
-            if (lane < rest) hq[lane] = moved;
-            __builtin_amdgcn_wave_barrier();
-            qn = rest;
-        }
-    };
-    float b = 0.f;
-    for (int t0 = colptr[j]; t0 < colptr[j + 1]; t0 += 64) {       // 64 nonzeros per step: lane-parallel hashing
-        const int t = t0 + lane;
-        const bool valid = t < colptr[j + 1];
-        const int row = valid ? rowidx[t] : 0;
-        const float a = valid ? vals[t] : 0.f;
-        const bool held = valid && (transposed ? cv_hash_dev(seed, col, (unsigned)row) : cv_hash_dev(seed, (unsigned)row, col)) < threshold;
-        // train right-hand side: lane = feature again, one nonzero at a time
-        unsigned long long tm = __ballot(valid && !held);
-        while (tm) {
-            const int bit = __builtin_ctzll(tm);
-            tm &= tm - 1;
-            const int rw = __builtin_amdgcn_readlane(row, bit);
-            const float av = lane_value(a, bit);
-            if (fok) b = tfma(av, F[(int64_t)rw * k + lane], b);
-        }
-        if (mask_zeros) push(held, row);
-    }
-    if (!mask_zeros) {
-        for (int r0 = 0; r0 < nrows; r0 += 64) {
-            const int rw = r0 + lane;
-            const bool held = rw < nrows &&
-                (transposed ? cv_hash_dev(seed, col, (unsigned)rw) : cv_hash_dev(seed, (unsigned)rw, col)) < threshold;
-            push(held, rw);
-        }
-    }
-    if (qn > 0) flush(qn);
-    // park G_local in LDS ([c][r]; symmetric)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int gi = (v & 3) + 8 * (v >> 2) + 4 * hh;
-        Gl[gi * KP + r] = a00[v];
-        Gl[(gi + 32) * KP + 32 + r] = a11[v];
-        Gl[(32 + r) * KP + gi] = a01[v];                  // G(row gi, col 32 + r) and its mirror
-        Gl[gi * KP + 32 + r] = a01[v];
-    }
-    __builtin_amdgcn_wave_barrier();
-    float x = fok ? X[j * (int64_t)k + lane] : 0.f;
-    if (solver_mode == 1) {
-        if (l1 > 0.f && fok) b -= l1;
-        for (int c = 0; c < KP; ++c) {
-            float s = Gl[c * KP + ll];
-            for (int p = 0; p < c; ++p) s -= Gl[p * KP + ll] * Gl[p * KP + c];
-            float dcc = __shfl(s, c, 64);
-            if (!(dcc > 0.f)) dcc = tabs(dcc) + 1e-30f;
-            const float lcc = sqrt(dcc);
-            if (lin) Gl[c * KP + lane] = lane == c ? lcc : (lane > c ? s / lcc : 0.f);
-            RK_WAVE_SYNC();
-        }
-        float y = b;
-        for (int i = 0; i < k; ++i) {
-            const float yi = __shfl(y, i, 64) / Gl[i * KP + i];
-            if (lane == i) y = yi;
-            else if (lane > i) y -= Gl[i * KP + ll] * yi;
-        }
-        for (int i = k - 1; i >= 0; --i) {
-            const float xi = __shfl(y, i, 64) / Gl[i * KP + i];
-            if (lane == i) y = xi;
-            else if (lane < i) y -= Gl[ll * KP + i] * xi;
-        }
-        x = y;
-        if (nonneg) x = x > 0.f ? x : 0.f;
-    } else {
-        const float gd = Gl[ll * KP + ll];
-        // the lane's column of the corrected Gram in registers: the sweep picks row i with a wave-uniform register-indexed
-        // move instead of an LDS read on the dependent chain of every step (as irls_nb_mfma32_kernel does)
-        typedef float f32x32 __attribute__((ext_vector_type(32)));      // (two halves: hipcc indexes 32-element vectors with
-        f32x32 gcol0, gcol1;                                            //  s_set_gpr_idx, 64-element ones through scratch)
-#pragma unroll
-        for (int c = 0; c < 32; ++c) { gcol0[c] = Gl[c * KP + ll]; gcol1[c] = Gl[(32 + c) * KP + ll]; }
-        {
-            float gg[KP];
-#pragma unroll
-            for (int c = 0; c < 32; ++c) { gg[c] = gcol0[c]; gg[32 + c] = gcol1[c]; }
-            cd_static_sweeps_scaled_f32<KP>(b, x, gd, fok, l1, nonneg, maxit, gg);
-        }
-    }
-    if (fok) X[j * (int64_t)k + lane] = x;
-}
-
-
-// fp64, k <= 32 (k % 2 == 0): the same with v_mfma_f64_16x16x4_f64 (2 x 2 tiles of 16 x 16, four held-out rows per
-// instruction step, C/D map col = lane&15, row = (lane>>4) + 4v).
-static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void cv_solve_mfma64_kernel(
-    const int* __restrict__ colptr, const int* __restrict__ rowidx, const double* __restrict__ vals, int64_t ncols, int nrows,
-    const double* __restrict__ F, const double* __restrict__ Gfull, double* __restrict__ X, int k, unsigned long long seed,
-    unsigned long long threshold, int mask_zeros, int transposed, double l1, int nonneg, int maxit, int solver_mode) {
-    constexpr int KP = 32, FS = 34, QCAP = 96;
-    constexpr int WAVE_DOUBLES = 32 * FS + QCAP / 2;   // staged rows (aliased by G_local afterwards) | row queue (ints)
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double* Fst = reinterpret_cast<double*>(smem_raw) + (size_t)wave * WAVE_DOUBLES;
-    int* hq = reinterpret_cast<int*>(Fst + 32 * FS);
-    double* Gl = Fst;                                  // [c][r]
-    const int64_t j = (int64_t)blockIdx.x * 4 + wave;
-    if (j >= ncols) return;
-    const int r = lane & 31, hh = lane >> 5;
-    const bool fok = lane < k;
-    const bool lin = lane < KP;
-    const int ll = lin ? lane : 0;
-    const unsigned col = (unsigned)j;
-    const int r16 = lane & 15, kk = lane >> 4;        // MFMA phase: feature slot r16, K-slot kk (16x16x4 f64)
-    f64x4 acc[2][2];
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int gi = 16 * ti + kk + 4 * v, gj = 16 * tj + r16;
-                acc[ti][tj][v] = (gi < k && gj < k) ? Gfull[(int64_t)gj * k + gi] : (gi == gj ? 1.0 : 0.0);
-            }
-    int qn = 0;                                       // rows waiting in hq (wave-uniform)
-    // apply the first `cnt` (<= 32) queued rows to the accumulator tile
-    auto flush = [&](int cnt) {
-        const bool ok = r < cnt;
-        const int row = ok ? hq[r] : 0;
-        const double* fsrc = F + (int64_t)row * k + 16 * hh;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int c0 = 16 * hh + 2 * q;
-            const double2 v = (ok && c0 < k) ? *reinterpret_cast<const double2*>(fsrc + 2 * q) : make_double2(0.0, 0.0);
-            *reinterpret_cast<double2*>(Fst + r * FS + c0) = v;
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int nst = (cnt + 3) >> 2;
-#pragma unroll 2
-        for (int s4 = 0; s4 < nst; ++s4) {
-            const int t = 4 * s4 + kk;
-            const double f0 = Fst[t * FS + r16], f1 = Fst[t * FS + 16 + r16];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(-f0, f0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(-f0, f1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(-f1, f0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(-f1, f1, acc[1][1], 0, 0, 0);
-        }
-        __builtin_amdgcn_wave_barrier();
-    };
-    // append the rows flagged in `held` (one per lane, row index `row`) to the queue; flush while >= 32 are waiting
-    auto push = [&](bool held, int row) {
-        const unsigned long long m = __ballot(held);
-        if (m == 0ull) return;
-        const int rank = __popcll(m & ((1ull << lane) - 1ull));
-        if (held) hq[qn + rank] = row;
-        qn += __popcll(m);
-        __builtin_amdgcn_wave_barrier();
-        while (qn >= 32) {
-            flush(32);
-            const int rest = qn - 32;
-            const int moved = lane < rest ? hq[32 + lane] : 0;      // rest <= 63
-            __builtin_amdgcn_wave_barrier();
-            if (lane < rest) hq[lane] = moved;
-            __builtin_amdgcn_wave_barrier();
-            qn = rest;
-        }
-    };
-    double b = 0.0;
-    for (int t0 = colptr[j]; t0 < colptr[j + 1]; t0 += 64) {       // 64 nonzeros per step: lane-parallel hashing
-        const int t = t0 + lane;
-        const bool valid = t < colptr[j + 1];
-        const int row = valid ? rowidx[t] : 0;
-        const double a = valid ? vals[t] : 0.0;
-        const bool held = valid && (transposed ? cv_hash_dev(seed, col, (unsigned)row) : cv_hash_dev(seed, (unsigned)row, col)) < threshold;
-        // train right-hand side: lane = feature again, one nonzero at a time
-        unsigned long long tm = __ballot(valid && !held);
-        while (tm) {
-            const int bit = __builtin_ctzll(tm);
-            tm &= tm - 1;
-            const int rw = __builtin_amdgcn_readlane(row, bit);
-            const double av = lane_value(a, bit);
-            if (fok) b = tfma(av, F[(int64_t)rw * k + lane], b);
-        }
-        if (mask_zeros) push(held, row);
-    }
-    if (!mask_zeros) {
-        for (int r0 = 0; r0 < nrows; r0 += 64) {
-            const int rw = r0 + lane;
-            const bool held = rw < nrows &&
-                (transposed ? cv_hash_dev(seed, col, (unsigned)rw) : cv_hash_dev(seed, (unsigned)rw, col)) < threshold;
-            push(held, rw);
-        }
-    }
-    if (qn > 0) flush(qn);
-    // park G_local in LDS ([c][r]; symmetric)
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) Gl[(16 * ti + kk + 4 * v) * KP + 16 * tj + r16] = acc[ti][tj][v];
-    __builtin_amdgcn_wave_barrier();
-    double x = fok ? X[j * (int64_t)k + lane] : 0.0;
-    if (solver_mode == 1) {
-        if (l1 > 0.0 && fok) b -= l1;
-        for (int c = 0; c < KP; ++c) {
-            double s = Gl[c * KP + ll];
-            for (int p = 0; p < c; ++p) s -= Gl[p * KP + ll] * Gl[p * KP + c];
-            double dcc = __shfl(s, c, 64);
-            if (!(dcc > 0.0)) dcc = tabs(dcc) + 1e-30;
-            const double lcc = sqrt(dcc);
-            if (lin) Gl[c * KP + lane] = lane == c ? lcc : (lane > c ? s / lcc : 0.0);
-            RK_WAVE_SYNC();
-        }
-        double y = b;
-        for (int i = 0; i < k; ++i) {
-            const double yi = __shfl(y, i, 64) / Gl[i * KP + i];
-            if (lane == i) y = yi;
-            else if (lane > i) y -= Gl[i * KP + ll] * yi;
-        }
-        for (int i = k - 1; i >= 0; --i) {
-            const double xi = __shfl(y, i, 64) / Gl[i * KP + i];
-            if (lane == i) y = xi;
-            else if (lane < i) y -= Gl[ll * KP + i] * xi;
-        }
-        x = y;
-        if (nonneg) x = x > 0.0 ? x : 0.0;
-    } else {
-        const double gd = Gl[ll * KP + ll];
-        cd_static_sweeps<double, KP>(b, x, gd, fok, l1, nonneg, maxit, [&](auto IC) { return Gl[decltype(IC)::value * KP + ll]; });
-    }
-    if (fok) X[j * (int64_t)k + lane] = x;
-}
-
-// Squared error and count over the held-out entries (fit_cv.hpp:1444-1494), one wavefront per column of A.
-// out partials: [block] = {sum of squared errors (fp64), count}
-template <class T>
-__global__ __launch_bounds__(256) void cv_test_error_kernel(
-    const int* __restrict__ colptr, const int* __restrict__ rowidx, const T* __restrict__ vals, int64_t ncols, int nrows,
-    const T* __restrict__ W_T, const T* __restrict__ d, const T* __restrict__ H, int k, unsigned long long seed,
-    unsigned long long threshold, int mask_zeros, double* __restrict__ partial_sq, unsigned long long* __restrict__ partial_n) {
-    __shared__ double shs[4];
-    __shared__ unsigned long long shn[4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t j = (int64_t)blockIdx.x * 4 + wave;
-    double acc = 0.0;
-    unsigned long long cnt = 0;
-    if (j < ncols) {
-        const bool fok = lane < k;
-        // lane f holds d_f * H(f, j) for features f and f + 64 (k <= 128); a held-out entry costs one gather of W_T(row, :) and a
-        // wave reduction
-        const bool fok2 = lane + 64 < k;
-        const T hd = fok ? H[j * (int64_t)k + lane] * d[lane] : T(0);
-        const T hd2 = fok2 ? H[j * (int64_t)k + lane + 64] * d[lane + 64] : T(0);
-        const unsigned col = (unsigned)j;
-        if (mask_zeros) {
-            for (int t = colptr[j]; t < colptr[j + 1]; ++t) {
-                const int row = rowidx[t];
-                if (!(cv_hash_dev(seed, (unsigned)row, col) < threshold)) continue;
-                T p = fok ? W_T[(int64_t)row * k + lane] * hd : T(0);
-                if (fok2) p = tfma(W_T[(int64_t)row * k + lane + 64], hd2, p);
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) p += shfl_xor_t(p, off);
-                const T diff = vals[t] - p;
-                acc += static_cast<double>(diff * diff);
-                ++cnt;
-            }
-        } else {
-            int t = colptr[j];
-            const int te = colptr[j + 1];
-            for (int r0 = 0; r0 < nrows; r0 += 64) {
-                const int r = r0 + lane;
-                const bool held = r < nrows && cv_hash_dev(seed, (unsigned)r, col) < threshold;
-                unsigned long long m = __ballot(held);
-                while (m) {
-                    const int bit = __builtin_ctzll(m);
-                    m &= m - 1;
-                    const int row = r0 + bit;
-                    while (t < te && rowidx[t] < row) ++t;
-                    const T actual = (t < te && rowidx[t] == row) ? vals[t] : T(0);
-                    T p = fok ? W_T[(int64_t)row * k + lane] * hd : T(0);
-                    if (fok2) p = tfma(W_T[(int64_t)row * k + lane + 64], hd2, p);
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1) p += shfl_xor_t(p, off);
-                    const T diff = actual - p;
-                    acc += static_cast<double>(diff * diff);
-                    ++cnt;
-                }
-            }
-        }
-    }
-    if (lane == 0) { shs[wave] = acc; shn[wave] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial_sq[blockIdx.x] = shs[0] + shs[1] + shs[2] + shs[3];
-        partial_n[blockIdx.x] = shn[0] + shn[1] + shn[2] + shn[3];
-    }
-}
-
-// ---------------------------------------------------------------------------
 // k x k feature layer (reference features/L21.hpp:38-51, features/angular.hpp:67-103)
 // ---------------------------------------------------------------------------
 // L21: G(i,i) += lambda / ||factor.row(i)||_2 for rows with norm > 1e-10; sumsq[i] = sum_j X(i,j)^2
@@ -2320,6 +1673,65 @@ __global__ __launch_bounds__(256) void angular_apply_kernel(T* __restrict__ X, i
     }
 }
 
+// ---------------------------------------------------------------------------
+// One wavefront per column, lane r = feature r (k <= KP, KP in {32, 64}), the column's own Gram as a KP x KP tile [c][r] in LDS:
+// the pieces shared by masked_solve_kernel below, the cross-validation solves (kernels_cv.hip.h) and cv_irls_solve_kernel
+// (kernels_cv_irls.hip.h).  With KP = 32 the upper half of the wave only takes part in the shuffles.
+// ---------------------------------------------------------------------------
+// tile <- G (k x k, column-major) padded with identity
+template <class T, int KP>
+__device__ __forceinline__ void wave_gram_load(T* Gl, const T* __restrict__ Gfull, int k, int lane) {
+    const bool fok = lane < k;
+    for (int c = 0; c < KP; ++c) {
+        T v = (fok && c < k) ? Gfull[(int64_t)c * k + lane] : (c == lane ? T(1) : T(0));
+        if (lane < KP) Gl[c * KP + lane] = v;
+    }
+}
+// tile -= f f^T, lane r holding f_r (0 beyond k)
+template <class T, int KP>
+__device__ __forceinline__ void wave_gram_downdate(T* Gl, T fr, int k, int lane) {
+    for (int c = 0; c < k; ++c) {
+        const T fc = __shfl(fr, c, 64);
+        if (lane < KP) Gl[c * KP + lane] -= fr * fc;
+    }
+}
+// x = clip(G^-1 b): in-LDS Cholesky (left-looking, the factor overwrites the tile), then forward/back substitution
+template <class T, int KP>
+__device__ __forceinline__ T wave_chol_clip(T* Gl, T b, int k, int nonneg, int lane) {
+    const bool lin = lane < KP;
+    const int ll = lin ? lane : 0;
+    for (int c = 0; c < KP; ++c) {
+        T s = Gl[c * KP + ll];
+        for (int p = 0; p < c; ++p) s -= Gl[p * KP + ll] * Gl[p * KP + c];
+        T dcc = __shfl(s, c, 64);
+        if (!(dcc > T(0))) dcc = tabs(dcc) + T(1e-30);
+        const T lcc = sqrt(dcc);
+        if (lin) Gl[c * KP + lane] = lane == c ? lcc : (lane > c ? s / lcc : T(0));
+        RK_WAVE_SYNC();
+    }
+    T y = b;
+    for (int i = 0; i < k; ++i) {   // forward: y_i = (b_i - sum_{p<i} L_ip y_p) / L_ii
+        const T yi = __shfl(y, i, 64) / Gl[i * KP + i];
+        if (lane == i) y = yi;
+        else if (lane > i) y -= Gl[i * KP + ll] * yi;
+    }
+    for (int i = k - 1; i >= 0; --i) {  // backward: x_i = (y_i - sum_{p>i} L_pi x_p) / L_ii
+        const T xi = __shfl(y, i, 64) / Gl[i * KP + i];
+        if (lane == i) y = xi;
+        else if (lane < i) y -= Gl[ll * KP + i] * xi;
+    }
+    if (nonneg) y = y > T(0) ? y : T(0);
+    return y;
+}
+
+// ---------------------------------------------------------------------------
+// Explicit-mask per-column NNLS (reference nmf/masked_nnls.hpp:96-154 / 177-242).
+// One wavefront per column; lane r owns feature r (k <= 64).  The per-column Gram
+//   G_loc = G_full - sum_{r in masked(j)} f_r f_r^T  (+ l2 on the diagonal)
+// lives in LDS (one k x k tile per wave); b skips masked rows of A (two-pointer merge: both row
+// lists are sorted).  Solve: CD exactly as the wave variant above (sequential visit, in-order), or
+// in-LDS Cholesky + clip for solver_mode 1.
+// ---------------------------------------------------------------------------
 template <class T, int KP>   // KP in {32, 64}: features padded to KP (k <= KP), lane r = feature r
 __global__ __launch_bounds__(256) void masked_solve_kernel(
     const int* __restrict__ colptr, const int* __restrict__ rowidx, const T* __restrict__ vals,
@@ -2332,13 +1744,8 @@ __global__ __launch_bounds__(256) void masked_solve_kernel(
     const int64_t j = (int64_t)blockIdx.x * 4 + wave;
     if (j >= ncols) return;
     const bool fok = lane < k;
-    const bool lin = lane < KP;                 // KP = 32: the upper half of the wave only takes part in shuffles
-    const int ll = lin ? lane : 0;
-    // G_loc = G_full (padded with identity)
-    for (int c = 0; c < KP; ++c) {
-        T v = (fok && c < k) ? Gfull[(int64_t)c * k + lane] : (c == lane ? T(1) : T(0));
-        if (lin) Gl[c * KP + lane] = v;
-    }
+    const int ll = lane < KP ? lane : 0;
+    wave_gram_load<T, KP>(Gl, Gfull, k, lane);
     // b over unmasked nonzeros; delta-G over ALL masked rows
     T b = T(0);
     const int as = colptr[j], ae = colptr[j + 1];
@@ -2353,38 +1760,13 @@ __global__ __launch_bounds__(256) void masked_solve_kernel(
     for (int t = mask_p[j]; t < me; ++t) {
         const int row = mask_i[t];
         const T fr = fok ? F[(int64_t)row * k + lane] : T(0);
-        for (int c = 0; c < k; ++c) {
-            const T fc = __shfl(fr, c, 64);
-            if (lin) Gl[c * KP + lane] -= fr * fc;
-        }
+        wave_gram_downdate<T, KP>(Gl, fr, k, lane);
     }
     if (fok) { b -= l1; Gl[lane * KP + lane] += l2; }   // fok implies lane < KP
     RK_WAVE_SYNC();
     T x = (warm && fok) ? X[j * (int64_t)k + lane] : T(0);
     if (solver_mode == 1) {
-        // in-LDS Cholesky (left-looking) then forward/back substitution; x = clip(G_loc^-1 b)
-        for (int c = 0; c < KP; ++c) {
-            T s = Gl[c * KP + ll];
-            for (int p = 0; p < c; ++p) s -= Gl[p * KP + ll] * Gl[p * KP + c];
-            T dcc = __shfl(s, c, 64);
-            if (!(dcc > T(0))) dcc = tabs(dcc) + T(1e-30);
-            const T lcc = sqrt(dcc);
-            if (lin) Gl[c * KP + lane] = lane == c ? lcc : (lane > c ? s / lcc : T(0));
-            RK_WAVE_SYNC();
-        }
-        T y = b;
-        for (int i = 0; i < k; ++i) {   // forward: y_i = (b_i - sum_{p<i} L_ip y_p) / L_ii
-            const T yi = __shfl(y, i, 64) / Gl[i * KP + i];
-            if (lane == i) y = yi;
-            else if (lane > i) y -= Gl[i * KP + ll] * yi;
-        }
-        for (int i = k - 1; i >= 0; --i) {  // backward: x_i = (y_i - sum_{p>i} L_pi x_p) / L_ii
-            const T xi = __shfl(y, i, 64) / Gl[i * KP + i];
-            if (lane == i) y = xi;
-            else if (lane < i) y -= Gl[ll * KP + i] * xi;
-        }
-        x = y;
-        if (nonneg) x = x > T(0) ? x : T(0);
+        x = wave_chol_clip<T, KP>(Gl, b, k, nonneg, lane);
     } else {
         // cd_nnls_col_fixed with the relative-change stop, static coordinate sweeps (cd_static_sweeps_tol above)
         const T gd = Gl[ll * KP + ll];

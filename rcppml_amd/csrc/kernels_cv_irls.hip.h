@@ -18,7 +18,7 @@
 // Correct first: the rank-1 accumulation runs on the vector ALU (k LDS read-modify-writes per training entry).
 // ============================================================================
 #pragma once
-#include "kernels.hip.h"
+#include "kernels_cv.hip.h"
 #include "kernels_irls.hip.h"
 
 namespace rk {
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void cv_irls_solve_kernel(
     T x = fok ? X[j * (int64_t)k + lane] : T(0);
     auto held_row = [&](int row) {          // excluded rows: held out, or user-masked (fit_cv.hpp:491-501 -> cv_detail.hpp:116-117)
         if (cv_user_masked(mp, mi, j, row)) return true;
-        return (transposed ? cv_hash_dev(seed, col, (unsigned)row) : cv_hash_dev(seed, (unsigned)row, col)) < threshold;
+        return cv_held(seed, transposed, col, (unsigned)row, threshold);
     };
     for (int it = 0; it < irls_max_iter; ++it) {
         for (int c = 0; c < KP; ++c)
@@ -169,28 +169,7 @@ __global__ __launch_bounds__(256) void cv_irls_solve_kernel(
         const T xo = x;
         if (solver_mode == 1) {
             if (l1 > T(0) && fok) b -= l1;
-            for (int c = 0; c < KP; ++c) {
-                T s = Gl[c * KP + ll];
-                for (int p = 0; p < c; ++p) s -= Gl[p * KP + ll] * Gl[p * KP + c];
-                T dcc = __shfl(s, c, 64);
-                if (!(dcc > T(0))) dcc = tabs(dcc) + T(1e-30);
-                const T lcc = sqrt(dcc);
-                if (lin) Gl[c * KP + lane] = lane == c ? lcc : (lane > c ? s / lcc : T(0));
-                RK_WAVE_SYNC();
-            }
-            T y = fok ? b : T(0);
-            for (int i = 0; i < k; ++i) {
-                const T yi = __shfl(y, i, 64) / Gl[i * KP + i];
-                if (lane == i) y = yi;
-                else if (lane > i) y -= Gl[i * KP + ll] * yi;
-            }
-            for (int i = k - 1; i >= 0; --i) {
-                const T xi = __shfl(y, i, 64) / Gl[i * KP + i];
-                if (lane == i) y = xi;
-                else if (lane < i) y -= Gl[ll * KP + i] * xi;
-            }
-            x = y;
-            if (nonneg) x = x > T(0) ? x : T(0);
+            x = wave_chol_clip<T, KP>(Gl, fok ? b : T(0), k, nonneg, lane);
             if (!fok) x = T(0);
         } else {
             const T gd = Gl[ll * KP + ll];
@@ -235,7 +214,7 @@ __global__ __launch_bounds__(256) void cv_irls_loss_kernel(
             for (int c = 0; c < k; ++c) pred = tfma(wr[c] * dsh[c], hs[wave][c], pred);
             const T th = (loss_type == 4 && theta_row) ? theta_row[row] : T(0);
             const double lv = static_cast<double>(cv_loss_term_dev<T>(loss_type, a, pred, th, power));
-            if (cv_hash_dev(seed, (unsigned)row, (unsigned)j) < threshold) { te += lv; ++nte; } else { tr += lv; ++ntr; }
+            if (cv_held(seed, 0, (unsigned)j, (unsigned)row, threshold)) { te += lv; ++nte; } else { tr += lv; ++ntr; }
         };
         if (mask_zeros) {
             for (int t = as + lane; t < ae; t += 64) term(rowidx[t], vals[t]);
@@ -301,7 +280,7 @@ __global__ __launch_bounds__(256) void cv_gp_theta_rows_kernel(
     double sum_y = 0.0, n_nz = 0.0;
     for (int t = ts + lane; t < te; t += 64) {
         const int col = ti[t];
-        if (cv_hash_dev(seed, (unsigned)i, (unsigned)col) < threshold) { s_cache[t] = T(-1); continue; }     // held out: not a training entry
+        if (cv_held(seed, 1, (unsigned)i, (unsigned)col, threshold)) { s_cache[t] = T(-1); continue; }     // held out: not a training entry
         const T* hr = H + (int64_t)col * k;
         T dot = T(0);
         for (int c = 0; c < k; ++c) dot = tfma(wds[wave][c], hr[c], dot);
@@ -317,7 +296,7 @@ __global__ __launch_bounds__(256) void cv_gp_theta_rows_kernel(
     double held_s = 0.0;
     for (int64_t j0 = 0; j0 < n; j0 += 64) {
         const int64_t jj = j0 + lane;
-        if (jj < n && cv_hash_dev(seed, (unsigned)i, (unsigned)jj) < threshold) {
+        if (jj < n && cv_held(seed, 1, (unsigned)i, (unsigned)jj, threshold)) {
             const T* hr = H + jj * k;
             T dot = T(0);
             for (int c = 0; c < k; ++c) dot = tfma(wds[wave][c], hr[c], dot);

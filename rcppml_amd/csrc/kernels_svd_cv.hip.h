@@ -14,7 +14,7 @@
 //                  host re-adds them in block order.
 // One wavefront walks one column, 64 entries (sparse) or 64 rows (dense) per step; no float atomics anywhere.
 #pragma once
-#include "kernels.hip.h"
+#include "kernels_cv.hip.h"
 #include "kernels_svd.hip.h"
 
 namespace rsv {

@@ -15,7 +15,7 @@
 // 66-85,101-292,304-405; nmf/masked_nnls.hpp; primitives/cpu/nnls_batch.hpp:70-132 (cd_nnls_col_fixed); cholesky_clip.
 // ============================================================================
 #pragma once
-#include "kernels.hip.h"
+#include "kernels_cv.hip.h"
 #include "kernels_irls.hip.h"
 #include "kernels_cv_irls.hip.h"
 
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(64) void wide_cv_solve_kernel(
     const int lane = wc.lane;
     const unsigned col = (unsigned)j;
     auto held_row = [&](int row) {
-        return (transposed ? cv_hash_dev(seed, col, (unsigned)row) : cv_hash_dev(seed, (unsigned)row, col)) < threshold;
+        return cv_held(seed, transposed, col, (unsigned)row, threshold);
     };
     wc.set_base(Gfull, T(0));
     T b[2] = {T(0), T(0)};
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(64) void wide_cv_irls_solve_kernel(
     const int ts = colptr[j], te = colptr[j + 1];
     auto held_row = [&](int row) {          // excluded rows: held out, or user-masked (fit_cv.hpp:491-501 -> cv_detail.hpp:116-117)
         if (cv_user_masked(mp, mi, j, row)) return true;
-        return (transposed ? cv_hash_dev(seed, col, (unsigned)row) : cv_hash_dev(seed, (unsigned)row, col)) < threshold;
+        return cv_held(seed, transposed, col, (unsigned)row, threshold);
     };
     T x[2];
     wc.load_x(X, j, x);

@@ -2,7 +2,7 @@
 #include <type_traits>
 #include <cstring>
 #include "common.hip.h"
-#include "kernels.hip.h"
+#include "kernels_cv.hip.h"
 #include "kernels_wide.hip.h"
 
 using namespace rk;
@@ -16,6 +16,12 @@ void mask_params(double holdout_fraction, unsigned long long cv_seed, unsigned l
     const unsigned long long inv_prob = static_cast<unsigned long long>(1.0 / holdout_fraction);
     if (inv_prob == 0) throw std::runtime_error("cv: holdout_fraction too large");
     *threshold = 0xFFFFFFFFFFFFFFFFULL / inv_prob;
+}
+
+// RCPPML_GPU_CV_VARIANT=valu keeps the LDS read-modify-write form of the Gram correction where an MFMA form exists
+bool cv_use_mfma() {
+    static const bool on = !exp_flag("RCPPML_GPU_CV_VARIANT", "valu");
+    return on;
 }
 
 template <class T>
@@ -40,19 +46,18 @@ void cv_solve_impl(rcppml_hip_ctx* c, const int* cp, const int* ri, const T* val
         return;
     }
     const int64_t nblk = (ncols + 3) / 4;
+    // Gram correction on the matrix cores; LDS of a block: four waves of the tile's own layout
+    const bool use_mfma = cv_use_mfma();
     if constexpr (std::is_same<T, float>::value) if (!mp) {
-        // fp32, k <= 32: Gram correction on the matrix cores (RCPPML_GPU_CV_VARIANT=valu keeps the LDS read-modify-write form)
-        static int use_mfma = -1;
-        if (use_mfma < 0) use_mfma = exp_flag("RCPPML_GPU_CV_VARIANT", "valu") ? 0 : 1;
         if (use_mfma && k <= 32 && k % 4 == 0 && reinterpret_cast<uintptr_t>(F) % 16 == 0) {
-            const size_t smem = (size_t)4 * (32 * 36 + 96) * sizeof(float);
+            const size_t smem = (size_t)4 * CvTile32::wave_elems * sizeof(float);
             hipLaunchKernelGGL(cv_solve_mfma32_kernel, dim3((unsigned)nblk), dim3(256), smem, c->stream, cp, ri, vals, ncols, nrows, F, G,
                                X, k, seed, thr, mask_zeros, transposed, l1, nonneg, maxit, solver_mode);
             HIPCHK(hipGetLastError());
             return;
         }
         if (use_mfma && k <= 64 && k % 4 == 0 && reinterpret_cast<uintptr_t>(F) % 16 == 0) {      // 32 < k <= 64: 2 x 2 tiles
-            const size_t smem = (size_t)4 * (64 * 64 + 96) * sizeof(float);
+            const size_t smem = (size_t)4 * CvTile32x2::wave_elems * sizeof(float);
             static DynSmemOnce once;
             once.ensure(reinterpret_cast<const void*>(&cv_solve_mfma32x2_kernel), smem, c->device);
             hipLaunchKernelGGL(cv_solve_mfma32x2_kernel, dim3((unsigned)nblk), dim3(256), smem, c->stream, cp, ri, vals, ncols, nrows, F, G,
@@ -62,10 +67,8 @@ void cv_solve_impl(rcppml_hip_ctx* c, const int* cp, const int* ri, const T* val
         }
     }
     if constexpr (std::is_same<T, double>::value) if (!mp) {
-        static int use_mfma64 = -1;
-        if (use_mfma64 < 0) use_mfma64 = exp_flag("RCPPML_GPU_CV_VARIANT", "valu") ? 0 : 1;
-        if (use_mfma64 && k <= 32 && k % 2 == 0 && reinterpret_cast<uintptr_t>(F) % 16 == 0) {
-            const size_t smem = (size_t)4 * (32 * 34 + 48) * sizeof(double);
+        if (use_mfma && k <= 32 && k % 2 == 0 && reinterpret_cast<uintptr_t>(F) % 16 == 0) {
+            const size_t smem = (size_t)4 * CvTile64::wave_elems * sizeof(double);
             hipLaunchKernelGGL(cv_solve_mfma64_kernel, dim3((unsigned)nblk), dim3(256), smem, c->stream, cp, ri, vals, ncols, nrows, F, G,
                                X, k, seed, thr, mask_zeros, transposed, l1, nonneg, maxit, solver_mode);
             HIPCHK(hipGetLastError());
