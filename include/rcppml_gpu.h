@@ -617,7 +617,12 @@ enum { RCPPML_OPT_CD_COUNT_NOOP = 1 /* LMF kernel counts all-zero coordinate ste
        RCPPML_OPT_CD_NO_LMF = 4 /* RCPPML_CD_AUTO falls back to the 32- / 16-column MFMA kernels */,
        RCPPML_OPT_IRLS_COLUMNS_PER_WAVE = 5, /* fp32 k <= 32 IRLS half-update: 0 = by the number of columns, 1 or 4 columns per wavefront */
        RCPPML_OPT_SMALL_GIVE_UP = 6 /* test switch: the one-kernel fit's first barrier gives up at once (its abort flag is preset), as if
-                                       its workgroups had not all arrived on one XCD -- exercises the caller's restart on the multi-launch ops */ };
+                                       its workgroups had not all arrived on one XCD -- exercises the caller's restart on the multi-launch ops */,
+       RCPPML_OPT_CD_PLACED = 7 /* launch form of the fp32 k <= 64 MFMA solves: 0 = explicitly placed (one workgroup per CU, static tile
+                                   map) when there are 2 to 5 32-column tiles, or between 1 and 2 16-column tiles, per SIMD; 1 = explicitly
+                                   placed whenever those kernels run; 2 = never (one workgroup per four tiles); 3 / 4 = as 0 for the 32- /
+                                   16-column tiles only (A/B runs).  Same results bit for bit */,
+       RCPPML_OPT_CD_ASSUME_CUS = 8 /* test switch: the explicitly placed launch assumes this many CUs (> 0) instead of the device's */ };
 RCPPML_GPU_API int rcppml_hip_ctx_set_option(rcppml_hip_ctx* ctx, int option, int value);
 
 /* One-time setup of a fit, on the device.

@@ -16,6 +16,7 @@ F32, F64 = 0, 1
 CD_AUTO, CD_LANE, CD_WAVE, CD_GROUP, CD_MFMA, CD_MFMA16, CD_LMF = 0, 1, 2, 5, 6, 7, 8
 # rcppml_hip_ctx_set_option
 OPT_CD_COUNT_NOOP, OPT_CD_LMF_LANE_GROUPS, OPT_CD_LMF_WAVES_PER_SIMD, OPT_CD_NO_LMF, OPT_IRLS_COLUMNS_PER_WAVE, OPT_SMALL_GIVE_UP = 1, 2, 3, 4, 5, 6
+OPT_CD_PLACED, OPT_CD_ASSUME_CUS = 7, 8          # launch form of the 32-column MFMA solve (0 auto, 1 always placed, 2 never); test switch
 
 # Every symbol include/rcppml_gpu.h declares (tests check the library exports all of them).
 EXPORTED_SYMBOLS = [

@@ -27,6 +27,7 @@
 // ============================================================================
 #pragma once
 #include "kernels.hip.h"
+#include "cd_placement.hip.h"
 
 namespace rk {
 
@@ -86,26 +87,17 @@ __host__ __device__ constexpr size_t cd_mfma_lds_bytes(int RT) {
     return RT <= 2 ? (size_t)(16 * RT) * 64 * sizeof(float4) : ((size_t)(32 * RT) * (32 * RT) + 2 * (32 * RT)) * sizeof(float);
 }
 
-template <int RT, int CT, bool SIMPLE>   // KP = 32*RT rows (k <= KP), 32*CT columns per wave, 4 waves per block share G
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CT == 1 && RT <= 2) ? 4 : 2, 8))) void cd_mfma_kernel(const float* __restrict__ G /* k x k, as rcppml_hip_gram wrote it */,
-                                                       const float* __restrict__ B,
-                                                       float* __restrict__ X, int k, int64_t ncols, float l1_pre,
-                                                       int warm, int zero_init, float l1_cd, float l2_cd, int nonneg,
-                                                       int maxit, float tol, float ub_cd, float ub_post,
-                                                       int* __restrict__ sweeps, const int* __restrict__ order,
-                                                       unsigned long long* __restrict__ stats) {
+// The permuted operand image and the per-coordinate table are formed by every workgroup from the k x k Gram (until round 3 a
+// launch of its own: every workgroup reads the same 4 k^2 bytes either way, and the solve is two launches shorter per
+// iteration).  LDS element e <-> (pair, row tile, half, r): the layout comment above.  The caller synchronises afterwards.
+template <int RT>
+__device__ __forceinline__ void cd_mfma_fill_lds(const float* __restrict__ G /* k x k, as rcppml_hip_gram wrote it */, int k) {
     constexpr int KP = 32 * RT;
     constexpr bool PACK = RT <= 2;
-    // SIMPLE keeps the iterate NEGATED (xs = -x): the step is max(diff, -x) and v_max takes no free negation, the update is
-    // min(fma(-b, 1/G, -x), 0) with the negation folded into the fma's modifiers -- same magnitudes bit for bit, one VALU less
-    // per pair
-    constexpr float XSIGN = SIMPLE ? -1.f : 1.f;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* Gs = reinterpret_cast<float*>(smem_raw);      // !PACK: KP*KP, pair-major (layout comment above)
     float2* tab_s = reinterpret_cast<float2*>(Gs + KP * KP);   // !PACK: KP x {1/G_cc, pair coupling}
     float4* img = reinterpret_cast<float4*>(smem_raw);   // PACK: (KP/2) x 64
-    // The permuted operand image and the per-coordinate table are formed HERE from the k x k Gram (until round 3 a launch of its own: every workgroup reads the same 4 k^2 bytes either way, and the solve is two launches shorter per
-    // iteration).  LDS element e <-> (pair, row tile, half, r): the layout comment above.
     {
         auto gp = [&](int col, int row) { return (row < k && col < k) ? G[(int64_t)col * k + row] : (row == col ? 1.f : 0.f); };
         if constexpr (PACK) {
@@ -137,10 +129,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CT == 1 &&
             }
         }
     }
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+}
+
+// One tile: the 32*CT work-order slots from `base` on, solved by the calling wave against the operand image in LDS -- load B
+// and X, warm pass, sweeps, store, sweep counts, work counters.  Both launch forms below run their tiles through this body; a
+// column's arithmetic depends neither on its tile-mates nor on which wave runs the tile.
+template <int RT, int CT, bool SIMPLE>   // KP = 32*RT rows (k <= KP), 32*CT columns per wave
+__device__ __forceinline__ void cd_mfma_tile(const int64_t base, const float* __restrict__ B, float* __restrict__ X, int k, int64_t ncols,
+                                             float l1_pre, int warm, int zero_init, float l1_cd, float l2_cd, int nonneg, int maxit,
+                                             float tol, float ub_cd, float ub_post, int* __restrict__ sweeps,
+                                             const int* __restrict__ order, unsigned long long* __restrict__ stats) {
+    constexpr int KP = 32 * RT;
+    constexpr bool PACK = RT <= 2;
+    // SIMPLE keeps the iterate NEGATED (xs = -x): the step is max(diff, -x) and v_max takes no free negation, the update is
+    // min(fma(-b, 1/G, -x), 0) with the negation folded into the fma's modifiers -- same magnitudes bit for bit, one VALU less
+    // per pair
+    constexpr float XSIGN = SIMPLE ? -1.f : 1.f;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    float* Gs = reinterpret_cast<float*>(smem_raw);      // !PACK: KP*KP, pair-major (layout comment above)
+    float2* tab_s = reinterpret_cast<float2*>(Gs + KP * KP);   // !PACK: KP x {1/G_cc, pair coupling}
+    float4* img = reinterpret_cast<float4*>(smem_raw);   // PACK: (KP/2) x 64
+    const int lane = threadIdx.x & 63;
     const int half = lane >> 5, cl = lane & 31;
-    const int64_t base = ((int64_t)blockIdx.x * (blockDim.x >> 6) + wave) * (32 * CT);
     if (base >= ncols) return;
     int64_t j[CT];
     bool inb[CT];
@@ -327,6 +337,54 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CT == 1 &&
     for (int ct = 0; ct < CT; ++ct)
         if (inb[ct] && half == 0) { nsw += nsweep[ct]; ncol += 1; }
     cd_stats_add(stats, nsw, ncol);
+}
+
+// Launch form 1: one tile per wave, 4 waves per workgroup share the operand image; the dispatcher decides where tiles run.
+template <int RT, int CT, bool SIMPLE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CT == 1 && RT <= 2) ? 4 : 2, 8))) void cd_mfma_kernel(const float* __restrict__ G /* k x k, as rcppml_hip_gram wrote it */,
+                                                       const float* __restrict__ B,
+                                                       float* __restrict__ X, int k, int64_t ncols, float l1_pre,
+                                                       int warm, int zero_init, float l1_cd, float l2_cd, int nonneg,
+                                                       int maxit, float tol, float ub_cd, float ub_post,
+                                                       int* __restrict__ sweeps, const int* __restrict__ order,
+                                                       unsigned long long* __restrict__ stats) {
+    cd_mfma_fill_lds<RT>(G, k);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6;
+    const int64_t base = ((int64_t)blockIdx.x * (blockDim.x >> 6) + wave) * (32 * CT);
+    cd_mfma_tile<RT, CT, SIMPLE>(base, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps,
+                                 order, stats);
+}
+
+// Launch form 2 (k <= 64, 32-column tiles): explicitly placed.  ONE workgroup of 4 R waves per CU (the launch asks for more than
+// half of a CU's LDS, so two never share one) and one operand image per CU; wave w runs the tiles that the static map of
+// cd_placement.hip.h gives SIMD 4 b + (w & 3) in round w >> 2, so the sum of sweeps per SIMD -- what the kernel's duration is
+// made of -- no longer depends on where the dispatcher puts workgroups.  (Waves w, w + 4, w + 8, ... of a workgroup share a
+// SIMD and the four classes w & 3 sit on the four SIMDs of the CU -- read from HW_ID on MI355X for all 256 workgroups, R = 2,
+// 3, 4; which SIMD a class gets varies by workgroup.  Only the balance relies on it: any assignment of waves to SIMDs
+// computes the same numbers.)  With `unserp` the work order is the serpentine layout of rcppml_hip_order_columns and the
+// map's longest-first positions are translated.  Register budget as form 1 (<= 128 VGPRs: four waves per SIMD), whatever R
+// the launch picks.
+template <int RT, bool SIMPLE>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 8))) void cd_mfma_placed_kernel(
+    const float* __restrict__ G, const float* __restrict__ B, float* __restrict__ X, int k, int64_t ncols, float l1_pre, int warm,
+    int zero_init, float l1_cd, float l2_cd, int nonneg, int maxit, float tol, float ub_cd, float ub_post, int* __restrict__ sweeps,
+    const int* __restrict__ order, unsigned long long* __restrict__ stats, CdPlace pl, int unserp) {
+    cd_mfma_fill_lds<RT>(G, k);
+    __syncthreads();
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = 4 * (int)blockIdx.x + (w & 3), r = w >> 2;
+    const int64_t ntiles = (ncols + 31) / 32;
+    const int64_t mapped = (int64_t)pl.rounds * pl.simds;
+    int64_t p = cd_place_pos(pl, g, r);
+    int64_t e = r == pl.rounds - 1 ? cd_place_extra(pl, g) : ntiles;      // left-over tiles: the last-round wave only
+    while (p < ntiles) {
+        const int64_t t = unserp ? cd_place_unserp(p, 4, ncols) : p;
+        cd_mfma_tile<RT, 1, SIMPLE>(t * 32, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post,
+                                    sweeps, order, stats);
+        p = mapped + e;
+        e += pl.simds;
+    }
 }
 
 }  // namespace rk

@@ -23,6 +23,7 @@
 // ============================================================================
 #pragma once
 #include "kernels.hip.h"
+#include "cd_placement.hip.h"
 
 namespace rk {
 
@@ -104,20 +105,16 @@ __device__ __forceinline__ double fast_recip(double den) {
     return __builtin_fma(__builtin_fma(-den, rc, 1.0), rc, rc);
 }
 
-template <class T, int NT, bool SIMPLE>   // KP = 16*NT rows (k <= KP), 16 columns per wave, 4 waves per block share G
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= 2 ? 4 : (NT <= 4 ? 2 : 1), 8)))
-void cd_mfma64_kernel(const T* __restrict__ G /* k x k, as rcppml_hip_gram wrote it */, const T* __restrict__ B,
-                      T* __restrict__ X, int k, int64_t ncols, T l1_pre, int warm, int zero_init, T l1_cd,
-                      T l2_cd, int nonneg, int maxit, T tol, T ub_cd, T ub_post,
-                      int* __restrict__ sweeps, const int* __restrict__ order, unsigned long long* __restrict__ stats) {
+// operand image and per-coordinate table formed by every workgroup from the k x k Gram (layout comment above; until round 3 a
+// launch of its own).  The caller synchronises afterwards.
+template <class T, int NT>
+__device__ __forceinline__ void cd_mfma64_fill_lds(const T* __restrict__ G /* k x k, as rcppml_hip_gram wrote it */, int k) {
     typedef typename Vec4T<T>::type Tab4;
-    typedef typename Acc4T<T>::type Acc4;
     constexpr int KP = 16 * NT;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     T* Gs = reinterpret_cast<T*>(smem_raw);               // KP*KP, quad-major (layout comment above)
     Tab4* tab_s = reinterpret_cast<Tab4*>(Gs + KP * KP);     // KP x {1/G_cc, 3 in-quad couplings}
     [[maybe_unused]] T* gd_s = Gs + KP * KP + 4 * KP;        // fp64 only: KP x G_cc (the corrected quotient's exact residual needs it)
-    // operand image and per-coordinate table formed here from the k x k Gram (layout comment above; until round 3 a launch of its own)
     {
         constexpr bool PERM = sizeof(T) == 4;
         auto gp = [&](int col, int row) { return (row < k && col < k) ? G[(int64_t)col * k + row] : (row == col ? T(1) : T(0)); };
@@ -139,10 +136,24 @@ void cd_mfma64_kernel(const T* __restrict__ G /* k x k, as rcppml_hip_gram wrote
             if constexpr (sizeof(T) == 8) gd_s[c] = gd > T(0) ? gd : T(0);
         }
     }
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+}
+
+// One tile: the 16 work-order slots from `base` on, solved by the calling wave against the operand image in LDS -- load B and
+// X, warm pass, sweeps, store, sweep counts, work counters.  Both launch forms below run their tiles through this body.
+template <class T, int NT, bool SIMPLE>   // KP = 16*NT rows (k <= KP), 16 columns per wave
+__device__ __forceinline__ void cd_mfma64_tile(const int64_t base, const T* __restrict__ B, T* __restrict__ X, int k, int64_t ncols, T l1_pre,
+                                               int warm, int zero_init, T l1_cd, T l2_cd, int nonneg, int maxit, T tol, T ub_cd, T ub_post,
+                                               int* __restrict__ sweeps, const int* __restrict__ order,
+                                               unsigned long long* __restrict__ stats) {
+    typedef typename Vec4T<T>::type Tab4;
+    typedef typename Acc4T<T>::type Acc4;
+    constexpr int KP = 16 * NT;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    T* Gs = reinterpret_cast<T*>(smem_raw);               // KP*KP, quad-major (layout comment above)
+    Tab4* tab_s = reinterpret_cast<Tab4*>(Gs + KP * KP);     // KP x {1/G_cc, 3 in-quad couplings}
+    [[maybe_unused]] T* gd_s = Gs + KP * KP + 4 * KP;        // fp64 only: KP x G_cc (the corrected quotient's exact residual needs it)
+    const int lane = threadIdx.x & 63;
     const int g = lane >> 4, cl = lane & 15;
-    const int64_t base = ((int64_t)blockIdx.x * (blockDim.x >> 6) + wave) * 16;
     if (base >= ncols) return;
     const int64_t slot = base + cl;
     const bool inb = slot < ncols;
@@ -254,6 +265,49 @@ void cd_mfma64_kernel(const T* __restrict__ G /* k x k, as rcppml_hip_gram wrote
         if (sweeps && g == 0) sweeps[j] = nsweep;
     }
     cd_stats_add(stats, (inb && g == 0) ? nsweep : 0, (inb && g == 0) ? 1 : 0);
+}
+
+// Launch form 1: one tile per wave, 4 waves per workgroup share the operand image; the dispatcher decides where tiles run.
+template <class T, int NT, bool SIMPLE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= 2 ? 4 : (NT <= 4 ? 2 : 1), 8)))
+void cd_mfma64_kernel(const T* __restrict__ G /* k x k, as rcppml_hip_gram wrote it */, const T* __restrict__ B,
+                      T* __restrict__ X, int k, int64_t ncols, T l1_pre, int warm, int zero_init, T l1_cd,
+                      T l2_cd, int nonneg, int maxit, T tol, T ub_cd, T ub_post,
+                      int* __restrict__ sweeps, const int* __restrict__ order, unsigned long long* __restrict__ stats) {
+    cd_mfma64_fill_lds<T, NT>(G, k);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6;
+    const int64_t base = ((int64_t)blockIdx.x * (blockDim.x >> 6) + wave) * 16;
+    cd_mfma64_tile<T, NT, SIMPLE>(base, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order,
+                                  stats);
+}
+
+// Launch form 2 (fp32, k <= 64; between one and two tiles per SIMD): explicitly placed, as cd_mfma_placed_kernel
+// (kernels_cd_mfma.hip.h) -- one workgroup of 4 R waves per CU, the static map of cd_placement.hip.h.  With R = 2 and the second
+// round dealt in descending SIMD order, the first `SIMDs` tiles of the longest-first order get a SIMD each and the surplus
+// (shortest) tiles become second waves on the SIMDs that hold the shortest first-round tiles, never beside the longest: this
+// kernel lasts as long as its longest lone chain, and a second wave on that chain's SIMD takes issue slots from it.
+template <int NT, bool SIMPLE>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NT <= 2 ? 4 : 2, 8)))
+void cd_mfma64_placed_kernel(const float* __restrict__ G, const float* __restrict__ B, float* __restrict__ X, int k, int64_t ncols,
+                             float l1_pre, int warm, int zero_init, float l1_cd, float l2_cd, int nonneg, int maxit, float tol, float ub_cd,
+                             float ub_post, int* __restrict__ sweeps, const int* __restrict__ order, unsigned long long* __restrict__ stats,
+                             CdPlace pl, int unserp) {
+    cd_mfma64_fill_lds<float, NT>(G, k);
+    __syncthreads();
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int gs = 4 * (int)blockIdx.x + (w & 3), r = w >> 2;
+    const int64_t ntiles = (ncols + 15) / 16;
+    const int64_t mapped = (int64_t)pl.rounds * pl.simds;
+    int64_t p = cd_place_pos(pl, gs, r);
+    int64_t e = r == pl.rounds - 1 ? cd_place_extra(pl, gs) : ntiles;      // left-over tiles: the last-round wave only
+    while (p < ntiles) {
+        const int64_t t = unserp ? cd_place_unserp(p, 8, ncols) : p;
+        cd_mfma64_tile<float, NT, SIMPLE>(t * 16, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post,
+                                          sweeps, order, stats);
+        p = mapped + e;
+        e += pl.simds;
+    }
 }
 
 }  // namespace rk

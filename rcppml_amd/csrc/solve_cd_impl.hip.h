@@ -57,11 +57,55 @@ static void cd_group_launch(rcppml_hip_ctx* c, const T* Gp, const T* invd, const
     HIPCHK(hipGetLastError());
 }
 
+// MFMA variant, explicitly placed launch (fp32, k <= 64, 32-column tiles): one workgroup of 4 R waves per CU, the tiles dealt to
+// SIMDs by the static map of cd_placement.hip.h.  R = tiles per SIMD (rounded down, 1..4); the workgroup asks for more than half
+// of a CU's LDS so that no two share a CU.  `order` is taken to be the layout rcppml_hip_order_columns writes.
+template <int RT>
+static void cd_mfma_placed_launch(rcppml_hip_ctx* c, int cus, const float* G, const float* B, float* X, int k, int64_t ncols,
+                                  float l1_pre, int warm, int zero_init, float l1_cd, float l2_cd, int nonneg, int maxit, float tol,
+                                  float ub_cd, float ub_post, int* sweeps, const int* order) {
+    const int64_t ntiles = (ncols + 31) / 32;
+    CdPlace pl;
+    pl.simds = 4 * cus;
+    const int64_t per = ntiles / pl.simds;
+    pl.rounds = per < 1 ? 1 : (per > 4 ? 4 : (int)per);
+    pl.desc = CD_PLACE_DESC;
+    pl.extra_top = CD_PLACE_EXTRA_TOP;
+    size_t smem = cd_mfma_lds_bytes(RT);
+    const size_t alone = (size_t)160 * 1024 / 2 + 1024;
+    if (smem < alone) smem = alone;
+    const bool simple = nonneg && ub_cd <= 0.f && l1_cd == 0.f && l2_cd == 0.f;
+    static DynSmemOnce once_simple, once_general;
+    if (simple) once_simple.ensure(reinterpret_cast<const void*>(&cd_mfma_placed_kernel<RT, true>), smem, c->device);
+    else once_general.ensure(reinterpret_cast<const void*>(&cd_mfma_placed_kernel<RT, false>), smem, c->device);
+    const dim3 grid((unsigned)cus), block(256u * (unsigned)pl.rounds);
+    if (simple)
+        hipLaunchKernelGGL((cd_mfma_placed_kernel<RT, true>), grid, block, smem, c->stream, G, B, X, k, ncols, l1_pre, warm, zero_init,
+                           l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats, pl, order ? 1 : 0);
+    else
+        hipLaunchKernelGGL((cd_mfma_placed_kernel<RT, false>), grid, block, smem, c->stream, G, B, X, k, ncols, l1_pre, warm, zero_init,
+                           l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats, pl, order ? 1 : 0);
+    HIPCHK(hipGetLastError());
+}
+
 // MFMA variant (fp32, k <= 128): rank-1 residual updates on the matrix cores, 32*CT columns per wave.
 template <int RT, int CT>
 static void cd_mfma_launch(rcppml_hip_ctx* c, const float* G, const float* /*unused*/, const float* B, float* X, int k,
                            int64_t ncols, float l1_pre, int warm, int zero_init, float l1_cd, float l2_cd, int nonneg,
                            int maxit, float tol, float ub_cd, float ub_post, int* sweeps, const int* order) {
+    // k <= 64: with 2 to 5 tiles per SIMD the explicitly placed form decides which SIMD runs which tiles (RCPPML_OPT_CD_PLACED:
+    // 1 = always, 2 = never, 3 / 4 = only this / only the 16-column form; RCPPML_GPU_CD_PLACED overrides in experiment builds)
+    if constexpr (RT <= 2 && CT == 1) {
+        int mode = c->opt_cd_placed;
+        if (const char* e = exp_env("RCPPML_GPU_CD_PLACED")) mode = atoi(e);
+        const int cus = c->opt_cd_assume_cus > 0 ? c->opt_cd_assume_cus : (c->num_cu > 0 ? c->num_cu : 256);
+        const int64_t per = ((ncols + 31) / 32) / ((int64_t)4 * cus);
+        if (mode == 1 || ((mode == 0 || mode == 3) && per >= 2 && per < 5)) {
+            cd_mfma_placed_launch<RT>(c, cus, G, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post,
+                                      sweeps, order);
+            return;
+        }
+    }
     size_t smem = cd_mfma_lds_bytes(RT);          // operand image of the k x k Gram, KP = 32 RT rows
     const int64_t per_block = 4 * 32 * CT;          // 4 waves per block
     const int64_t nblk = (ncols + per_block - 1) / per_block;
@@ -105,9 +149,39 @@ static void cd_mfma64_launch(rcppml_hip_ctx* c, const T* G, const T* /*unused*/,
                              int64_t ncols, T l1_pre, int warm, int zero_init, T l1_cd, T l2_cd, int nonneg,
                              int maxit, T tol, T ub_cd, T ub_post, int* sweeps, const int* order) {
     constexpr int KP = 16 * NT;
+    const bool simple = nonneg && ub_cd <= T(0) && l1_cd == T(0) && l2_cd == T(0);
+    // fp32, k <= 64, between one and two tiles per SIMD: the explicitly placed form (one workgroup of two rounds of waves per
+    // CU; RCPPML_OPT_CD_PLACED / RCPPML_GPU_CD_PLACED as for the 32-column tiles)
+    if constexpr (std::is_same<T, float>::value && NT <= 4) {
+        int mode = c->opt_cd_placed;
+        if (const char* e = exp_env("RCPPML_GPU_CD_PLACED")) mode = atoi(e);
+        const int cus = c->opt_cd_assume_cus > 0 ? c->opt_cd_assume_cus : (c->num_cu > 0 ? c->num_cu : 256);
+        const int64_t ntiles = (ncols + 15) / 16, simds = (int64_t)4 * cus;
+        if (mode == 1 || ((mode == 0 || mode == 4) && ntiles > simds && ntiles < 2 * simds)) {
+            CdPlace pl;
+            pl.simds = (int)simds;
+            pl.rounds = ntiles > simds ? 2 : 1;
+            pl.desc = CD_PLACE_DESC;
+            pl.extra_top = CD_PLACE_EXTRA_TOP;
+            size_t smem = ((size_t)KP * KP + 4 * KP) * sizeof(float);
+            const size_t alone = (size_t)160 * 1024 / 2 + 1024;      // more than half of a CU's LDS: no two workgroups share a CU
+            if (smem < alone) smem = alone;
+            static DynSmemOnce once_simple, once_general;
+            if (simple) once_simple.ensure(reinterpret_cast<const void*>(&cd_mfma64_placed_kernel<NT, true>), smem, c->device);
+            else once_general.ensure(reinterpret_cast<const void*>(&cd_mfma64_placed_kernel<NT, false>), smem, c->device);
+            const dim3 grid((unsigned)cus), block(256u * (unsigned)pl.rounds);
+            if (simple)
+                hipLaunchKernelGGL((cd_mfma64_placed_kernel<NT, true>), grid, block, smem, c->stream, G, B, X, k, ncols, l1_pre, warm, zero_init,
+                                   l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats, pl, order ? 1 : 0);
+            else
+                hipLaunchKernelGGL((cd_mfma64_placed_kernel<NT, false>), grid, block, smem, c->stream, G, B, X, k, ncols, l1_pre, warm, zero_init,
+                                   l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats, pl, order ? 1 : 0);
+            HIPCHK(hipGetLastError());
+            return;
+        }
+    }
     const size_t smem = ((size_t)KP * KP + 4 * KP + (sizeof(T) == 8 ? KP : 0)) * sizeof(T);      // fp64: + the diagonal itself
     const int64_t nblk = (ncols + 63) / 64;          // 4 waves x 16 columns per block
-    const bool simple = nonneg && ub_cd <= T(0) && l1_cd == T(0) && l2_cd == T(0);
     static DynSmemOnce once_simple, once_general;    // fp64 above k = 64: the LDS copy of G passes 64 KiB (128 KiB at KP = 128)
     if (simple) once_simple.ensure(reinterpret_cast<const void*>(&cd_mfma64_kernel<T, NT, true>), smem, c->device);
     else once_general.ensure(reinterpret_cast<const void*>(&cd_mfma64_kernel<T, NT, false>), smem, c->device);
