@@ -378,6 +378,40 @@ RCPPML_GPU_API void rcppml_gpu_svd_cv_dense_ex(const double* A_data, int* m, int
         int* out_n_masked, int* out_iters_per_factor, double* out_frobenius_norm_sq, double* out_row_means,
         double* out_wall_time_ms, int* out_status);
 
+/* Constrained block SVD, Krylov-Seeded Projected Refinement (rcppml_amd/csrc/ops_svd.hip, kernels_svd_krylov.hip.h).  BUILD-DEFINED:
+ * the reference runs this as algorithm 4 with element constraints (svd/krylov.hpp:262-796), which the four rcppml_gpu_svd_pca_*
+ * entries still refuse.  Scope: L1, L2, nonneg and upper bound on either side, centering, FACTOR convergence.
+ *   seed      V0 = NULL: Phase 1, the Lanczos of rcppml_gpu_svd_pca_* (algorithm 2, *max_iter 0, the caller's *tol, *center, *seed, no
+ *             constraints), and k_actual is what it selected.  Else V0 is the n x *k_max column-major seed and k_actual = *k_max.  Only
+ *             V of a seed is read: the first W-update overwrites W and d.
+ *   pass      G = V'V, diagonal += 1e-12 + *L2_u; B = A V (centred: - mu (1'V)); W = B G^-1; per column with nsq = |V_c|^2 (the Gram's
+ *             diagonal before the ridge): nsq <= 0 zeroes it (d_c = 0); else soft threshold *L1_u / (2 nsq), max(0, .) with *nonneg_u,
+ *             min(*ub_u, .) with *ub_u > 0; d_c = |column| when above 100 eps, else 0; column /= d_c where d_c > 0.  L2 is not applied
+ *             again in the projection.  Then the same for V with A'W - 1 (mu'W) and the _v values; d is overwritten.
+ *             The k x k reduction, ridge, factorisation and inverse run in fp64 in both precisions (the reference's float path adds
+ *             a ridge below fp32's epsilon).
+ *   stop      from the second pass on dW = |W - W_prev|_F / (|W_prev|_F + eps) goes to out_dw, and dW < *tol ends the loop after that
+ *             pass; at most *max_iter passes, or max(10, 2 ceil(log2 k_actual) + 3) when *max_iter <= 0.
+ *   result    with nonneg, L1 or an upper bound on either side: the factors ordered by d descending (ties by index); with L2 only:
+ *             QR of W diag(d) and of V and the SVD of R_w R_v', on the host in fp64 (signs of a column pair are not the reference's).
+ * Outputs: U (m x *k_max) and V (n x *k_max) column-major and d with the first *out_k_selected (= k_actual) columns / values written;
+ * *out_passes; out_dw (capacity: the pass limit) holds *out_passes - 1 values; out_row_means (m) when *center.
+ * Refused with *out_status = -1 (rcppml_gpu_last_error), nothing written: a null pointer (V0 aside), *precision not RCPPML_F32 /
+ * RCPPML_F64, *k_max outside [1, min(m, n)] or above 128, a negative or non-finite *tol, penalty or bound, no element constraint at all
+ * (that is Lanczos: rcppml_gpu_svd_pca_*), a non-finite V0, a malformed CSC, more device memory than is free, no device, a non-positive
+ * Cholesky pivot (the message names the pass and the update). */
+RCPPML_GPU_API void rcppml_gpu_svd_krylov_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+        int* precision, int* k_max, double* tol, int* max_iter, int* center, int* seed, double* L1_u, double* L1_v, double* L2_u,
+        double* L2_v, int* nonneg_u, int* nonneg_v, double* ub_u, double* ub_v, const double* V0, double* U, double* d, double* V,
+        int* out_k_selected, int* out_passes, double* out_dw, double* out_frobenius_norm_sq, double* out_row_means,
+        double* out_wall_time_ms, int* out_status);
+/* The same for a column-major dense matrix, read as a full CSC; with V0 = NULL its Lanczos seed is rcppml_gpu_svd_pca_dense_*'s. */
+RCPPML_GPU_API void rcppml_gpu_svd_krylov_dense_ex(const double* A_data, int* m, int* n,
+        int* precision, int* k_max, double* tol, int* max_iter, int* center, int* seed, double* L1_u, double* L1_v, double* L2_u,
+        double* L2_v, int* nonneg_u, int* nonneg_v, double* ub_u, double* ub_v, const double* V0, double* U, double* d, double* V,
+        int* out_k_selected, int* out_passes, double* out_dw, double* out_frobenius_norm_sq, double* out_row_means,
+        double* out_wall_time_ms, int* out_status);
+
 /* Embedding assessment (rcppml_amd/csrc/ops_assess.hip): the reference plugin's rcppml_gpu_assess (src/gpu_bridge_assess.cu:358-753)
  * with its 26 pointers, called by R's assess() (R/assess.R:708-769).  embedding: n x dim row-major doubles, cast to fp32.  Seeds are
  * (unsigned)*seed plus an offset (restart r: + r; silhouette: + 100; folds: + 200), each driving std::mt19937 + std::shuffle.

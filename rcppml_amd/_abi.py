@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_hip_als_small_eligible", "rcppml_hip_als_small_fit",
     "rcppml_gpu_bipartition_double", "rcppml_gpu_dclust_double", "rcppml_gpu_bipartition_ex", "rcppml_gpu_dclust_ex",
     "rcppml_gpu_svd_pca_double", "rcppml_gpu_svd_pca_float", "rcppml_gpu_svd_pca_dense_double", "rcppml_gpu_svd_pca_dense_float",
-    "rcppml_gpu_svd_cv_ex", "rcppml_gpu_svd_cv_dense_ex",
+    "rcppml_gpu_svd_cv_ex", "rcppml_gpu_svd_cv_dense_ex", "rcppml_gpu_svd_krylov_ex", "rcppml_gpu_svd_krylov_dense_ex",
     "rcppml_gpu_assess", "rcppml_gpu_assess_ex", "rcppml_gpu_knn_float", "rcppml_gpu_assess_plan",
     "rcppml_gpu_score_test_double", "rcppml_gpu_zero_inflation_double", "rcppml_gpu_dispersion_double",
     "rcppml_gpu_consensus_double", "rcppml_gpu_hclust_average_double",
@@ -961,6 +961,49 @@ def svd_cv(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=200,
                 V=b["V"][:n * kb].reshape(kb, n).T, d=b["d"], k=ksel.value, k_computed=kcomp.value, test_loss=b["test_loss"],
                 n_test=ntest.value, n_masked=nmask.value, iters=b["iters"], frob=frob.value, row_means=b["row_means"],
                 wall_ms=wall.value, buffers=b)
+
+
+def krylov_pass_limit(k, max_iter=0):
+    """krylov.hpp:428-431: the pass limit of KSPR at rank k."""
+    return int(max_iter) if max_iter > 0 else max(10, 2 * int(np.ceil(np.log2(max(k, 1)))) + 3)
+
+
+def svd_krylov(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=0, center=False, seed=0, L1=(0.0, 0.0), L2=(0.0, 0.0),
+               nonneg=(False, False), upper_bound=(0.0, 0.0), V0=None, buffers=None):
+    """The build-defined rcppml_gpu_svd_krylov_ex / rcppml_gpu_svd_krylov_dense_ex: the constrained block SVD (KSPR).  A as in
+    svd_pca; V0: n x k_max seed or None (Lanczos).  buffers: dict of preallocated outputs.  Returns dict(status, error, U (m x k_max),
+    d, V (n x k_max), k (k_actual), passes, dw (passes - 1 values), frob, row_means, wall_ms)."""
+    if dense:
+        Ad = np.asfortranarray(np.asarray(A, np.float64))
+        m, n = Ad.shape
+        head = [_np_ptr(Ad.ravel(order="F")), _ci(m), _ci(n)]
+        keep = [Ad]
+    else:
+        p, i, x, m, n = A
+        p, i, x = _csc_args(p, i, x)
+        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0])]
+        keep = [p, i, x]
+    kb = max(k_max, 1)
+    b = dict(U=np.zeros(m * kb), d=np.zeros(kb), V=np.zeros(n * kb), dw=np.zeros(krylov_pass_limit(kb, max_iter)), row_means=np.zeros(m))
+    if buffers:
+        b.update(buffers)
+    v0 = None
+    if V0 is not None:
+        v0 = np.asfortranarray(np.asarray(V0, np.float64))
+        assert v0.shape == (n, k_max), "V0 must be n x k_max"
+        keep.append(v0)
+    ksel, passes = C.c_int(0), C.c_int(0)
+    wall, frob, st = C.c_double(0.0), C.c_double(0.0), C.c_int(-99)
+    args = head + [_ci(F32 if precision == "float" else F64), _ci(k_max), _cd(tol), _ci(max_iter), _ci(int(bool(center))), _ci(seed),
+                   _cd(L1[0]), _cd(L1[1]), _cd(L2[0]), _cd(L2[1]), _ci(int(bool(nonneg[0]))), _ci(int(bool(nonneg[1]))),
+                   _cd(upper_bound[0]), _cd(upper_bound[1]), _np_ptr(v0.ravel(order="F")) if v0 is not None else None,
+                   _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]), C.byref(ksel), C.byref(passes), _np_ptr(b["dw"]), C.byref(frob),
+                   _np_ptr(b["row_means"]), C.byref(wall), C.byref(st)]
+    assert len(args) == (28 if dense else 31)
+    getattr(lib(), "rcppml_gpu_svd_krylov_dense_ex" if dense else "rcppml_gpu_svd_krylov_ex")(*args)
+    return dict(status=st.value, error=last_error() if st.value else "", U=b["U"][:m * kb].reshape(kb, m).T,
+                V=b["V"][:n * kb].reshape(kb, n).T, d=b["d"], k=ksel.value, passes=passes.value,
+                dw=b["dw"][:max(passes.value - 1, 0)], frob=frob.value, row_means=b["row_means"], wall_ms=wall.value, buffers=b)
 
 
 # ----------------------------------------------------------------------------- embedding assessment (ops_assess.hip)

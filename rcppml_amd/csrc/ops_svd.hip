@@ -21,6 +21,7 @@
 #include "entry_common.hip.h"
 #include "kernels_svd.hip.h"
 #include "kernels_svd_cv.hip.h"
+#include "kernels_svd_krylov.hip.h"
 
 #include <chrono>
 #include <climits>
@@ -45,6 +46,8 @@ struct Opts {
     // the cv entries only: hold-out fraction (0: no CV), effective mask seed, patience, mask_zeros, obs-mask pattern CSC (or null)
     double test_fraction = 0; uint64_t cv_seed = 0; int patience = 0; int mask_zeros = 0;
     const int* mp = nullptr; const int* mi = nullptr; int64_t mnnz = 0;
+    // the krylov entries only: KSPR (kspr), its pass limit (0: the default) and the n x k seed (null: Lanczos); max_iter stays 0
+    bool kspr = false; int ks_iter = 0; const double* V0 = nullptr;
     bool cv() const { return test_fraction > 0; }
     bool trains() const { return cv() || mp; }      // the products read a training copy of A
 };
@@ -57,6 +60,8 @@ struct Result {
     std::vector<double> test_loss;          // one value per computed factor (CV only)
     int k_computed = 0, n_test = 0;
     int64_t n_masked = 0;
+    int passes = 0;                         // KSPR: passes run, and the dW of each pass from the second on
+    std::vector<double> dw;
 };
 
 bool has_constraints(const Opts& o) {
@@ -142,6 +147,90 @@ void bidiag_svd(const std::vector<double>& a, const std::vector<double>& b, int 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------ host QR / SVD
+// KSPR's Phase 3 (krylov.hpp:216-247), once per call on k columns.
+// A (rows x k, column-major) = Q R by twice-applied modified Gram-Schmidt: A becomes Q, R (k x k, column-major) is upper triangular.
+// A column that vanishes leaves a zero column in Q and a zero on R's diagonal, so Q R = A still holds.
+void mgs2_qr(std::vector<double>& A, int rows, int k, std::vector<double>& Rm) {
+    Rm.assign((size_t)k * k, 0.0);
+    for (int j = 0; j < k; ++j) {
+        double* v = &A[(size_t)j * rows];
+        for (int pass = 0; pass < 2; ++pass)
+            for (int i = 0; i < j; ++i) {
+                const double* q = &A[(size_t)i * rows];
+                double r = 0;
+                for (int t = 0; t < rows; ++t) r += q[t] * v[t];
+                for (int t = 0; t < rows; ++t) v[t] -= r * q[t];
+                Rm[(size_t)j * k + i] += r;
+            }
+        double nn = 0;
+        for (int t = 0; t < rows; ++t) nn += v[t] * v[t];
+        nn = std::sqrt(nn);
+        Rm[(size_t)j * k + j] = nn;
+        for (int t = 0; t < rows; ++t) v[t] = nn > 0 ? v[t] / nn : 0.0;
+    }
+}
+// S (k x k, column-major) = Us diag(sig) Vs' by one-sided Jacobi, sig descending (ties by index)
+void jacobi_svd(std::vector<double> S, int k, std::vector<double>& Us, std::vector<double>& sig, std::vector<double>& Vs) {
+    std::vector<double> Vm((size_t)k * k, 0.0);
+    for (int c = 0; c < k; ++c) Vm[(size_t)c * k + c] = 1.0;
+    const double eps = std::numeric_limits<double>::epsilon();
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < k - 1; ++p)
+            for (int q = p + 1; q < k; ++q) {
+                double* gp = &S[(size_t)p * k];
+                double* gq = &S[(size_t)q * k];
+                double al = 0, be = 0, ga = 0;
+                for (int t = 0; t < k; ++t) { al += gp[t] * gp[t]; be += gq[t] * gq[t]; ga += gp[t] * gq[t]; }
+                if (!(std::fabs(ga) > eps * std::sqrt(al * be))) continue;
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / std::sqrt(1.0 + t * t), sn = c * t;
+                double* vp = &Vm[(size_t)p * k];
+                double* vq = &Vm[(size_t)q * k];
+                for (int r = 0; r < k; ++r) {
+                    const double a = gp[r], b = gq[r];
+                    gp[r] = c * a - sn * b; gq[r] = sn * a + c * b;
+                    const double x = vp[r], y = vq[r];
+                    vp[r] = c * x - sn * y; vq[r] = sn * x + c * y;
+                }
+            }
+        if (!rotated) break;
+    }
+    std::vector<double> nrm(k);
+    for (int c = 0; c < k; ++c) {
+        double s = 0;
+        for (int t = 0; t < k; ++t) s += S[(size_t)c * k + t] * S[(size_t)c * k + t];
+        nrm[c] = std::sqrt(s);
+    }
+    std::vector<int> ord(k);
+    std::iota(ord.begin(), ord.end(), 0);
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return nrm[x] > nrm[y]; });
+    Us.assign((size_t)k * k, 0.0); Vs.assign((size_t)k * k, 0.0); sig.assign(k, 0.0);
+    for (int c = 0; c < k; ++c) {
+        const int s = ord[c];
+        sig[c] = nrm[s];
+        for (int t = 0; t < k; ++t) {
+            Us[(size_t)c * k + t] = nrm[s] > 0 ? S[(size_t)s * k + t] / nrm[s] : 0.0;
+            Vs[(size_t)c * k + t] = Vm[(size_t)s * k + t];
+        }
+    }
+}
+// out (rows x k) = Q (rows x k) M (k x k), all column-major
+std::vector<double> times_small(const std::vector<double>& Q, int rows, int k, const std::vector<double>& M) {
+    std::vector<double> out((size_t)rows * k, 0.0);
+    for (int c = 0; c < k; ++c)
+        for (int l = 0; l < k; ++l) {
+            const double w = M[(size_t)c * k + l];
+            const double* q = &Q[(size_t)l * rows];
+            double* y = &out[(size_t)c * rows];
+            for (int t = 0; t < rows; ++t) y[t] += q[t] * w;
+        }
+    return out;
+}
+
 // ------------------------------------------------------------------------------------------------------------ engine
 template <class T> struct Engine {
     const Opts& o;
@@ -160,12 +249,14 @@ template <class T> struct Engine {
             upload_cast<T>(g.c, o.dense, (size_t)m * n, Ad, s);
             for (int j = 0; j < n; ++j)
                 for (int i = 0; i < m; ++i) mu_h[i] += o.dense[(size_t)j * m + i];
-        } else {
+        }
+        if (!o.dense || o.kspr) {           // KSPR reads a dense matrix as a full CSC (its Lanczos seed still runs the dense products)
             const size_t nz = (size_t)std::max<int64_t>(o.nnz, 1);
             upload_ints(o.p, (size_t)n + 1, Ap, s);
             upload_ints(o.i, nz, Ai, s);
             upload_cast<T>(g.c, o.x, nz, Ax, s);
-            for (int64_t e = 0; e < o.nnz; ++e) mu_h[o.i[e]] += o.x[e];
+            if (!o.dense)
+                for (int64_t e = 0; e < o.nnz; ++e) mu_h[o.i[e]] += o.x[e];
         }
         for (auto& v : mu_h) v /= (double)n;
         if (o.center) {
@@ -173,13 +264,13 @@ template <class T> struct Engine {
             upload_cast<T>(g.c, tmp.data(), (size_t)m, mu, s);
         }
         if (o.trains()) hold_out();
-        if (!o.dense) {
+        if (!o.dense || o.kspr) {
             const size_t nz = (size_t)std::max<int64_t>(o.nnz, 1);
             grow<int>(Tp, (size_t)m + 1);
             grow<int>(Ti, nz);
             grow<T>(Tx, nz);
-            OPCHK(rcppml_hip_transpose_csc(g.c, DT<T>::id, m, n, Ap.as<int>(), Ai.as<int>(), (const void*)xa(), Tp.as<int>(), Ti.as<int>(),
-                                           Tx.p));
+            OPCHK(rcppml_hip_transpose_csc(g.c, DT<T>::id, m, n, Ap.as<int>(), Ai.as<int>(),
+                                           (const void*)(o.trains() ? Xt.as<T>() : Ax.as<T>()), Tp.as<int>(), Ti.as<int>(), Tx.p));
         }
     }
     const T* mup() const { return o.center ? mu.as<T>() : nullptr; }
@@ -517,6 +608,127 @@ template <class T> struct Engine {
         HIPCHK(hipStreamSynchronize(s));
     }
 
+    // -------------------------------------------------------------------------------------------------------- KSPR
+    // krylov.hpp:303-796 for L1 / L2 / nonneg / upper bound, FACTOR convergence: a Lanczos seed (or the caller's V0), then passes of
+    // W = proj(A V (V'V + ridge)^-1), V = proj(A' W (W'W + ridge)^-1), six launches a pass (kernels_svd_krylov.hip.h) and no host
+    // synchronisation inside a group of kPoll passes; Phase 3 on the host.
+    void kspr(Result& R) {
+        std::vector<double> seed_v;
+        const double* V0 = o.V0;
+        int K = o.k;
+        R.passes = 0; R.dw.clear();
+        if (!V0) {                                              // Phase 1, krylov.hpp:311-335
+            lanczos(R);
+            K = R.k_sel;
+            R.iters.clear();
+            if (K == 0) return;
+            seed_v = R.V;
+            V0 = seed_v.data();
+        }
+        const int maxp = o.ks_iter > 0 ? o.ks_iter : std::max(10, 2 * (int)std::ceil(std::log2((double)K)) + 3);
+        const int kp = K > 32 ? WAVE : (int)std::max(1.0, std::exp2(std::ceil(std::log2((double)K))));
+        const int nhm = (m + KS_RB - 1) / KS_RB, nhn = (n + KS_RB - 1) / KS_RB, ngm = (m + KS_GR - 1) / KS_GR, ngn = (n + KS_GR - 1) / KS_GR;
+        const T eps = std::numeric_limits<T>::epsilon(), eps100 = eps * T(100);
+        const double tol = (double)(T)o.tol;
+        DevBuf bW[2], bV, bd, bPm, bPn, bPG, bGi, bLi, bns, bcs, bdw, st;
+        T* W[2] = {grow<T>(bW[0], (size_t)K * m), grow<T>(bW[1], (size_t)K * m)};
+        T* V = grow<T>(bV, (size_t)K * n);
+        T* d = grow<T>(bd, K);
+        double* Pm = grow<double>(bPm, (size_t)nhm * K);
+        double* Pn = grow<double>(bPn, (size_t)nhn * K);
+        double* PG = grow<double>(bPG, (size_t)std::max(ngm, ngn) * ks_np(K));
+        double* Gi = grow<double>(bGi, (size_t)K * K);
+        double* Li = grow<double>(bLi, (size_t)K * K);
+        double* ns = grow<double>(bns, K);
+        double* cs = grow<double>(bcs, K);
+        double* dw = grow<double>(bdw, (size_t)maxp);
+        int* S = grow<int>(st, S_WORDS);
+        const int init[S_WORDS] = {INT_MAX, 0, 0, 0, 0, 0, 0, 0};
+        std::vector<T> vt((size_t)K * n);
+        for (int c = 0; c < K; ++c)
+            for (int j = 0; j < n; ++j) vt[(size_t)j * K + c] = (T)V0[(size_t)c * n + j];
+        HIPCHK(hipMemcpyAsync(V, vt.data(), vt.size() * sizeof(T), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(S, init, sizeof(init), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(dw, 0, (size_t)maxp * sizeof(double), s));
+        const double ru = 1e-12 + o.L2_u, rv = 1e-12 + o.L2_v;
+        auto small = [&](int nb, double ridge, int it, int side, int last) {
+            hipLaunchKernelGGL(ks_small_kernel, dim3(1), dim3(WG), 0, s, (const double*)PG, nb, K, ridge, Gi, Li, ns, cs, dw, tol, (double)eps,
+                               S, it, side, last);
+        };
+        auto finish = [&](int nb, T* X, long len, const double* Pp, int nbh, int raw, const T* wt, const T* Xold, const int* stp, int it) {
+            auto* f = K <= 16 ? ks_finish_kernel<T, 1> : K <= 32 ? ks_finish_kernel<T, 2> : K <= 64 ? ks_finish_kernel<T, 4> : ks_finish_kernel<T, 8>;
+            hipLaunchKernelGGL(f, dim3(nb), dim3(WG), 0, s, X, len, K, Pp, nbh, eps100, raw, wt, Xold, d, PG, stp, it);
+        };
+        // the seed's Gram and column sums: only V of the seed is read (krylov.hpp:472-524 overwrite W and d)
+        finish(ngn, V, (long)n, nullptr, 0, 0, nullptr, nullptr, nullptr, 0);
+        small(ngn, ru, -1, 1, 0);
+        for (int done = 0; done < maxp;) {
+            const int P = std::min(kPoll, maxp - done);
+            for (int q = 0; q < P; ++q) {
+                const int it = done + q;
+                T* Wn = W[it & 1];
+                const T* Wo = it > 0 ? W[(it & 1) ^ 1] : nullptr;
+                hipLaunchKernelGGL(ks_half_kernel<T>, dim3(nhm), dim3(WG), 0, s, (const int*)Tp.as<int>(), (const int*)Ti.as<int>(),
+                                   (const T*)Tx.as<T>(), (long)m, (const T*)V, K, kp, (const double*)Gi, (const double*)ns,
+                                   (const double*)cs, mup(), o.center ? 1 : 0, (T)o.L1_u, o.nonneg_u, (T)o.ub_u, Wn, Pm, (const int*)S, it);
+                finish(ngm, Wn, (long)m, Pm, nhm, 1, mup(), Wo, S, it);
+                small(ngm, rv, it, 0, 0);
+                hipLaunchKernelGGL(ks_half_kernel<T>, dim3(nhn), dim3(WG), 0, s, (const int*)Ap.as<int>(), (const int*)Ai.as<int>(),
+                                   (const T*)Ax.as<T>(), (long)n, (const T*)Wn, K, kp, (const double*)Gi, (const double*)ns,
+                                   (const double*)cs, (const T*)nullptr, o.center ? 2 : 0, (T)o.L1_v, o.nonneg_v, (T)o.ub_v, V, Pn,
+                                   (const int*)S, it);
+                finish(ngn, V, (long)n, Pn, nhn, 1, nullptr, nullptr, S, it);
+                small(ngn, ru, it, 1, it == maxp - 1);
+            }
+            HIPCHK(hipGetLastError());
+            done += P;
+            if (read<int>(S + S_STOP, 1)[0] <= done) break;
+        }
+        const std::vector<int> sh = read<int>(S, S_WORDS);
+        if (sh[KS_ERR]) {
+            const int code = sh[KS_ERR] - 1;
+            throw std::runtime_error("KSPR: non-positive Cholesky pivot in pass " + std::to_string(code / 2 + 1) + ", " +
+                                     (code % 2 ? "V" : "W") + "-update: the Gram matrix of the fixed factor is not positive definite");
+        }
+        R.passes = sh[S_ITERS];
+        const std::vector<T> wh = read<T>(W[(R.passes - 1) & 1], (size_t)K * m), vh = read<T>(V, (size_t)K * n), dh = read<T>(d, K);
+        const std::vector<double> dwh = read<double>(dw, (size_t)maxp);
+        R.dw.assign(dwh.begin(), dwh.begin() + std::max(R.passes - 1, 0));
+        // ---- Phase 3 (krylov.hpp:742-781)
+        std::vector<double> Uc((size_t)m * K), Vc((size_t)n * K);
+        const bool hard = o.nonneg_u || o.nonneg_v || o.L1_u > 0 || o.L1_v > 0 || o.ub_u > 0 || o.ub_v > 0;
+        R.k_sel = K;
+        if (hard) {                                             // the factors as they are, by d descending (ties by index)
+            std::vector<int> ord(K);
+            std::iota(ord.begin(), ord.end(), 0);
+            std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return dh[x] > dh[y]; });
+            R.d.resize(K);
+            for (int c = 0; c < K; ++c) {
+                R.d[c] = (double)dh[ord[c]];
+                for (int i = 0; i < m; ++i) Uc[(size_t)c * m + i] = (double)wh[(size_t)i * K + ord[c]];
+                for (int j = 0; j < n; ++j) Vc[(size_t)c * n + j] = (double)vh[(size_t)j * K + ord[c]];
+            }
+            R.U.swap(Uc); R.V.swap(Vc);
+            return;
+        }
+        for (int c = 0; c < K; ++c) {                           // L2 only: QR of W diag(d) and of V, SVD of R_w R_v'
+            for (int i = 0; i < m; ++i) Uc[(size_t)c * m + i] = (double)wh[(size_t)i * K + c] * (double)dh[c];
+            for (int j = 0; j < n; ++j) Vc[(size_t)c * n + j] = (double)vh[(size_t)j * K + c];
+        }
+        std::vector<double> Rw, Rv, Sm((size_t)K * K, 0.0), Us, Vs;
+        mgs2_qr(Uc, m, K, Rw);
+        mgs2_qr(Vc, n, K, Rv);
+        for (int b = 0; b < K; ++b)
+            for (int a = 0; a < K; ++a) {
+                double acc = 0;
+                for (int l = 0; l < K; ++l) acc += Rw[(size_t)l * K + a] * Rv[(size_t)l * K + b];
+                Sm[(size_t)b * K + a] = acc;
+            }
+        jacobi_svd(Sm, K, Us, R.d, Vs);
+        R.U = times_small(Uc, m, K, Us);
+        R.V = times_small(Vc, n, K, Vs);
+    }
+
     void run(Result& R) {
         R.row_means = mu_h;
         double f = 0;
@@ -530,7 +742,8 @@ template <class T> struct Engine {
         R.frob = f;
         R.n_test = (int)n_test;
         R.n_masked = n_masked;          // masked stored entries; every mask entry on a dense input (deflation.hpp:452-487)
-        if (o.algorithm == 0) deflation(R);
+        if (o.kspr) kspr(R);
+        else if (o.algorithm == 0) deflation(R);
         else lanczos(R);
     }
 };
@@ -763,5 +976,110 @@ extern "C" void rcppml_gpu_svd_cv_dense_ex(const double* A_data, int* m, int* n,
         if (!A_data) throw std::invalid_argument("null matrix");
         o.nnz = (int64_t)o.m * o.n; o.dense = A_data;
         run_cv_entry(a, o);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------------------ krylov entries
+// Build-defined: the constrained block SVD (KSPR), which the four reference entries refuse as "algorithm 1-4 with element
+// constraints".  Every check runs before any device work, and nothing is written on a refusal.
+namespace {
+struct KsRaw {
+    int* precision; int* k_max; double* tol; int* max_iter; int *center, *seed;
+    double *L1_u, *L1_v, *L2_u, *L2_v; int *nonneg_u, *nonneg_v; double *ub_u, *ub_v;
+    const double* V0;
+    double *U, *d, *V; int *out_k_selected, *out_passes; double *out_dw, *out_frobenius_norm_sq, *out_row_means, *out_wall_time_ms;
+};
+
+Opts make_ks_opts(const KsRaw& a, const int* m, const int* n) {
+    if (!m || !n || !a.precision || !a.k_max || !a.tol || !a.max_iter || !a.center || !a.seed || !a.L1_u || !a.L1_v || !a.L2_u ||
+        !a.L2_v || !a.nonneg_u || !a.nonneg_v || !a.ub_u || !a.ub_v || !a.U || !a.d || !a.V || !a.out_k_selected || !a.out_passes ||
+        !a.out_dw || !a.out_frobenius_norm_sq || !a.out_row_means || !a.out_wall_time_ms)
+        throw std::invalid_argument("null pointer");
+    if (*a.precision != RCPPML_F32 && *a.precision != RCPPML_F64) throw std::invalid_argument("precision must be RCPPML_F32 or RCPPML_F64");
+    Opts o;
+    o.m = *m; o.n = *n; o.k = *a.k_max;
+    o.tol = *a.tol; o.max_iter = 0; o.ks_iter = *a.max_iter; o.center = *a.center != 0; o.seed = (unsigned)(uint32_t)*a.seed;
+    o.algorithm = 4; o.kspr = true; o.V0 = a.V0;
+    o.L1_u = *a.L1_u; o.L1_v = *a.L1_v; o.L2_u = *a.L2_u; o.L2_v = *a.L2_v; o.ub_u = *a.ub_u; o.ub_v = *a.ub_v;
+    o.nonneg_u = *a.nonneg_u != 0; o.nonneg_v = *a.nonneg_v != 0;
+    if (o.m < 1 || o.n < 1) throw std::invalid_argument("the matrix must have at least one row and one column");
+    if (o.k < 1 || o.k > std::min(o.m, o.n)) throw std::invalid_argument("k_max must be in [1, min(m, n)]");
+    if (o.k > KS_KMAX) throw std::invalid_argument("k_max above " + std::to_string(KS_KMAX) + " is not supported by the krylov method");
+    if (!(o.tol >= 0)) throw std::invalid_argument("tol must be non-negative");
+    if (!(o.L1_u >= 0 && o.L1_v >= 0)) throw std::invalid_argument("L1 penalties must be non-negative");
+    if (!(o.L2_u >= 0 && o.L2_v >= 0)) throw std::invalid_argument("L2 penalties must be non-negative");
+    if (!(o.ub_u >= 0 && o.ub_v >= 0)) throw std::invalid_argument("upper bounds must be non-negative");
+    if (!std::isfinite(o.L1_u + o.L1_v + o.L2_u + o.L2_v + o.ub_u + o.ub_v + o.tol))
+        throw std::invalid_argument("a penalty, bound or tol is not finite");
+    if (!has_constraints(o))
+        throw std::invalid_argument("the krylov method without element constraints is Lanczos: call rcppml_gpu_svd_pca_* with algorithm 2");
+    if (a.V0) all_finite(a.V0, (size_t)o.n * o.k, "V0");
+    return o;
+}
+
+// device bytes of a fit, generously: the CSC and its transpose with the fp64 staging copy (a dense input also as it is), the
+// Lanczos bases of the seed, the block factors and the partial records
+size_t ks_bytes(const Opts& o, size_t ts) {
+    const size_t len = (size_t)o.nnz, K = (size_t)o.k, mn = (size_t)std::min(o.m, o.n);
+    size_t b = len * (2 * (sizeof(int) + ts) + sizeof(double)) + (o.dense ? len * ts : 0) + ((size_t)o.m + o.n + 2) * sizeof(int);
+    if (!o.V0) b += ((size_t)o.m + o.n) * (std::min(mn, std::max(3 * K, K + 50)) + 8) * ts;
+    b += (2 * (size_t)o.m + o.n) * K * ts;
+    b += ((size_t)o.m / KS_RB + o.n / KS_RB + 2) * K * sizeof(double) + ((size_t)std::max(o.m, o.n) / KS_GR + 1) * ks_np(o.k) * sizeof(double);
+    return b + 3 * K * K * sizeof(double);
+}
+
+void run_ks_entry(const KsRaw& a, const Opts& o) {
+    const bool f32 = *a.precision == RCPPML_F32;
+    device_ready(ks_bytes(o, f32 ? sizeof(float) : sizeof(double)), "the SVD");
+    const auto t0 = std::chrono::steady_clock::now();
+    Result R;
+    if (f32) { Engine<float> E(o); E.run(R); }
+    else { Engine<double> E(o); E.run(R); }
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::copy(R.U.begin(), R.U.end(), a.U);           // the first k_selected columns
+    std::copy(R.V.begin(), R.V.end(), a.V);
+    std::copy(R.d.begin(), R.d.end(), a.d);
+    std::copy(R.dw.begin(), R.dw.end(), a.out_dw);
+    *a.out_k_selected = R.k_sel;
+    *a.out_passes = R.passes;
+    *a.out_frobenius_norm_sq = R.frob;
+    if (o.center) std::copy(R.row_means.begin(), R.row_means.end(), a.out_row_means);
+    *a.out_wall_time_ms = ms;
+}
+}  // namespace
+
+#define RCPPML_SVD_KS_PARAMS                                                                                                      \
+    int *precision, int *k_max, double *tol, int *max_iter, int *center, int *seed, double *L1_u, double *L1_v, double *L2_u,       \
+        double *L2_v, int *nonneg_u, int *nonneg_v, double *ub_u, double *ub_v, const double *V0, double *U, double *d, double *V,  \
+        int *out_k_selected, int *out_passes, double *out_dw, double *out_frobenius_norm_sq, double *out_row_means,                 \
+        double *out_wall_time_ms, int *out_status
+#define RCPPML_SVD_KS_RAW                                                                                                         \
+    KsRaw{precision, k_max, tol, max_iter, center, seed, L1_u, L1_v, L2_u, L2_v, nonneg_u, nonneg_v, ub_u, ub_v, V0, U, d, V,     \
+          out_k_selected, out_passes, out_dw, out_frobenius_norm_sq, out_row_means, out_wall_time_ms}
+
+extern "C" void rcppml_gpu_svd_krylov_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+                                         RCPPML_SVD_KS_PARAMS) {
+    entry_guard(out_status, [&] {
+        const KsRaw a = RCPPML_SVD_KS_RAW;
+        Opts o = make_ks_opts(a, m, n);
+        if (!nnz) throw std::invalid_argument("null pointer");
+        o.nnz = *nnz; o.p = col_ptr; o.i = row_idx; o.x = values;
+        check_csc_lenient(o.p, o.i, o.x, o.m, o.n, o.nnz);
+        run_ks_entry(a, o);
+    });
+}
+// the dense matrix enumerated as a full CSC (as the reference's bridge does for krylov); the Lanczos seed runs the dense products
+extern "C" void rcppml_gpu_svd_krylov_dense_ex(const double* A_data, int* m, int* n, RCPPML_SVD_KS_PARAMS) {
+    entry_guard(out_status, [&] {
+        const KsRaw a = RCPPML_SVD_KS_RAW;
+        Opts o = make_ks_opts(a, m, n);
+        if (!A_data) throw std::invalid_argument("null matrix");
+        o.nnz = (int64_t)o.m * o.n;
+        if (o.nnz >= INT_MAX) throw std::invalid_argument("nnz out of range");
+        std::vector<int> p((size_t)o.n + 1), i((size_t)o.nnz);
+        for (int j = 0; j <= o.n; ++j) p[j] = (int)((int64_t)j * o.m);
+        for (int64_t e = 0; e < o.nnz; ++e) i[e] = (int)(e % o.m);
+        o.dense = A_data; o.p = p.data(); o.i = i.data(); o.x = A_data;
+        run_ks_entry(a, o);
     });
 }

@@ -1,6 +1,7 @@
 """svd() and pca(): host-side mirror of the reference R surface (R/svd.R) on the HIP SVD path (csrc/ops_svd.hip).  Method
 resolution, per-method maxit defaults and the validation messages are R's (R/svd.R:118-406) for the arguments this surface takes;
-the GPU runs deflation (method "deflation") or Golub-Kahan-Lanczos (every other method, unconstrained).  Cross-validation,
+the GPU runs deflation (method "deflation"), Golub-Kahan-Lanczos (every other method, unconstrained) or, for an explicit
+method "krylov" with element constraints, the block refinement KSPR of rcppml_gpu_svd_krylov_ex (_abi.svd_krylov).  Cross-validation,
 auto-rank (k = "auto") and a mask matrix run the deflation of the build-defined rcppml_gpu_svd_cv_ex entries (_abi.svd_cv);
 everything else stays on the reference-shaped entries (_abi.svd_pca).  No CPU fallback: without a device the calls raise
 BackendError."""
@@ -121,18 +122,26 @@ def resolve_cv(k, method="auto", test_fraction=0, patience=3, k_max=50, L1=0, L2
 def svd(A, k=10, tol=1e-5, maxit=_MISSING, center=False, seed=None, L1=0, L2=0, nonneg=False, upper_bound=0, method="auto",
         precision="float", test_fraction=0, mask=None, cv_seed=None, patience=3, k_max=50):
     """Truncated SVD on the GPU (R/svd.R with resource = "gpu").  A: scipy sparse / CSC (the sparse entries) or a dense matrix (the
-    dense entries).  precision: "float" (fp32 on the device, R's default) or "double".  Constrained fits with k >= 8 resolve to
-    krylov, as in R, which the GPU refuses (BackendError); pass method="deflation" for them.
+    dense entries).  precision: "float" (fp32 on the device, R's default) or "double".
+
+    method="krylov" with L1, L2, nonneg or upper_bound runs Krylov-Seeded Projected Refinement: a Lanczos seed, then passes of
+    Gram-solve-and-project on all k factors at once (k <= 128); maxit is the pass limit (missing: max(10, 2 ceil(log2 k) + 3), as R
+    resolves krylov's maxit to 0) and tol the bound on the relative change of u that ends the passes.  With nonneg, L1 or an upper
+    bound the factors come back as they are, ordered by d; with L2 only they are re-orthogonalised.  Without constraints krylov is
+    Lanczos.  method="auto" still resolves constrained fits with k >= 8 to krylov as in R, and that resolution is still refused
+    (BackendError): name method="krylov" or method="deflation" for them.
 
     k = "auto" (rank up to k_max, default 50) or test_fraction > 0 holds out a speckled set of entries and stops adding factors
     when their error has not improved for `patience` factors, with a fixed k too, so fewer than k factors may come back; the
     result is trimmed to the best rank.  mask: None, "zeros" (only stored entries are held out), a sparse matrix whose nonzero
     entries are unobserved, or ("zeros", matrix).  cv_seed: seed of the hold-out set (None: derived from seed).  These run
-    deflation; under CV krylov is refused on the GPU, and so is a mask matrix with any method but deflation.  A rank above
+    deflation; under CV or a mask matrix krylov is refused on the GPU, and so is a mask matrix with any method but deflation.  A rank above
     min(m, n) is clamped here (the reference's gateway passes k_max on unchanged and its loop then ends on sigma ~ 0).
 
     Returns dict(u, d, v, misc) with misc = dict(iters_per_factor, frobenius_norm_sq, row_means (or None), method, wall_time_ms,
-    auto_rank, k_selected, test_loss (one value per computed factor; empty without CV), n_test, cv_seed_effective)."""
+    auto_rank, k_selected, test_loss (one value per computed factor; empty without CV), n_test, cv_seed_effective); under KSPR
+    also passes and dw (the relative change of u in each pass from the second on), and iters_per_factor is empty."""
+    explicit = method
     M, dense = as_matrix(A, what="'A' must be a matrix, dgCMatrix, or path to a .spz file")
     shape = dense.shape if dense is not None else (M.rows, M.cols)
     k, method, test_fraction, auto_rank = resolve_cv(k, method, test_fraction, patience, k_max, L1, L2, nonneg, upper_bound)
@@ -145,6 +154,12 @@ def svd(A, k=10, tol=1e-5, maxit=_MISSING, center=False, seed=None, L1=0, L2=0, 
     if test_fraction > 0 or obs is not None:
         return _svd_cv(M, dense, min(k, min(shape)), method, maxit, tol, center, s, (L1v, L2v, nn, ub), precision, test_fraction, cs,
                        int(patience), mask_zeros, obs, auto_rank)
+    constrained = bool(np.any(L1v > 0) or np.any(L2v > 0) or np.any(nn) or np.any(ub > 0))
+    if method == "krylov" and constrained:
+        if explicit != "krylov":
+            raise _abi.BackendError("GPU SVD/PCA failed: method 'auto' resolves a constrained fit with k >= 8 to 'krylov', which the GPU "
+                                    "runs only when it is named: pass method = \"krylov\" (block refinement) or method = \"deflation\"")
+        return _svd_krylov(M, dense, min(k, min(shape)), maxit, tol, center, s, (L1v, L2v, nn, ub), precision)
     kw = dict(precision=precision, tol=tol, max_iter=maxit, center=center, seed=s, L1=L1v, L2=L2v, nonneg=nn, upper_bound=ub,
               algorithm=_abi.SVD_ALGORITHMS[method])
     if dense is not None:
@@ -184,6 +199,23 @@ def _svd_cv(M, dense, k, method, maxit, tol, center, seed, cons, precision, test
                 row_means=r["row_means"][:m].copy() if center else None, method=method, wall_time_ms=r["wall_ms"],
                 auto_rank=auto_rank, k_selected=ks, test_loss=r["test_loss"][:kc].copy() if test_fraction > 0 else np.zeros(0),
                 n_test=r["n_test"], cv_seed_effective=eff)
+    return dict(u=r["U"][:, :ks].copy(), d=r["d"][:ks].copy(), v=r["V"][:, :ks].copy(), misc=misc)
+
+
+def _svd_krylov(M, dense, k, maxit, tol, center, seed, cons, precision):
+    """The constrained krylov call: KSPR through _abi.svd_krylov."""
+    L1v, L2v, nn, ub = cons
+    src = dense if dense is not None else (M.p, M.i, M.x, M.rows, M.cols)
+    r = _abi.svd_krylov(src, k, dense=dense is not None, precision=precision, tol=tol, max_iter=maxit, center=center, seed=seed,
+                        L1=L1v, L2=L2v, nonneg=nn, upper_bound=ub)
+    if r["status"] != 0:
+        raise _abi.BackendError("GPU SVD/PCA failed: %s" % r["error"])
+    ks = r["k"]
+    m = dense.shape[0] if dense is not None else M.rows
+    misc = dict(iters_per_factor=np.zeros(0, np.int32), frobenius_norm_sq=r["frob"],
+                row_means=r["row_means"][:m].copy() if center else None, method="krylov", wall_time_ms=r["wall_ms"],
+                auto_rank=False, k_selected=ks, test_loss=np.zeros(0), n_test=0, cv_seed_effective=None, passes=r["passes"],
+                dw=r["dw"].copy())
     return dict(u=r["U"][:, :ks].copy(), d=r["d"][:ks].copy(), v=r["V"][:, :ks].copy(), misc=misc)
 
 

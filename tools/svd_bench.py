@@ -12,7 +12,13 @@ labelled as such.  Prints one JSON line per workload.
 
 --auto runs one leg only: pca(k = "auto") through the Python surface (rcppml_gpu_svd_cv_ex: cross-validated deflation, k_max 50,
 test_fraction 0.05, patience 3, fp64), and prints one JSON line with the call's wall time (best of three after a warm-up),
-k_selected, the factors computed, and the time and rank of the numpy restatement (tests/svd_cv_ref.py; not the reference's C++)."""
+k_selected, the factors computed, and the time and rank of the numpy restatement (tests/svd_cv_ref.py; not the reference's C++).
+
+--krylov runs one leg only: svd(k = 16, nonneg) in fp32 with the constrained block method KSPR (rcppml_gpu_svd_krylov_ex, default
+pass limit, tol 1e-5), with deflation under the same constraints on the same device (what the fit cost before KSPR), and with the
+numpy restatement of KSPR from the device's Lanczos seed (tests/svd_krylov_ref.py; not the reference's C++).  One JSON line: wall
+times (best of three after a warm-up), the pass count, ms per pass (the call with the default limit minus a one-pass call, over the
+passes in between: the seed and the transfers cancel) and the relative Frobenius error of both fits."""
 import argparse
 import json
 import os
@@ -63,14 +69,52 @@ def auto_leg(A):
                                     "reference's C++")), flush=True)
 
 
+def krylov_leg(A):
+    import scipy.sparse as sp
+    import svd_krylov_ref
+    parts = (A.p, A.i, A.x, A.rows, A.cols)
+    k, kw = 16, dict(precision="float", tol=1e-5, seed=0, nonneg=(True, True))
+    r, ts = timed(lambda: _abi.svd_krylov(parts, k, max_iter=0, **kw))
+    assert r["status"] == 0, r["error"]
+    one, t1 = timed(lambda: _abi.svd_krylov(parts, k, max_iter=1, **kw))
+    assert one["status"] == 0, one["error"]
+    dfl, td = timed(lambda: _abi.svd_pca(parts, k, algorithm=0, max_iter=200, **kw))
+    assert dfl["status"] == 0, dfl["error"]
+    lz = _abi.svd_pca(parts, k, algorithm=2, max_iter=0, precision="float", tol=1e-5, seed=0)
+    assert lz["status"] == 0, lz["error"]
+    M = sp.csc_matrix((A.x, A.i, A.p), shape=(A.rows, A.cols))
+    dense = M.toarray()
+    t0 = time.perf_counter()
+    ref = svd_krylov_ref.kspr(dense, lz["V"][:, :lz["k"]], 0, 1e-5, nonneg=(True, True), dtype=np.float32)
+    cpu_s = time.perf_counter() - t0
+    fro = np.linalg.norm(dense)
+
+    def err(x):
+        kk = x["k"]
+        return float(np.linalg.norm(dense - (x["U"][:, :kk] * x["d"][:kk]) @ x["V"][:, :kk].T) / fro)
+    passes = int(r["passes"])
+    print(json.dumps(dict(workload="svd k=16 nonneg krylov (KSPR)", precision="float", m=A.rows, n=A.cols, nnz=int(A.x.shape[0]),
+                          wall_s=min(ts), wall_s_all=ts, entry_wall_ms=r["wall_ms"], passes=passes,
+                          ms_per_pass=(min(ts) - min(t1)) * 1e3 / max(passes - 1, 1), one_pass_wall_s=min(t1), dw_last=float(r["dw"][-1]),
+                          rel_error=err(r), deflation_wall_s=min(td), deflation_wall_s_all=td,
+                          deflation_iterations=int(np.sum(dfl["iters"][:dfl["k"]])), deflation_rel_error=err(dfl),
+                          cpu_s=cpu_s, cpu_passes=int(ref["passes"]),
+                          cpu_label="numpy restatement of KSPR in float32 from the device's Lanczos seed (tests/svd_krylov_ref.py), "
+                                    "not the reference's C++")), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cpu", action="store_true", help="also time the numpy restatements (slow)")
     ap.add_argument("--auto", action="store_true", help="only the pca(k = \"auto\") leg")
+    ap.add_argument("--krylov", action="store_true", help="only the svd(k = 16, nonneg, method = \"krylov\") leg")
     args = ap.parse_args()
     A = pbmc3k()
     if args.auto:
         auto_leg(A)
+        return
+    if args.krylov:
+        krylov_leg(A)
         return
     parts = (A.p, A.i, A.x, A.rows, A.cols)
     work = [("pca k=10 lanczos", dict(k=10, center=True, algorithm=2, max_iter=0)),
