@@ -378,6 +378,48 @@ RCPPML_GPU_API void rcppml_gpu_svd_cv_dense_ex(const double* A_data, int* m, int
         int* out_n_masked, int* out_iters_per_factor, double* out_frobenius_norm_sq, double* out_row_means,
         double* out_wall_time_ms, int* out_status);
 
+/* L21, angular and graph-regularised deflation SVD (rcppml_amd/csrc/ops_svd.hip, kernels_svd_reg.hip.h).  BUILD-DEFINED: the reference has
+ * no such symbols; its CPU deflation loop applies the three terms between the element constraints and the normalisation, on both sides, in
+ * every iteration, with or without cross-validation (svd/deflation.hpp:191-292, :734-742, :779-787), and the four rcppml_gpu_svd_pca_*
+ * entries still refuse them.  The parameters are rcppml_gpu_svd_cv_ex's, in order, with the new ones after ub_v; everything said there
+ * (hold-out, *mask_zeros, obs_mask, patience, auto-rank, centering, the element constraints, the outputs) holds here and combines with
+ * the new terms.  Per side and per iteration, on the freshly divided update x with nsq = |u_hat|^2 (v side) or |v|^2 (u side), times the
+ * denominator correction under CV -- the number the element constraints take:
+ *   L21      *L21 > 0 and |x|_2 > 1e-10 (cast to the working precision): L2_eff = L2 + *L21 / |x|_2, |x|_2 taken before any shrinkage;
+ *            the L2 -> L1 -> nonneg -> upper-bound chain then runs with L2_eff (:200-213)
+ *   angular  *angular > 0 and factor k > 0: x -= (*angular / nsq) F (F' x), F the k stored factors of that side, F' x taken from x
+ *            after the element chain (:256-267)
+ *   graph    graph_*_p != NULL and *graph_*_lambda > 0: x -= (*lambda / nsq) (L x), L the dim x dim CSC exactly as passed (L x, not L' x;
+ *            L need not be symmetric), x the vector after the angular step (:283-292).  A gradient step, not a solve: it amplifies the
+ *            high end of L's spectrum once *lambda * lambda_max(L) / nsq passes 1, as the reference does.
+ * Normalisation, the break rules, momentum, the warm start, Gram-Schmidt, the Rayleigh quotient, the test loss and patience are the cv
+ * entry's; none of the three terms touches the warm start or the Rayleigh quotient.  graph_*_p = NULL or *graph_*_lambda <= 0: no graph on
+ * that side (the other five pointers of that side are then not read).  With *L21_*, *angular_* and both graphs off the call is
+ * rcppml_gpu_svd_cv_ex, bit for bit and launch for launch.
+ * Refused with *out_status = -1 (rcppml_gpu_last_error), nothing written: everything rcppml_gpu_svd_cv_ex refuses; a negative or non-finite
+ * *L21_*, *angular_* or *graph_*_lambda; *graph_u_dim != m or *graph_v_dim != n; a malformed graph CSC (the checks A gets); a non-finite
+ * graph value; more device memory than is free, the graphs counted. */
+RCPPML_GPU_API void rcppml_gpu_svd_reg_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+        int* precision, int* k_max, double* tol, int* max_iter, int* center, int* seed, double* L1_u, double* L1_v, double* L2_u,
+        double* L2_v, int* nonneg_u, int* nonneg_v, double* ub_u, double* ub_v, double* L21_u, double* L21_v, double* angular_u,
+        double* angular_v, const int* graph_u_p, const int* graph_u_i, const double* graph_u_x, int* graph_u_dim, int* graph_u_nnz,
+        double* graph_u_lambda, const int* graph_v_p, const int* graph_v_i, const double* graph_v_x, int* graph_v_dim,
+        int* graph_v_nnz, double* graph_v_lambda, double* test_fraction, int* cv_seed, int* patience, int* mask_zeros,
+        const int* obs_mask_p, const int* obs_mask_i, int* obs_mask_rows, int* obs_mask_cols, int* obs_mask_nnz,
+        double* U, double* d, double* V, int* out_k_selected, int* out_k_computed, double* out_test_loss, int* out_n_test,
+        int* out_n_masked, int* out_iters_per_factor, double* out_frobenius_norm_sq, double* out_row_means,
+        double* out_wall_time_ms, int* out_status);
+RCPPML_GPU_API void rcppml_gpu_svd_reg_dense_ex(const double* A_data, int* m, int* n,
+        int* precision, int* k_max, double* tol, int* max_iter, int* center, int* seed, double* L1_u, double* L1_v, double* L2_u,
+        double* L2_v, int* nonneg_u, int* nonneg_v, double* ub_u, double* ub_v, double* L21_u, double* L21_v, double* angular_u,
+        double* angular_v, const int* graph_u_p, const int* graph_u_i, const double* graph_u_x, int* graph_u_dim, int* graph_u_nnz,
+        double* graph_u_lambda, const int* graph_v_p, const int* graph_v_i, const double* graph_v_x, int* graph_v_dim,
+        int* graph_v_nnz, double* graph_v_lambda, double* test_fraction, int* cv_seed, int* patience, int* mask_zeros,
+        const int* obs_mask_p, const int* obs_mask_i, int* obs_mask_rows, int* obs_mask_cols, int* obs_mask_nnz,
+        double* U, double* d, double* V, int* out_k_selected, int* out_k_computed, double* out_test_loss, int* out_n_test,
+        int* out_n_masked, int* out_iters_per_factor, double* out_frobenius_norm_sq, double* out_row_means,
+        double* out_wall_time_ms, int* out_status);
+
 /* Constrained block SVD, Krylov-Seeded Projected Refinement (rcppml_amd/csrc/ops_svd.hip, kernels_svd_krylov.hip.h).  BUILD-DEFINED:
  * the reference runs this as algorithm 4 with element constraints (svd/krylov.hpp:262-796), which the four rcppml_gpu_svd_pca_*
  * entries still refuse.  Scope: L1, L2, nonneg and upper bound on either side, centering, FACTOR convergence.

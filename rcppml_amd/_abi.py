@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_bipartition_double", "rcppml_gpu_dclust_double", "rcppml_gpu_bipartition_ex", "rcppml_gpu_dclust_ex",
     "rcppml_gpu_svd_pca_double", "rcppml_gpu_svd_pca_float", "rcppml_gpu_svd_pca_dense_double", "rcppml_gpu_svd_pca_dense_float",
     "rcppml_gpu_svd_cv_ex", "rcppml_gpu_svd_cv_dense_ex", "rcppml_gpu_svd_krylov_ex", "rcppml_gpu_svd_krylov_dense_ex",
+    "rcppml_gpu_svd_reg_ex", "rcppml_gpu_svd_reg_dense_ex",
     "rcppml_gpu_assess", "rcppml_gpu_assess_ex", "rcppml_gpu_knn_float", "rcppml_gpu_assess_plan",
     "rcppml_gpu_score_test_double", "rcppml_gpu_zero_inflation_double", "rcppml_gpu_dispersion_double",
     "rcppml_gpu_consensus_double", "rcppml_gpu_hclust_average_double",
@@ -957,6 +958,64 @@ def svd_cv(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=200,
                    C.byref(st)]
     assert len(args) == (39 if dense else 42)
     getattr(lib(), "rcppml_gpu_svd_cv_dense_ex" if dense else "rcppml_gpu_svd_cv_ex")(*args)
+    return dict(status=st.value, error=last_error() if st.value else "", U=b["U"][:m * kb].reshape(kb, m).T,
+                V=b["V"][:n * kb].reshape(kb, n).T, d=b["d"], k=ksel.value, k_computed=kcomp.value, test_loss=b["test_loss"],
+                n_test=ntest.value, n_masked=nmask.value, iters=b["iters"], frob=frob.value, row_means=b["row_means"],
+                wall_ms=wall.value, buffers=b)
+
+
+def svd_reg(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=200, center=False, seed=0, L1=(0.0, 0.0),
+            L2=(0.0, 0.0), nonneg=(False, False), upper_bound=(0.0, 0.0), L21=(0.0, 0.0), angular=(0.0, 0.0), graph_u=None,
+            graph_v=None, test_fraction=0.0, cv_seed=0, patience=3, mask_zeros=False, obs_mask=None, buffers=None):
+    """The build-defined rcppml_gpu_svd_reg_ex / rcppml_gpu_svd_reg_dense_ex: svd_cv plus L21, angular and graph regularisation in
+    the deflation loop.  A, obs_mask, buffers and the result dict as in svd_cv; L21 / angular: (u, v); graph_u / graph_v: (p, i, x,
+    dim, lambda) as svd_pca takes them, or None."""
+    if dense:
+        Ad = np.asfortranarray(np.asarray(A, np.float64))
+        m, n = Ad.shape
+        head = [_np_ptr(Ad.ravel(order="F")), _ci(m), _ci(n)]
+        keep = [Ad]
+    else:
+        p, i, x, m, n = A
+        p, i, x = _csc_args(p, i, x)
+        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0])]
+        keep = [p, i, x]
+    kb = max(k_max, 1)
+    b = dict(U=np.zeros(m * kb), d=np.zeros(kb), V=np.zeros(n * kb), test_loss=np.zeros(kb), iters=np.zeros(kb, np.int32),
+             row_means=np.zeros(m))
+    if buffers:
+        b.update(buffers)
+
+    def graph(g):
+        if g is None:
+            return [None] * 6
+        gp, gi, gx, dim, lam = g
+        gp, gi, gx = _csc_args(gp, gi, gx)
+        gi_arg, gx_arg = (gi, gx) if gx.shape[0] else (np.zeros(1, np.int32), np.zeros(1))
+        keep.extend([gp, gi_arg, gx_arg])
+        return [_np_ptr(gp), _np_ptr(gi_arg), _np_ptr(gx_arg), _ci(dim), _ci(gx.shape[0]), _cd(lam)]
+
+    if obs_mask is None:
+        om = [None, None, None, None, None]
+    else:
+        op_, oi, rows, cols = obs_mask
+        op_ = np.ascontiguousarray(op_, np.int32)
+        oi = np.ascontiguousarray(oi, np.int32)
+        oi_arg = oi if oi.shape[0] else np.zeros(1, np.int32)
+        keep.extend([op_, oi_arg])
+        om = [_np_ptr(op_), _np_ptr(oi_arg), _ci(rows), _ci(cols), _ci(oi.shape[0])]
+    ksel, kcomp, ntest, nmask = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    wall, frob, st = C.c_double(0.0), C.c_double(0.0), C.c_int(-99)
+    args = head + [_ci(F32 if precision == "float" else F64), _ci(k_max), _cd(tol), _ci(max_iter), _ci(int(bool(center))), _ci(seed),
+                   _cd(L1[0]), _cd(L1[1]), _cd(L2[0]), _cd(L2[1]), _ci(int(bool(nonneg[0]))), _ci(int(bool(nonneg[1]))),
+                   _cd(upper_bound[0]), _cd(upper_bound[1]), _cd(L21[0]), _cd(L21[1]), _cd(angular[0]), _cd(angular[1])
+                   ] + graph(graph_u) + graph(graph_v) + [
+                   _cd(test_fraction), _ci(cv_seed), _ci(patience), _ci(int(bool(mask_zeros)))] + om + [
+                   _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]), C.byref(ksel), C.byref(kcomp), _np_ptr(b["test_loss"]),
+                   C.byref(ntest), C.byref(nmask), _np_ptr(b["iters"]), C.byref(frob), _np_ptr(b["row_means"]), C.byref(wall),
+                   C.byref(st)]
+    assert len(args) == (55 if dense else 58)
+    getattr(lib(), "rcppml_gpu_svd_reg_dense_ex" if dense else "rcppml_gpu_svd_reg_ex")(*args)
     return dict(status=st.value, error=last_error() if st.value else "", U=b["U"][:m * kb].reshape(kb, m).T,
                 V=b["V"][:n * kb].reshape(kb, n).T, d=b["d"], k=ksel.value, k_computed=kcomp.value, test_loss=b["test_loss"],
                 n_test=ntest.value, n_masked=nmask.value, iters=b["iters"], frob=frob.value, row_means=b["row_means"],

@@ -17,11 +17,16 @@
 // reference's correction, and after each stored factor updates the held-out residuals in one launch and applies the patience
 // rule on the host, at the synchronisation the factor's sigma already needs.  The four reference entries keep refusing both.
 //
+// L21, angular and graph regularisation (deflation.hpp:191-292, :734-742, :779-787; kernels: kernels_svd_reg.hip.h) run through the
+// build-defined entries rcppml_gpu_svd_reg_ex / rcppml_gpu_svd_reg_dense_ex, a superset of the cv entries: a side with a term on
+// runs a chain of launches in place of its one epilogue, and with every term off the engine launches what the cv entries launch.
+//
 // Centering never densifies: A'u - (mu . u) 1 and A v - mu sum(v) are scalar corrections inside the epilogues.
 #include "entry_common.hip.h"
 #include "kernels_svd.hip.h"
 #include "kernels_svd_cv.hip.h"
 #include "kernels_svd_krylov.hip.h"
+#include "kernels_svd_reg.hip.h"
 
 #include <chrono>
 #include <climits>
@@ -48,6 +53,12 @@ struct Opts {
     const int* mp = nullptr; const int* mi = nullptr; int64_t mnnz = 0;
     // the krylov entries only: KSPR (kspr), its pass limit (0: the default) and the n x k seed (null: Lanczos); max_iter stays 0
     bool kspr = false; int ks_iter = 0; const double* V0 = nullptr;
+    // the reg entries only: L21 and angular per side, and a square graph CSC per side (p = null or lambda <= 0: none)
+    double L21_u = 0, L21_v = 0, ang_u = 0, ang_v = 0;
+    struct Graph {
+        const int* p = nullptr; const int* i = nullptr; const double* x = nullptr; int dim = 0; int64_t nnz = 0; double lambda = 0;
+        bool on() const { return p && lambda > 0 && nnz > 0; }     // an empty L is the identity step: nothing to launch
+    } gu, gv;
     bool cv() const { return test_fraction > 0; }
     bool trains() const { return cv() || mp; }      // the products read a training copy of A
 };
@@ -242,6 +253,7 @@ template <class T> struct Engine {
     long n_test = 0;
     int64_t n_masked = 0;
     std::vector<double> mu_h;
+    struct DevGraph { DevBuf p, i, x, tp, ti, tx; } Gu, Gv;      // a graph and its rows (the CSC of L')
 
     Engine(const Opts& o_) : o(o_), g(env_device()), s(g.s), m(o_.m), n(o_.n) {
         mu_h.assign(m, 0.0);
@@ -272,6 +284,18 @@ template <class T> struct Engine {
             OPCHK(rcppml_hip_transpose_csc(g.c, DT<T>::id, m, n, Ap.as<int>(), Ai.as<int>(),
                                            (const void*)(o.trains() ? Xt.as<T>() : Ax.as<T>()), Tp.as<int>(), Ti.as<int>(), Tx.p));
         }
+        if (o.gu.on()) upload_graph(o.gu, Gu);
+        if (o.gv.on()) upload_graph(o.gv, Gv);
+    }
+    void upload_graph(const Opts::Graph& gr, DevGraph& G) {
+        upload_ints(gr.p, (size_t)gr.dim + 1, G.p, s);
+        upload_ints(gr.i, (size_t)gr.nnz, G.i, s);
+        upload_cast<T>(g.c, gr.x, (size_t)gr.nnz, G.x, s);
+        grow<int>(G.tp, (size_t)gr.dim + 1);
+        grow<int>(G.ti, (size_t)gr.nnz);
+        grow<T>(G.tx, (size_t)gr.nnz);
+        OPCHK(rcppml_hip_transpose_csc(g.c, DT<T>::id, gr.dim, gr.dim, (const int*)G.p.p, (const int*)G.i.p, (const void*)G.x.p,
+                                       (int*)G.tp.p, (int*)G.ti.p, G.tx.p));
     }
     const T* mup() const { return o.center ? mu.as<T>() : nullptr; }
     // the values the products read: the training copy when there is one
@@ -361,6 +385,44 @@ template <class T> struct Engine {
         grow<T>(Pm, (size_t)nbm * (K + 2)); grow<T>(Pn, (size_t)nbn * (K + 2)); grow<T>(Pu, (size_t)nbm * 2);
         int* S = grow<int>(st, S_WORDS);
         T* dn = grow<T>(nrm, 1);
+        // kernels_svd_reg.hip.h: a side with L21, angular (from the second factor on) or a graph runs a chain instead of its epilogue
+        const T l21u = (T)o.L21_u, l21v = (T)o.L21_v, angu = (T)o.ang_u, angv = (T)o.ang_v;
+        const bool any_reg = l21u > 0 || l21v > 0 || angu > 0 || angv > 0 || o.gu.on() || o.gv.on();
+        DevBuf bQa, bQb, bnsq, blx;
+        T *Qa = nullptr, *Qb = nullptr, *nsq = nullptr, *lx = nullptr;
+        if (any_reg) {
+            Qa = grow<T>(bQa, (size_t)std::max(nbm, nbn) * (K + 2));
+            Qb = grow<T>(bQb, (size_t)std::max(nbm, nbn) * (K + 2));
+            nsq = grow<T>(bnsq, 2);
+            lx = grow<T>(blx, (size_t)std::max(m, n));
+        }
+        // the links after a head, on x (len) in place: the head left the mid partials (k + 2 columns, |x|^2 in column sq) in Qa;
+        // the last link writes Cfin -> Pfin
+        auto chain = [&](T* x, long len, int nb, const T* F, int kf, int sq, T l1, T l2, T l21, int nonneg, T ub, T ang,
+                         const Opts::Graph& gr, const DevGraph& G, const T* nq, const Cols<T>& Cmid, const Cols<T>& Cfin, T* Pfin, int it,
+                         int uside) {
+            const bool on[3] = {l21 > 0, ang > 0 && kf > 0, gr.on()};
+            const int last = on[2] ? 2 : on[1] ? 1 : 0;
+            const T* Pin = Qa;
+            for (int op = 0; op < 3; ++op) {
+                if (!on[op]) continue;
+                T* Pout = op == last ? Pfin : (Pin == Qa ? Qb : Qa);
+                const Cols<T>& Co = op == last ? Cfin : Cmid;
+                if (op == 0)
+                    hipLaunchKernelGGL(reg_shrink_kernel<T>, dim3(nb), dim3(WG), 0, s, x, len, Pin, nb, kf + 2, sq, nq, l1, l2, l21, nonneg, ub,
+                                       Co, Pout, (const int*)S, it, uside);
+                else if (op == 1)
+                    hipLaunchKernelGGL(reg_angular_kernel<T>, dim3(nb), dim3(WG), 0, s, x, len, F, kf, Pin, nb, kf + 2, nq, ang, Co, Pout,
+                                       (const int*)S, it, uside);
+                else {
+                    hipLaunchKernelGGL(spmv_csr<T>, dim3(wblk(len)), dim3(WG), 0, s, (const int*)G.tp.p, (const int*)G.ti.p, (const T*)G.tx.p, (int)len, (const T*)x, lx,
+                                       (const int*)S, it, uside ? (int)S_BRKU : (int)S_BRKV);
+                    hipLaunchKernelGGL(reg_graph_kernel<T>, dim3(nb), dim3(WG), 0, s, x, len, (const T*)lx, nq, (T)gr.lambda, Co, Pout,
+                                       (const int*)S, it, uside);
+                }
+                Pin = Pout;
+            }
+        };
         HIPCHK(hipMemsetAsync(U, 0, (size_t)m * K * sizeof(T), s));
         HIPCHK(hipMemsetAsync(V, 0, (size_t)n * K * sizeof(T), s));
         HIPCHK(hipMemsetAsync(d, 0, (size_t)K * sizeof(T), s));
@@ -418,18 +480,40 @@ template <class T> struct Engine {
             HIPCHK(hipMemcpyAsync(S, init, sizeof(init), hipMemcpyHostToDevice, s));
             Cm.e[1] = uhat.as<T>();
             dots(uhat.as<T>(), m, Cm, Pm.as<T>());
+            // the regularised chains of this factor: angular has nothing to subtract from at k = 0
+            const bool reg_v = l21v > 0 || (angv > 0 && k > 0) || o.gv.on(), reg_u = l21u > 0 || (angu > 0 && k > 0) || o.gu.on();
+            Cols<T> Cnr = Cn, Cum, Cuf;                         // n side (mid = final); m side mid [U_k' x, |x|^2, x . u] and final
+            Cnr.e[1] = vraw.as<T>();
+            Cum.X = U; Cum.ld = m; Cum.nx = k; Cum.e[0] = uraw.as<T>(); Cum.e[1] = u; Cum.ne = 2;
+            Cuf.e[0] = uraw.as<T>(); Cuf.e[1] = u; Cuf.ne = 2;
             for (int done = 0; done < o.max_iter;) {
                 const int P = std::min(kPoll, o.max_iter - done);
                 for (int q = 0; q < P; ++q) {
                     const int it = done + q;
                     at(uhat.as<T>(), y.as<T>(), S, it, 0);
-                    hipLaunchKernelGGL(defl_v_kernel<T>, dim3(nbn), dim3(WG), 0, s, (const T*)y.as<T>(), n, (const T*)V, k, (const T*)d,
-                                       (const T*)Pm.as<T>(), nbm, o.center, l1v, l2v, o.nonneg_v, ubv, dc, (int)M_LOOP, vraw.as<T>(),
-                                       Pn.as<T>(), S, it);
+                    if (!reg_v)
+                        hipLaunchKernelGGL(defl_v_kernel<T>, dim3(nbn), dim3(WG), 0, s, (const T*)y.as<T>(), n, (const T*)V, k, (const T*)d,
+                                           (const T*)Pm.as<T>(), nbm, o.center, l1v, l2v, o.nonneg_v, ubv, dc, (int)M_LOOP, vraw.as<T>(),
+                                           Pn.as<T>(), S, it);
+                    else {
+                        hipLaunchKernelGGL(reg_v_head_kernel<T>, dim3(nbn), dim3(WG), 0, s, (const T*)y.as<T>(), n, (const T*)V, k,
+                                           (const T*)d, (const T*)Pm.as<T>(), nbm, o.center, l1v, l2v, o.nonneg_v, ubv, dc,
+                                           l21v > 0 ? 0 : 1, vraw.as<T>(), Qa, nsq, S, it);
+                        chain(vraw.as<T>(), (long)n, nbn, (const T*)V, k, k + 1, l1v, l2v, l21v, o.nonneg_v, ubv, angv, o.gv, Gv,
+                              (const T*)nsq, Cnr, Cnr, Pn.as<T>(), it, 0);
+                    }
                     ax(vraw.as<T>(), t.as<T>(), S, it, S_BRKV);
-                    hipLaunchKernelGGL(defl_u_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)t.as<T>(), m, (const T*)U, k, (const T*)d,
-                                       (const T*)Pn.as<T>(), nbn, mup(), l1u, l2u, o.nonneg_u, ubu, dc, (int)M_LOOP, (const T*)vraw.as<T>(),
-                                       v, n, uraw.as<T>(), (const T*)u, Pu.as<T>(), S, it);
+                    if (!reg_u)
+                        hipLaunchKernelGGL(defl_u_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)t.as<T>(), m, (const T*)U, k, (const T*)d,
+                                           (const T*)Pn.as<T>(), nbn, mup(), l1u, l2u, o.nonneg_u, ubu, dc, (int)M_LOOP,
+                                           (const T*)vraw.as<T>(), v, n, uraw.as<T>(), (const T*)u, Pu.as<T>(), S, it);
+                    else {
+                        hipLaunchKernelGGL(reg_u_head_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)t.as<T>(), m, (const T*)U, k,
+                                           (const T*)d, (const T*)Pn.as<T>(), nbn, mup(), l1u, l2u, o.nonneg_u, ubu, dc, l21u > 0 ? 0 : 1,
+                                           (const T*)vraw.as<T>(), v, n, uraw.as<T>(), (const T*)u, Qa, nsq + 1, S, it);
+                        chain(uraw.as<T>(), (long)m, nbm, (const T*)U, k, k, l1u, l2u, l21u, o.nonneg_u, ubu, angu, o.gu, Gu,
+                              (const T*)(nsq + 1), Cum, Cuf, Pu.as<T>(), it, 1);
+                    }
                     hipLaunchKernelGGL(defl_finish_kernel<T>, dim3(nbm), dim3(WG), 0, s, (const T*)uraw.as<T>(), u, uhat.as<T>(), m,
                                        (const T*)Pu.as<T>(), nbm, (const T*)U, k, mup(), Pm.as<T>(), tol_k, S, it);
                 }
@@ -922,9 +1006,9 @@ size_t cv_bytes(const Opts& o, size_t ts) {
     return b;
 }
 
-void run_cv_entry(const CvRaw& a, const Opts& o) {
+void run_fit_entry(const CvRaw& a, const Opts& o, size_t (*bytes)(const Opts&, size_t)) {
     const bool f32 = *a.precision == RCPPML_F32;
-    device_ready(cv_bytes(o, f32 ? sizeof(float) : sizeof(double)), "the SVD");
+    device_ready(bytes(o, f32 ? sizeof(float) : sizeof(double)), "the SVD");
     const auto t0 = std::chrono::steady_clock::now();
     Result R;
     if (f32) { Engine<float> E(o); E.run(R); }
@@ -943,6 +1027,7 @@ void run_cv_entry(const CvRaw& a, const Opts& o) {
     if (o.center) std::copy(R.row_means.begin(), R.row_means.end(), a.out_row_means);
     *a.out_wall_time_ms = ms;
 }
+void run_cv_entry(const CvRaw& a, const Opts& o) { run_fit_entry(a, o, cv_bytes); }
 }  // namespace
 
 #define RCPPML_SVD_CV_PARAMS                                                                                                      \
@@ -976,6 +1061,95 @@ extern "C" void rcppml_gpu_svd_cv_dense_ex(const double* A_data, int* m, int* n,
         if (!A_data) throw std::invalid_argument("null matrix");
         o.nnz = (int64_t)o.m * o.n; o.dense = A_data;
         run_cv_entry(a, o);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------------------ reg entries
+// Build-defined: the cv entries plus L21, angular and a graph per side (the four reference entries refuse all three).  Every check
+// runs before any device work, and nothing is written on a refusal.  With every new term off this is the cv entry, launch for launch.
+namespace {
+struct RegRaw {
+    double *L21_u, *L21_v, *angular_u, *angular_v;
+    const int *graph_u_p, *graph_u_i; const double* graph_u_x; int *graph_u_dim, *graph_u_nnz; double* graph_u_lambda;
+    const int *graph_v_p, *graph_v_i; const double* graph_v_x; int *graph_v_dim, *graph_v_nnz; double* graph_v_lambda;
+};
+
+Opts::Graph make_graph(const int* p, const int* i, const double* x, const int* dim, const int* nnz, const double* lambda, int want,
+                       const char* name) {
+    Opts::Graph gr;
+    if (!p) return gr;
+    if (!lambda) throw std::invalid_argument("null pointer");
+    if (!(*lambda >= 0) || !std::isfinite(*lambda)) throw std::invalid_argument(std::string(name) + " lambda must be non-negative and finite");
+    if (!(*lambda > 0)) return gr;
+    if (!dim || !nnz) throw std::invalid_argument("null pointer");
+    if (*dim != want)
+        throw std::invalid_argument(std::string(name) + " must be " + std::to_string(want) + " x " + std::to_string(want) + " (dim " +
+                                    std::to_string(*dim) + ")");
+    try {
+        check_csc_lenient(p, i, x, want, want, *nnz);
+    } catch (const std::invalid_argument& e) {
+        throw std::invalid_argument("malformed " + std::string(name) + " CSC: " + e.what());
+    }
+    all_finite(x, (size_t)*nnz, name);
+    gr.p = p; gr.i = i; gr.x = x; gr.dim = want; gr.nnz = *nnz; gr.lambda = *lambda;
+    return gr;
+}
+
+void add_reg_opts(Opts& o, const RegRaw& r) {
+    if (!r.L21_u || !r.L21_v || !r.angular_u || !r.angular_v) throw std::invalid_argument("null pointer");
+    o.L21_u = *r.L21_u; o.L21_v = *r.L21_v; o.ang_u = *r.angular_u; o.ang_v = *r.angular_v;
+    if (!(o.L21_u >= 0 && o.L21_v >= 0) || !std::isfinite(o.L21_u + o.L21_v))
+        throw std::invalid_argument("L21 penalties must be non-negative and finite");
+    if (!(o.ang_u >= 0 && o.ang_v >= 0) || !std::isfinite(o.ang_u + o.ang_v))
+        throw std::invalid_argument("angular penalties must be non-negative and finite");
+    o.gu = make_graph(r.graph_u_p, r.graph_u_i, r.graph_u_x, r.graph_u_dim, r.graph_u_nnz, r.graph_u_lambda, o.m, "graph_u");
+    o.gv = make_graph(r.graph_v_p, r.graph_v_i, r.graph_v_x, r.graph_v_dim, r.graph_v_nnz, r.graph_v_lambda, o.n, "graph_v");
+}
+
+// cv_bytes plus the graphs (CSC, rows, fp64 staging), the chain's two partial buffers and L x
+size_t reg_bytes(const Opts& o, size_t ts) {
+    size_t b = cv_bytes(o, ts);
+    for (const Opts::Graph* gr : {&o.gu, &o.gv})
+        if (gr->on()) b += (size_t)gr->nnz * (2 * (sizeof(int) + ts) + sizeof(double)) + 2 * ((size_t)gr->dim + 1) * sizeof(int);
+    b += 2 * (size_t)std::max(nblk(o.m), nblk(o.n)) * ((size_t)o.k + 2) * ts + (size_t)std::max(o.m, o.n) * ts;
+    return b;
+}
+void run_reg_entry(const CvRaw& a, const Opts& o) { run_fit_entry(a, o, reg_bytes); }
+}  // namespace
+
+#define RCPPML_SVD_REG_PARAMS                                                                                                     \
+    int *precision, int *k_max, double *tol, int *max_iter, int *center, int *seed, double *L1_u, double *L1_v, double *L2_u,       \
+        double *L2_v, int *nonneg_u, int *nonneg_v, double *ub_u, double *ub_v, double *L21_u, double *L21_v, double *angular_u,    \
+        double *angular_v, const int *graph_u_p, const int *graph_u_i, const double *graph_u_x, int *graph_u_dim, int *graph_u_nnz, \
+        double *graph_u_lambda, const int *graph_v_p, const int *graph_v_i, const double *graph_v_x, int *graph_v_dim,              \
+        int *graph_v_nnz, double *graph_v_lambda, double *test_fraction, int *cv_seed, int *patience, int *mask_zeros,              \
+        const int *obs_mask_p, const int *obs_mask_i, int *obs_mask_rows, int *obs_mask_cols, int *obs_mask_nnz, double *U,         \
+        double *d, double *V, int *out_k_selected, int *out_k_computed, double *out_test_loss, int *out_n_test, int *out_n_masked,  \
+        int *out_iters_per_factor, double *out_frobenius_norm_sq, double *out_row_means, double *out_wall_time_ms, int *out_status
+#define RCPPML_SVD_REG_RAW                                                                                                        \
+    RegRaw{L21_u, L21_v, angular_u, angular_v, graph_u_p, graph_u_i, graph_u_x, graph_u_dim, graph_u_nnz, graph_u_lambda,         \
+           graph_v_p, graph_v_i, graph_v_x, graph_v_dim, graph_v_nnz, graph_v_lambda}
+
+extern "C" void rcppml_gpu_svd_reg_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+                                      RCPPML_SVD_REG_PARAMS) {
+    entry_guard(out_status, [&] {
+        const CvRaw a = RCPPML_SVD_CV_RAW;
+        Opts o = make_cv_opts(a, m, n);
+        if (!nnz) throw std::invalid_argument("null pointer");
+        o.nnz = *nnz; o.p = col_ptr; o.i = row_idx; o.x = values;
+        check_csc_lenient(o.p, o.i, o.x, o.m, o.n, o.nnz);
+        add_reg_opts(o, RCPPML_SVD_REG_RAW);
+        run_reg_entry(a, o);
+    });
+}
+extern "C" void rcppml_gpu_svd_reg_dense_ex(const double* A_data, int* m, int* n, RCPPML_SVD_REG_PARAMS) {
+    entry_guard(out_status, [&] {
+        const CvRaw a = RCPPML_SVD_CV_RAW;
+        Opts o = make_cv_opts(a, m, n);
+        if (!A_data) throw std::invalid_argument("null matrix");
+        o.nnz = (int64_t)o.m * o.n; o.dense = A_data;
+        add_reg_opts(o, RCPPML_SVD_REG_RAW);
+        run_reg_entry(a, o);
     });
 }
 

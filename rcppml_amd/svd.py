@@ -3,7 +3,8 @@ resolution, per-method maxit defaults and the validation messages are R's (R/svd
 the GPU runs deflation (method "deflation"), Golub-Kahan-Lanczos (every other method, unconstrained) or, for an explicit
 method "krylov" with element constraints, the block refinement KSPR of rcppml_gpu_svd_krylov_ex (_abi.svd_krylov).  Cross-validation,
 auto-rank (k = "auto") and a mask matrix run the deflation of the build-defined rcppml_gpu_svd_cv_ex entries (_abi.svd_cv);
-everything else stays on the reference-shaped entries (_abi.svd_pca).  No CPU fallback: without a device the calls raise
+L21, angular and graph regularisation run the same deflation through rcppml_gpu_svd_reg_ex (_abi.svd_reg), with or without CV or a
+mask; everything else stays on the reference-shaped entries (_abi.svd_pca).  No CPU fallback: without a device the calls raise
 BackendError."""
 import numpy as np
 
@@ -14,8 +15,18 @@ VALID_METHODS = ("auto", "deflation", "krylov", "lanczos", "irlba", "randomized"
 _MISSING = object()
 
 
-def resolve_method(k, method="auto", maxit=_MISSING, tol=1e-5, L1=0, L2=0, nonneg=False, upper_bound=0, use_gpu=True):
-    """R/svd.R:140-406 for the arguments svd() takes here: returns (method, maxit, tol) or raises ValueError with R's message."""
+def _gram_level(angular, graph, graph_lambda):
+    """R/svd.R:290-292: angular > 0 on a side, or a graph given on a side whose graph_lambda is > 0.  graph: (U given, V given)."""
+    ang, lam = np.resize(np.asarray(angular, float), 2), np.resize(np.asarray(graph_lambda, float), 2)
+    gr = np.resize(np.asarray(graph, bool), 2)
+    return bool(np.any(ang > 0) or (gr[0] and lam[0] > 0) or (gr[1] and lam[1] > 0))
+
+
+def resolve_method(k, method="auto", maxit=_MISSING, tol=1e-5, L1=0, L2=0, nonneg=False, upper_bound=0, use_gpu=True, *, L21=0,
+                   angular=0, graph_lambda=0, graph=(False, False)):
+    """R/svd.R:140-406 for the arguments svd() takes here: returns (method, maxit, tol, (L1, L2, nonneg, upper_bound)) or raises
+    ValueError with R's message.  graph: which of graph_U / graph_V is given.  L21 counts as an element constraint, angular and an
+    active graph as Gram-level constraints (:286-311)."""
     maxit_missing = maxit is _MISSING
     if maxit_missing:
         maxit = 200
@@ -37,15 +48,25 @@ def resolve_method(k, method="auto", maxit=_MISSING, tol=1e-5, L1=0, L2=0, nonne
         raise ValueError("L2 penalties must be non-negative")
     if np.any(upper_bound < 0):
         raise ValueError("upper_bound must be non-negative")
+    L21 = np.resize(np.asarray(L21, float), 2)
+    if np.any(L21 < 0):
+        raise ValueError("L21 penalties must be non-negative")
+    if np.any(np.resize(np.asarray(angular, float), 2) < 0):
+        raise ValueError("angular penalties must be non-negative")
+    if np.any(np.resize(np.asarray(graph_lambda, float), 2) < 0):
+        raise ValueError("graph_lambda must be non-negative")
     if tol < 0:
         raise ValueError("'tol' must be non-negative")
     if not (method in ("lanczos", "irlba", "krylov") and maxit == 0) and maxit < 1:
         raise ValueError("'maxit' must be >= 1")
-    constrained = bool(np.any(L1 > 0) or np.any(L2 > 0) or np.any(nonneg) or np.any(upper_bound > 0))
+    constrained = bool(np.any(L1 > 0) or np.any(L2 > 0) or np.any(nonneg) or np.any(upper_bound > 0) or np.any(L21 > 0))
+    gram = _gram_level(angular, graph, graph_lambda)
     if method != "auto" and constrained and method not in ("deflation", "krylov"):
         raise ValueError("method '%s' does not support constraints (L1/L2/nonneg/bounds/L21). Use 'deflation' or 'krylov'." % method)
+    if method != "auto" and gram and method not in ("deflation", "krylov"):
+        raise ValueError("method '%s' does not support Gram-level regularization (angular/graph). Use 'krylov'." % method)
     if method == "auto":
-        if constrained:
+        if constrained or gram:
             method = "krylov" if k >= 8 else "deflation"
         elif use_gpu:
             method = "lanczos" if k < 32 else ("randomized" if k < 64 else "irlba")
@@ -87,7 +108,24 @@ def resolve_mask(mask, shape):
     return mask_zeros, (mat.indptr.astype(np.int32), mat.indices.astype(np.int32), mat.shape[0], mat.shape[1])
 
 
-def resolve_cv(k, method="auto", test_fraction=0, patience=3, k_max=50, L1=0, L2=0, nonneg=False, upper_bound=0):
+def resolve_graph(g, lam, dim, name, of):
+    """R/svd.R:326-339 for one side: None, or (p, i, x, dim, lambda) of the sparse matrix as given (duplicates summed, rows
+    ascending).  Raises ValueError with R's message."""
+    import scipy.sparse as sp
+    if g is None:
+        return None
+    if not sp.issparse(g):
+        raise ValueError("%s must be a sparse matrix" % name)
+    if g.shape != (dim, dim):
+        raise ValueError("%s must be %d x %d (matching %s of A)" % (name, dim, dim, of))
+    g = sp.csc_matrix(g, dtype=np.float64)
+    g.sum_duplicates()
+    g.sort_indices()
+    return (g.indptr.astype(np.int32), g.indices.astype(np.int32), g.data.astype(np.float64), dim, float(lam))
+
+
+def resolve_cv(k, method="auto", test_fraction=0, patience=3, k_max=50, L1=0, L2=0, nonneg=False, upper_bound=0, *, L21=0, angular=0,
+               graph_lambda=0, graph=(False, False)):
     """The cross-validation rules of R/svd.R beside resolve_method(): :177-186 (k = "auto" sets k = k_max and test_fraction = 0.05
     when it is <= 0), :216-217 (ranges), :313-321 (a method without CV raises under auto-rank and drops CV silently under a fixed
     k), :377-385 (method "auto" under CV is deflation, or krylov for a constrained k >= 8).  Returns (k, method, test_fraction,
@@ -108,7 +146,8 @@ def resolve_cv(k, method="auto", test_fraction=0, patience=3, k_max=50, L1=0, L2
     has_cv = auto_rank or 0 < test_fraction < 1
     if method not in VALID_METHODS:
         raise ValueError("method must be one of: %s" % ", ".join(VALID_METHODS))
-    constrained = any(bool(np.any(np.asarray(v, float) > 0)) for v in (L1, L2, nonneg, upper_bound))
+    constrained = any(bool(np.any(np.asarray(v, float) > 0)) for v in (L1, L2, nonneg, upper_bound, L21))
+    constrained = constrained or _gram_level(angular, graph, graph_lambda)
     if method == "auto":
         if has_cv:
             method = "krylov" if constrained and k >= 8 else "deflation"
@@ -120,7 +159,8 @@ def resolve_cv(k, method="auto", test_fraction=0, patience=3, k_max=50, L1=0, L2
 
 
 def svd(A, k=10, tol=1e-5, maxit=_MISSING, center=False, seed=None, L1=0, L2=0, nonneg=False, upper_bound=0, method="auto",
-        precision="float", test_fraction=0, mask=None, cv_seed=None, patience=3, k_max=50):
+        precision="float", test_fraction=0, mask=None, cv_seed=None, patience=3, k_max=50, L21=0, angular=0, graph_U=None,
+        graph_V=None, graph_lambda=0):
     """Truncated SVD on the GPU (R/svd.R with resource = "gpu").  A: scipy sparse / CSC (the sparse entries) or a dense matrix (the
     dense entries).  precision: "float" (fp32 on the device, R's default) or "double".
 
@@ -138,19 +178,37 @@ def svd(A, k=10, tol=1e-5, maxit=_MISSING, center=False, seed=None, L1=0, L2=0, 
     deflation; under CV or a mask matrix krylov is refused on the GPU, and so is a mask matrix with any method but deflation.  A rank above
     min(m, n) is clamped here (the reference's gateway passes k_max on unchanged and its loop then ends on sigma ~ 0).
 
+    L21, angular (one value or one per side, u then v) and graph_U (m x m) / graph_V (n x n) with graph_lambda (one value or one per
+    side) are R's three further regularisers, applied in every deflation iteration after the element constraints: L21 adds
+    L21 / |x| to L2, angular pulls the update away from the factors already stored, and a graph takes the gradient step
+    x -= (graph_lambda / nsq) L x -- keep graph_lambda * lambda_max(L) well below the squared norm it is divided by, or the step
+    amplifies instead of smoothing.  They run with method "deflation", with or without CV or a mask; method "krylov" with any of
+    them on, named or reached through "auto" (k >= 8), is refused on the GPU: pass method = "deflation".
+
     Returns dict(u, d, v, misc) with misc = dict(iters_per_factor, frobenius_norm_sq, row_means (or None), method, wall_time_ms,
     auto_rank, k_selected, test_loss (one value per computed factor; empty without CV), n_test, cv_seed_effective); under KSPR
     also passes and dw (the relative change of u in each pass from the second on), and iters_per_factor is empty."""
     explicit = method
     M, dense = as_matrix(A, what="'A' must be a matrix, dgCMatrix, or path to a .spz file")
     shape = dense.shape if dense is not None else (M.rows, M.cols)
-    k, method, test_fraction, auto_rank = resolve_cv(k, method, test_fraction, patience, k_max, L1, L2, nonneg, upper_bound)
-    method, maxit, tol, (L1v, L2v, nn, ub) = resolve_method(k, method, maxit, tol, L1, L2, nonneg, upper_bound)
+    new = dict(L21=L21, angular=angular, graph_lambda=graph_lambda, graph=(graph_U is not None, graph_V is not None))
+    k, method, test_fraction, auto_rank = resolve_cv(k, method, test_fraction, patience, k_max, L1, L2, nonneg, upper_bound, **new)
+    method, maxit, tol, (L1v, L2v, nn, ub) = resolve_method(k, method, maxit, tol, L1, L2, nonneg, upper_bound, **new)
     mask_zeros, obs = resolve_mask(mask, shape)
+    L21v, angv, lam = (np.resize(np.asarray(v, float), 2) for v in (L21, angular, graph_lambda))
+    gu = resolve_graph(graph_U, lam[0], shape[0], "graph_U", "rows")
+    gv = resolve_graph(graph_V, lam[1], shape[1], "graph_V", "columns")
     if precision not in ("float", "double"):
         raise ValueError("precision must be 'float' or 'double'")
     s = 0 if seed is None else int(seed)
     cs = 0 if cv_seed is None else int(cv_seed)
+    if np.any(L21v > 0) or _gram_level(angv, new["graph"], lam):
+        if method != "deflation":
+            raise _abi.BackendError("GPU SVD/PCA failed: L21, angular and graph regularisation run only in the deflation loop on the GPU "
+                                    "(method '%s' has no such terms yet): pass method = \"deflation\"" % method)
+        reg = dict(L21=L21v, angular=angv, graph_u=gu if lam[0] > 0 else None, graph_v=gv if lam[1] > 0 else None)
+        return _svd_cv(M, dense, min(k, min(shape)), method, maxit, tol, center, s, (L1v, L2v, nn, ub), precision, test_fraction, cs,
+                       int(patience), mask_zeros, obs, auto_rank, reg=reg)
     if test_fraction > 0 or obs is not None:
         return _svd_cv(M, dense, min(k, min(shape)), method, maxit, tol, center, s, (L1v, L2v, nn, ub), precision, test_fraction, cs,
                        int(patience), mask_zeros, obs, auto_rank)
@@ -179,16 +237,18 @@ def svd(A, k=10, tol=1e-5, maxit=_MISSING, center=False, seed=None, L1=0, L2=0, 
     return dict(u=r["U"][:, :ks].copy(), d=r["d"][:ks].copy(), v=r["V"][:, :ks].copy(), misc=misc)
 
 
-def _svd_cv(M, dense, k, method, maxit, tol, center, seed, cons, precision, test_fraction, cv_seed, patience, mask_zeros, obs, auto_rank):
-    """The cross-validated / masked call: deflation through _abi.svd_cv."""
+def _svd_cv(M, dense, k, method, maxit, tol, center, seed, cons, precision, test_fraction, cv_seed, patience, mask_zeros, obs, auto_rank,
+            reg=None):
+    """The cross-validated / masked call: deflation through _abi.svd_cv, or through _abi.svd_reg with reg = its further keywords."""
     if method != "deflation":
         raise _abi.BackendError("GPU SVD/PCA failed: cross-validation, auto-rank and a mask matrix need method 'deflation' on the GPU "
                                 "(got '%s')" % method)
     L1v, L2v, nn, ub = cons
     src = dense if dense is not None else (M.p, M.i, M.x, M.rows, M.cols)
-    r = _abi.svd_cv(src, k, dense=dense is not None, precision=precision, tol=tol, max_iter=maxit, center=center, seed=seed, L1=L1v,
-                    L2=L2v, nonneg=nn, upper_bound=ub, test_fraction=test_fraction, cv_seed=cv_seed, patience=patience,
-                    mask_zeros=mask_zeros, obs_mask=obs)
+    call = _abi.svd_cv if reg is None else _abi.svd_reg
+    r = call(src, k, dense=dense is not None, precision=precision, tol=tol, max_iter=maxit, center=center, seed=seed, L1=L1v,
+             L2=L2v, nonneg=nn, upper_bound=ub, test_fraction=test_fraction, cv_seed=cv_seed, patience=patience,
+             mask_zeros=mask_zeros, obs_mask=obs, **(reg or {}))
     if r["status"] != 0:
         raise _abi.BackendError("GPU SVD/PCA failed: %s" % r["error"])
     ks, kc = r["k"], r["k_computed"]

@@ -18,7 +18,13 @@ k_selected, the factors computed, and the time and rank of the numpy restatement
 pass limit, tol 1e-5), with deflation under the same constraints on the same device (what the fit cost before KSPR), and with the
 numpy restatement of KSPR from the device's Lanczos seed (tests/svd_krylov_ref.py; not the reference's C++).  One JSON line: wall
 times (best of three after a warm-up), the pass count, ms per pass (the call with the default limit minus a one-pass call, over the
-passes in between: the seed and the transfers cancel) and the relative Frobenius error of both fits."""
+passes in between: the seed and the transfers cancel) and the relative Frobenius error of both fits.
+
+--reg runs one leg only: pca(k = 6, method = "deflation") in fp32 through the Python surface, three times: plain; with L21 and
+angular; with those plus a banded Laplacian on the cell side (every cell joined to its next two, graph_lambda * lambda_max <= 0.25)
+-- the last two through rcppml_gpu_svd_reg_ex.  One JSON line: per run the wall ms (best of three after a warm-up), the total
+iterations and the ms per iteration, and the marginal ms per iteration from two fixed iteration counts (tol = 0, maxit 10 and 30:
+uploads, transposes and the per-factor work cancel), which is the figure to hold the on-terms against the plain run with."""
 import argparse
 import json
 import os
@@ -103,13 +109,42 @@ def krylov_leg(A):
                                     "not the reference's C++")), flush=True)
 
 
+def reg_leg(A):
+    import scipy.sparse as sp
+    from rcppml_amd import svd as S
+    M = sp.csc_matrix((A.x, A.i, A.p), shape=(A.rows, A.cols))
+    n = A.cols
+    W = sp.diags([np.ones(n - 1), np.ones(n - 2)], [1, 2], format="csc")
+    W = W + W.T
+    L = (sp.diags(np.asarray(W.sum(axis=1)).ravel()) - W).tocsc()
+    lam = 0.25 / float(np.max(np.abs(L).sum(axis=1)))            # the row-sum bound of lambda_max
+    runs = [("plain", dict()), ("L21+angular", dict(L21=0.1, angular=0.2)),
+            ("L21+angular+graph_V", dict(L21=0.1, angular=0.2, graph_V=L, graph_lambda=(0, lam)))]
+    rec = dict(workload="pca k=6 deflation, regularisers", precision="float", m=A.rows, n=A.cols, nnz=int(A.x.shape[0]),
+               graph_lambda=lam, runs=[])
+    for name, kw in runs:
+        call = lambda **extra: S.pca(M, k=6, method="deflation", precision="float", **kw, **extra)
+        r, ts = timed(call)
+        its = int(np.sum(r["misc"]["iters_per_factor"]))
+        (ra, ta), (rb, tb) = timed(lambda: call(tol=0.0, maxit=10)), timed(lambda: call(tol=0.0, maxit=30))
+        ia, ib = (int(np.sum(x["misc"]["iters_per_factor"])) for x in (ra, rb))
+        rec["runs"].append(dict(run=name, wall_ms=min(ts) * 1e3, wall_ms_all=[t * 1e3 for t in ts], iterations=its,
+                                ms_per_iteration=min(ts) * 1e3 / max(its, 1),
+                                marginal_ms_per_iteration=(min(tb) - min(ta)) * 1e3 / max(ib - ia, 1), d=r["d"].tolist()))
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cpu", action="store_true", help="also time the numpy restatements (slow)")
     ap.add_argument("--auto", action="store_true", help="only the pca(k = \"auto\") leg")
     ap.add_argument("--krylov", action="store_true", help="only the svd(k = 16, nonneg, method = \"krylov\") leg")
+    ap.add_argument("--reg", action="store_true", help="only the pca(k = 6, deflation) leg with L21 / angular / graph regularisation")
     args = ap.parse_args()
     A = pbmc3k()
+    if args.reg:
+        reg_leg(A)
+        return
     if args.auto:
         auto_leg(A)
         return
