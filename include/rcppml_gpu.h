@@ -454,6 +454,42 @@ RCPPML_GPU_API void rcppml_gpu_svd_krylov_dense_ex(const double* A_data, int* m,
         int* out_k_selected, int* out_passes, double* out_dw, double* out_frobenius_norm_sq, double* out_row_means,
         double* out_wall_time_ms, int* out_status);
 
+/* Randomized block SVD (rcppml_amd/csrc/ops_svd.hip, kernels_svd_rand.hip.h).  BUILD-DEFINED: the reference's CPU method
+ * randomized_svd (svd/randomized.hpp:59-241, Halko-Martinsson-Tropp), which the four rcppml_gpu_svd_pca_* entries run as Lanczos
+ * under algorithm 3.  A fixed cost and no convergence test:
+ *   sizes     p = min(max(10, k / 5), min(m, n) - k), l = k + max(p, 0) (refused above 128), q = 3 when *max_iter <= 0, else
+ *             min(*max_iter, 10).
+ *   sketch    Omega (n x l), Omega(i, j) = uniform<T>() - 0.5 from draw j n + i of the SplitMix64 stream of *seed (0: 42), filled on
+ *             the device.
+ *   steps     Y = A~ Omega; q times: Q = orth(Y), Z = orth(A~' Q), Y = A~ Z; then Q = orth(Y), Bt = A~' Q.  A~ is A, or with *center
+ *             A minus its row means (never formed: A~ X = A X - mu (1'X), A~' X = A' X - 1 (mu'X)).  orth() is CholeskyQR2 in place of
+ *             the reference's Householder QR (the thin factor is the same up to column signs, which cancel in U d V'): the l x l Gram
+ *             and its factor are fp64 in both precisions, always two rounds.  A pivot that is not above l eps(T) times its column's
+ *             Gram diagonal (or is NaN) zeroes that column of Q and the factorisation goes on: rank-deficient input is no error.
+ *   result    the eigensystem of the l x l Gram Bt'Bt on the host in fp64: d = sqrt(lambda) descending, U = Q Vb, V = Bt Vb / d (a
+ *             zero column where d = 0).  Singular values below sqrt(eps) d_1 are not resolved.  The answer is the method's
+ *             approximation of the truncated SVD, not the truncated SVD.
+ * Outputs: U (m x *k_max) and V (n x *k_max) column-major and d, all *out_k_selected = *k_max columns / values written;
+ * out_iters_per_factor[0] = q; out_row_means (m) when *center.  Two runs are bitwise equal.
+ * Refused with *out_status = -1 (rcppml_gpu_last_error), nothing written: a null pointer (the graph and obs_mask pointers aside, where
+ * null means none), *precision not RCPPML_F32 / RCPPML_F64, *k_max outside [1, min(m, n)], l above 128 (the message names l and the
+ * limit), any of L1 / L2 / nonneg / upper bound / L21 / angular set, a graph pointer with its lambda above 0, *test_fraction > 0, a
+ * non-null obs_mask_p (the reference's method supports none of them), a malformed CSC, a non-finite value, more device memory than is
+ * free, no device. */
+RCPPML_GPU_API void rcppml_gpu_svd_randomized_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+        int* precision, int* k_max, int* max_iter, int* center, int* seed, double* L1_u, double* L1_v, double* L2_u, double* L2_v,
+        int* nonneg_u, int* nonneg_v, double* ub_u, double* ub_v, double* L21_u, double* L21_v, double* angular_u, double* angular_v,
+        const int* graph_u_p, double* graph_u_lambda, const int* graph_v_p, double* graph_v_lambda, double* test_fraction,
+        const int* obs_mask_p, double* U, double* d, double* V, int* out_k_selected, int* out_iters_per_factor,
+        double* out_frobenius_norm_sq, double* out_row_means, double* out_wall_time_ms, int* out_status);
+/* The same for a column-major dense matrix, read as a full CSC (svd/randomized.hpp is one template for both). */
+RCPPML_GPU_API void rcppml_gpu_svd_randomized_dense_ex(const double* A_data, int* m, int* n,
+        int* precision, int* k_max, int* max_iter, int* center, int* seed, double* L1_u, double* L1_v, double* L2_u, double* L2_v,
+        int* nonneg_u, int* nonneg_v, double* ub_u, double* ub_v, double* L21_u, double* L21_v, double* angular_u, double* angular_v,
+        const int* graph_u_p, double* graph_u_lambda, const int* graph_v_p, double* graph_v_lambda, double* test_fraction,
+        const int* obs_mask_p, double* U, double* d, double* V, int* out_k_selected, int* out_iters_per_factor,
+        double* out_frobenius_norm_sq, double* out_row_means, double* out_wall_time_ms, int* out_status);
+
 /* Embedding assessment (rcppml_amd/csrc/ops_assess.hip): the reference plugin's rcppml_gpu_assess (src/gpu_bridge_assess.cu:358-753)
  * with its 26 pointers, called by R's assess() (R/assess.R:708-769).  embedding: n x dim row-major doubles, cast to fp32.  Seeds are
  * (unsigned)*seed plus an offset (restart r: + r; silhouette: + 100; folds: + 200), each driving std::mt19937 + std::shuffle.

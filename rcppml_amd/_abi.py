@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_bipartition_double", "rcppml_gpu_dclust_double", "rcppml_gpu_bipartition_ex", "rcppml_gpu_dclust_ex",
     "rcppml_gpu_svd_pca_double", "rcppml_gpu_svd_pca_float", "rcppml_gpu_svd_pca_dense_double", "rcppml_gpu_svd_pca_dense_float",
     "rcppml_gpu_svd_cv_ex", "rcppml_gpu_svd_cv_dense_ex", "rcppml_gpu_svd_krylov_ex", "rcppml_gpu_svd_krylov_dense_ex",
-    "rcppml_gpu_svd_reg_ex", "rcppml_gpu_svd_reg_dense_ex",
+    "rcppml_gpu_svd_reg_ex", "rcppml_gpu_svd_reg_dense_ex", "rcppml_gpu_svd_randomized_ex", "rcppml_gpu_svd_randomized_dense_ex",
     "rcppml_gpu_assess", "rcppml_gpu_assess_ex", "rcppml_gpu_knn_float", "rcppml_gpu_assess_plan",
     "rcppml_gpu_score_test_double", "rcppml_gpu_zero_inflation_double", "rcppml_gpu_dispersion_double",
     "rcppml_gpu_consensus_double", "rcppml_gpu_hclust_average_double",
@@ -1063,6 +1063,65 @@ def svd_krylov(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=
     return dict(status=st.value, error=last_error() if st.value else "", U=b["U"][:m * kb].reshape(kb, m).T,
                 V=b["V"][:n * kb].reshape(kb, n).T, d=b["d"], k=ksel.value, passes=passes.value,
                 dw=b["dw"][:max(passes.value - 1, 0)], frob=frob.value, row_means=b["row_means"], wall_ms=wall.value, buffers=b)
+
+
+RANDOMIZED_MAX_SKETCH = 128
+
+
+def randomized_sizes(m, n, k, max_iter=0):
+    """randomized.hpp:73-76: (oversampling p, sketch dimension l, power iterations q) of the randomized method."""
+    p = min(max(10, k // 5), min(m, n) - k)
+    return p, k + max(p, 0), 3 if max_iter <= 0 else min(int(max_iter), 10)
+
+
+def svd_randomized(A, k_max, *, dense=False, precision="double", max_iter=0, center=False, seed=0, buffers=None, L1=(0.0, 0.0),
+                   L2=(0.0, 0.0), nonneg=(False, False), upper_bound=(0.0, 0.0), L21=(0.0, 0.0), angular=(0.0, 0.0), graph_u=None,
+                   graph_v=None, test_fraction=0.0, obs_mask=None):
+    """The build-defined rcppml_gpu_svd_randomized_ex / rcppml_gpu_svd_randomized_dense_ex: the randomized block SVD
+    (Halko-Martinsson-Tropp).  A as in svd_pca; max_iter: the power iterations q (<= 0: 3, at most 10).  buffers: dict of
+    preallocated outputs.  Everything after buffers is what the method does not support and the entry refuses: graph_u / graph_v:
+    (p, lambda) or None, obs_mask: a column-pointer array or None.  Returns the dict of svd_pca: status, error, U (m x k_max), d,
+    V (n x k_max), k, iters, frob, row_means, wall_ms, test_loss (empty)."""
+    if dense:
+        Ad = np.asfortranarray(np.asarray(A, np.float64))
+        m, n = Ad.shape
+        head = [_np_ptr(Ad.ravel(order="F")), _ci(m), _ci(n)]
+        keep = [Ad]
+    else:
+        p, i, x, m, n = A
+        p, i, x = _csc_args(p, i, x)
+        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0])]
+        keep = [p, i, x]
+    kb = max(k_max, 1)
+    b = dict(buffers or {})
+    for key, size, dt in (("U", m * kb, np.float64), ("d", kb, np.float64), ("V", n * kb, np.float64), ("iters", kb, np.int32),
+                          ("row_means", m, np.float64)):
+        if key not in b:                # a buffer handed in is used as it is (a refused call may be shown a short one)
+            b[key] = np.zeros(size, dt)
+
+    def graph(g):
+        if g is None:
+            return [None, _cd(0.0)]
+        gp = np.ascontiguousarray(g[0], np.int32)
+        keep.append(gp)
+        return [_np_ptr(gp), _cd(g[1])]
+
+    om = None
+    if obs_mask is not None:
+        om = np.ascontiguousarray(obs_mask, np.int32)
+        keep.append(om)
+    ksel, wall, frob, st = C.c_int(0), C.c_double(0.0), C.c_double(0.0), C.c_int(-99)
+    args = head + [_ci(F32 if precision == "float" else F64), _ci(k_max), _ci(max_iter), _ci(int(bool(center))), _ci(seed),
+                   _cd(L1[0]), _cd(L1[1]), _cd(L2[0]), _cd(L2[1]), _ci(int(bool(nonneg[0]))), _ci(int(bool(nonneg[1]))),
+                   _cd(upper_bound[0]), _cd(upper_bound[1]), _cd(L21[0]), _cd(L21[1]), _cd(angular[0]), _cd(angular[1])
+                   ] + graph(graph_u) + graph(graph_v) + [
+                   _cd(test_fraction), _np_ptr(om) if om is not None else None, _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]),
+                   C.byref(ksel), _np_ptr(b["iters"]), C.byref(frob), _np_ptr(b["row_means"]), C.byref(wall), C.byref(st)]
+    assert len(args) == (35 if dense else 38)
+    getattr(lib(), "rcppml_gpu_svd_randomized_dense_ex" if dense else "rcppml_gpu_svd_randomized_ex")(*args)
+    U, V = (b[key][:rows * kb].reshape(kb, rows).T if b[key].size >= rows * kb else b[key] for key, rows in (("U", m), ("V", n)))
+    return dict(status=st.value, error=last_error() if st.value else "", U=U, V=V, d=b["d"], k=ksel.value, iters=b["iters"],
+                frob=frob.value, row_means=b["row_means"], wall_ms=wall.value, test_loss=np.zeros(0), buffers=b)
 
 
 # ----------------------------------------------------------------------------- embedding assessment (ops_assess.hip)

@@ -21,11 +21,17 @@
 // build-defined entries rcppml_gpu_svd_reg_ex / rcppml_gpu_svd_reg_dense_ex, a superset of the cv entries: a side with a term on
 // runs a chain of launches in place of its one epilogue, and with every term off the engine launches what the cv entries launch.
 //
+// The randomized block method (svd/randomized.hpp:59-241, Halko-Martinsson-Tropp; kernels: kernels_svd_rand.hip.h) runs through the
+// build-defined entries rcppml_gpu_svd_randomized_ex / rcppml_gpu_svd_randomized_dense_ex: a fixed 2q + 2 block products against
+// l = k + oversampling <= 128 vectors, CholeskyQR2 between them, and one host synchronisation for the l x l eigenproblem at the end.
+// algorithm 3 on the four reference entries still runs Lanczos.
+//
 // Centering never densifies: A'u - (mu . u) 1 and A v - mu sum(v) are scalar corrections inside the epilogues.
 #include "entry_common.hip.h"
 #include "kernels_svd.hip.h"
 #include "kernels_svd_cv.hip.h"
 #include "kernels_svd_krylov.hip.h"
+#include "kernels_svd_rand.hip.h"
 #include "kernels_svd_reg.hip.h"
 
 #include <chrono>
@@ -53,6 +59,8 @@ struct Opts {
     const int* mp = nullptr; const int* mi = nullptr; int64_t mnnz = 0;
     // the krylov entries only: KSPR (kspr), its pass limit (0: the default) and the n x k seed (null: Lanczos); max_iter stays 0
     bool kspr = false; int ks_iter = 0; const double* V0 = nullptr;
+    // the randomized entries only: the block method; max_iter is its q (<= 0: 3)
+    bool rand = false;
     // the reg entries only: L21 and angular per side, and a square graph CSC per side (p = null or lambda <= 0: none)
     double L21_u = 0, L21_v = 0, ang_u = 0, ang_v = 0;
     struct Graph {
@@ -258,11 +266,11 @@ template <class T> struct Engine {
     Engine(const Opts& o_) : o(o_), g(env_device()), s(g.s), m(o_.m), n(o_.n) {
         mu_h.assign(m, 0.0);
         if (o.dense) {
-            upload_cast<T>(g.c, o.dense, (size_t)m * n, Ad, s);
+            if (!o.rand) upload_cast<T>(g.c, o.dense, (size_t)m * n, Ad, s);
             for (int j = 0; j < n; ++j)
                 for (int i = 0; i < m; ++i) mu_h[i] += o.dense[(size_t)j * m + i];
         }
-        if (!o.dense || o.kspr) {           // KSPR reads a dense matrix as a full CSC (its Lanczos seed still runs the dense products)
+        if (!o.dense || o.kspr || o.rand) {   // the block methods read a dense matrix as a full CSC (KSPR's Lanczos seed still runs the dense products)
             const size_t nz = (size_t)std::max<int64_t>(o.nnz, 1);
             upload_ints(o.p, (size_t)n + 1, Ap, s);
             upload_ints(o.i, nz, Ai, s);
@@ -276,7 +284,7 @@ template <class T> struct Engine {
             upload_cast<T>(g.c, tmp.data(), (size_t)m, mu, s);
         }
         if (o.trains()) hold_out();
-        if (!o.dense || o.kspr) {
+        if (!o.dense || o.kspr || o.rand) {
             const size_t nz = (size_t)std::max<int64_t>(o.nnz, 1);
             grow<int>(Tp, (size_t)m + 1);
             grow<int>(Ti, nz);
@@ -813,6 +821,86 @@ template <class T> struct Engine {
         R.V = times_small(Vc, n, K, Vs);
     }
 
+    // -------------------------------------------------------------------------------------------------------- randomized
+    // svd/randomized.hpp:59-241: Y = A~ Omega, q times (Q = orth(Y), Z = orth(A~' Q), Y = A~ Z), Q = orth(Y), Bt = A~' Q, and the
+    // SVD of Bt.  orth() is CholeskyQR2 (a thin QR with positive pivots is unique up to column signs, which cancel in U d V'), and
+    // the small SVD is the eigenproblem of the l x l Gram Bt'Bt on the host in fp64: sigma = sqrt(lambda), U = Q Vb, V = Bt Vb /
+    // sigma.  Singular values below sqrt(eps) d_1 are not resolved that way, which a top-k fit does not need.  Four launches per
+    // orth(), one per product, and no host synchronisation before the final Gram.
+    void randomized(Result& R) {
+        const int K = o.k, mn = std::min(m, n);
+        const int p = std::min(std::max(10, K / 5), mn - K), l = K + std::max(p, 0);
+        const int q = o.max_iter <= 0 ? 3 : std::min(o.max_iter, 10);
+        const int lp = l > 32 ? WAVE : (int)std::max(1.0, std::exp2(std::ceil(std::log2((double)l))));
+        const int nbm = (m + RS_RB - 1) / RS_RB, nbn = (n + RS_RB - 1) / RS_RB, np = rs_np(l);
+        const double thr = (double)l * (double)std::numeric_limits<T>::epsilon();
+        DevBuf bY, bZ, bPm, bPn, bRi, bLi, bG;
+        T* Y = grow<T>(bY, (size_t)l * m);
+        T* Z = grow<T>(bZ, (size_t)l * n);
+        double* Pm = grow<double>(bPm, (size_t)nbm * np);
+        double* Pn = grow<double>(bPn, (size_t)nbn * np);
+        double* Ri = grow<double>(bRi, (size_t)l * l);
+        double* Li = grow<double>(bLi, (size_t)l * l);
+        double* G = grow<double>(bG, (size_t)l * l);
+        auto* f_omega = l <= 16 ? rs_omega_kernel<T, 1> : l <= 32 ? rs_omega_kernel<T, 2> : l <= 64 ? rs_omega_kernel<T, 4> : rs_omega_kernel<T, 8>;
+        auto* f_prod = l <= 16 ? rs_prod_kernel<T, 1> : l <= 32 ? rs_prod_kernel<T, 2> : l <= 64 ? rs_prod_kernel<T, 4> : rs_prod_kernel<T, 8>;
+        auto* f_apply = l <= 16 ? rs_apply_kernel<T, 1> : l <= 32 ? rs_apply_kernel<T, 2> : l <= 64 ? rs_apply_kernel<T, 4> : rs_apply_kernel<T, 8>;
+        auto forward = [&] {        // Y = A~ Z
+            hipLaunchKernelGGL(f_prod, dim3(nbm), dim3(WG), 0, s, (const int*)Tp.as<int>(), (const int*)Ti.as<int>(), (const T*)Tx.as<T>(),
+                               (long)m, (const T*)Z, l, lp, (const double*)Pn, nbn, mup(), o.center ? 1 : 0, Y, Pm);
+        };
+        auto backward = [&] {       // Z = A~' Y
+            hipLaunchKernelGGL(f_prod, dim3(nbn), dim3(WG), 0, s, (const int*)Ap.as<int>(), (const int*)Ai.as<int>(), (const T*)Ax.as<T>(),
+                               (long)n, (const T*)Y, l, lp, (const double*)Pm, nbm, (const T*)nullptr, o.center ? 2 : 0, Z, Pn);
+        };
+        // X <- its orthonormal factor, twice; the last apply leaves the column sums the next product's centering reads (weights wt)
+        auto orth = [&](T* X, long len, int nb, double* P, const T* wt) {
+            hipLaunchKernelGGL(rs_chol_kernel, dim3(1), dim3(WG), 0, s, (const double*)P, nb, l, thr, Ri, Li, G, 0);
+            hipLaunchKernelGGL(f_apply, dim3(nb), dim3(WG), 0, s, X, len, l, (const double*)Ri, (const T*)nullptr, 1, P);
+            hipLaunchKernelGGL(rs_chol_kernel, dim3(1), dim3(WG), 0, s, (const double*)P, nb, l, thr, Ri, Li, G, 0);
+            hipLaunchKernelGGL(f_apply, dim3(nb), dim3(WG), 0, s, X, len, l, (const double*)Ri, wt, 0, P);
+        };
+        hipLaunchKernelGGL(f_omega, dim3(nbn), dim3(WG), 0, s, Z, (long)n, l, (unsigned long long)(o.seed == 0 ? 42ull : (uint64_t)o.seed), Pn);
+        forward();
+        for (int it = 0; it < q; ++it) {
+            orth(Y, (long)m, nbm, Pm, mup());
+            backward();
+            orth(Z, (long)n, nbn, Pn, (const T*)nullptr);
+            forward();
+        }
+        orth(Y, (long)m, nbm, Pm, mup());
+        backward();                                             // Bt, not orthonormalised
+        hipLaunchKernelGGL(rs_chol_kernel, dim3(1), dim3(WG), 0, s, (const double*)Pn, nbn, l, thr, Ri, Li, G, 1);
+        HIPCHK(hipGetLastError());
+        const std::vector<double> Gh = read<double>(G, (size_t)l * l);
+        std::vector<double> Us, lam, Vb;
+        jacobi_svd(Gh, l, Us, lam, Vb);                         // G is symmetric positive semidefinite: its SVD is its eigensystem
+        const int kc = std::min(K, l);
+        R.iters.assign(1, q);
+        R.k_sel = kc;
+        R.d.resize(kc);
+        std::vector<double> wu((size_t)l * kc), wv((size_t)l * kc);
+        for (int c = 0; c < kc; ++c) {
+            const double sg = std::sqrt(std::max(lam[c], 0.0));
+            R.d[c] = sg;
+            for (int b = 0; b < l; ++b) {
+                wu[(size_t)b * kc + c] = Vb[(size_t)c * l + b];
+                wv[(size_t)b * kc + c] = sg > 0 ? Vb[(size_t)c * l + b] / sg : 0.0;
+            }
+        }
+        DevBuf dwu, dwv, ou, ov;
+        const double* Wu = upload<double>(dwu, wu.data(), wu.size(), s);
+        const double* Wv = upload<double>(dwv, wv.data(), wv.size(), s);
+        grow<T>(ou, (size_t)m * kc); grow<T>(ov, (size_t)n * kc);
+        hipLaunchKernelGGL(rs_rotate_kernel<T>, dim3(wblk(m)), dim3(WG), 0, s, (const T*)Y, (long)m, l, Wu, kc, ou.as<T>());
+        hipLaunchKernelGGL(rs_rotate_kernel<T>, dim3(wblk(n)), dim3(WG), 0, s, (const T*)Z, (long)n, l, Wv, kc, ov.as<T>());
+        HIPCHK(hipGetLastError());
+        R.U.resize((size_t)m * kc);
+        R.V.resize((size_t)n * kc);
+        download_cast<T>(g.c, ou, (size_t)m * kc, R.U.data(), s);
+        download_cast<T>(g.c, ov, (size_t)n * kc, R.V.data(), s);
+    }
+
     void run(Result& R) {
         R.row_means = mu_h;
         double f = 0;
@@ -826,7 +914,8 @@ template <class T> struct Engine {
         R.frob = f;
         R.n_test = (int)n_test;
         R.n_masked = n_masked;          // masked stored entries; every mask entry on a dense input (deflation.hpp:452-487)
-        if (o.kspr) kspr(R);
+        if (o.rand) randomized(R);
+        else if (o.kspr) kspr(R);
         else if (o.algorithm == 0) deflation(R);
         else lanczos(R);
     }
@@ -1255,5 +1344,120 @@ extern "C" void rcppml_gpu_svd_krylov_dense_ex(const double* A_data, int* m, int
         for (int64_t e = 0; e < o.nnz; ++e) i[e] = (int)(e % o.m);
         o.dense = A_data; o.p = p.data(); o.i = i.data(); o.x = A_data;
         run_ks_entry(a, o);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------------------ randomized entries
+// Build-defined: the randomized block SVD (svd/randomized.hpp:59-241), which the four reference entries run as Lanczos under
+// algorithm 3.  Every check runs before any device work, and nothing is written on a refusal.
+namespace {
+struct RsRaw {
+    int* precision; int* k_max; int* max_iter; int *center, *seed;
+    double *L1_u, *L1_v, *L2_u, *L2_v; int *nonneg_u, *nonneg_v; double *ub_u, *ub_v, *L21_u, *L21_v, *angular_u, *angular_v;
+    const int* graph_u_p; double* graph_u_lambda; const int* graph_v_p; double* graph_v_lambda; double* test_fraction;
+    const int* obs_mask_p;
+    double *U, *d, *V; int *out_k_selected, *out_iters; double *out_frobenius_norm_sq, *out_row_means, *out_wall_time_ms;
+};
+
+int rs_sketch(int m, int n, int k) {        // randomized.hpp:73-74
+    const int p = std::min(std::max(10, k / 5), std::min(m, n) - k);
+    return k + std::max(p, 0);
+}
+
+Opts make_rs_opts(const RsRaw& a, const int* m, const int* n) {
+    if (!m || !n || !a.precision || !a.k_max || !a.max_iter || !a.center || !a.seed || !a.L1_u || !a.L1_v || !a.L2_u || !a.L2_v ||
+        !a.nonneg_u || !a.nonneg_v || !a.ub_u || !a.ub_v || !a.L21_u || !a.L21_v || !a.angular_u || !a.angular_v || !a.test_fraction ||
+        !a.U || !a.d || !a.V || !a.out_k_selected || !a.out_iters || !a.out_frobenius_norm_sq || !a.out_row_means || !a.out_wall_time_ms)
+        throw std::invalid_argument("null pointer");
+    if (*a.precision != RCPPML_F32 && *a.precision != RCPPML_F64) throw std::invalid_argument("precision must be RCPPML_F32 or RCPPML_F64");
+    Opts o;
+    o.m = *m; o.n = *n; o.k = *a.k_max;
+    o.tol = 0; o.max_iter = *a.max_iter; o.center = *a.center != 0; o.seed = (unsigned)(uint32_t)*a.seed;
+    o.algorithm = 3; o.rand = true;
+    o.L1_u = *a.L1_u; o.L1_v = *a.L1_v; o.L2_u = *a.L2_u; o.L2_v = *a.L2_v; o.ub_u = *a.ub_u; o.ub_v = *a.ub_v;
+    o.nonneg_u = *a.nonneg_u != 0; o.nonneg_v = *a.nonneg_v != 0;
+    if (o.m < 1 || o.n < 1) throw std::invalid_argument("the matrix must have at least one row and one column");
+    if (o.k < 1 || o.k > std::min(o.m, o.n)) throw std::invalid_argument("k_max must be in [1, min(m, n)]");
+    const int l = rs_sketch(o.m, o.n, o.k);
+    if (l > RS_LMAX)
+        throw std::invalid_argument("the randomized method's sketch dimension l = k + oversampling = " + std::to_string(l) +
+                                    " is above the limit of " + std::to_string(RS_LMAX));
+    if (has_constraints(o))
+        throw std::invalid_argument("the randomized method does not support element constraints (L1 / L2 / nonneg / upper bound)");
+    if (*a.L21_u != 0 || *a.L21_v != 0) throw std::invalid_argument("the randomized method does not support L21");
+    if (*a.angular_u != 0 || *a.angular_v != 0) throw std::invalid_argument("the randomized method does not support angular");
+    if ((a.graph_u_p && a.graph_u_lambda && *a.graph_u_lambda > 0) || (a.graph_v_p && a.graph_v_lambda && *a.graph_v_lambda > 0))
+        throw std::invalid_argument("the randomized method does not support graph regularization");
+    if (*a.test_fraction > 0) throw std::invalid_argument("the randomized method does not support test_fraction > 0 (cross-validation / auto-rank)");
+    if (a.obs_mask_p) throw std::invalid_argument("the randomized method does not support obs_mask");
+    return o;
+}
+
+// device bytes of a fit, generously: the CSC and its transpose with the fp64 staging copy, the row means, the two l-wide blocks,
+// the rotated outputs with their fp64 staging, the block records and the small matrices
+size_t rs_bytes(const Opts& o, size_t ts) {
+    const size_t len = (size_t)o.nnz, K = (size_t)o.k, l = (size_t)rs_sketch(o.m, o.n, o.k);
+    size_t b = len * (2 * (sizeof(int) + ts) + sizeof(double)) + ((size_t)o.m + o.n + 2) * sizeof(int) + (size_t)o.m * (ts + sizeof(double));
+    b += ((size_t)o.m + o.n) * (l * ts + K * (ts + sizeof(double)));
+    b += ((size_t)o.m / RS_RB + o.n / RS_RB + 2) * rs_np((int)l) * sizeof(double);
+    return b + (3 * l * l + 2 * l * K) * sizeof(double);
+}
+
+void run_rs_entry(const RsRaw& a, const Opts& o) {
+    const bool f32 = *a.precision == RCPPML_F32;
+    device_ready(rs_bytes(o, f32 ? sizeof(float) : sizeof(double)), "the SVD");
+    const auto t0 = std::chrono::steady_clock::now();
+    Result R;
+    if (f32) { Engine<float> E(o); E.run(R); }
+    else { Engine<double> E(o); E.run(R); }
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::copy(R.U.begin(), R.U.end(), a.U);           // the first k_selected columns
+    std::copy(R.V.begin(), R.V.end(), a.V);
+    std::copy(R.d.begin(), R.d.end(), a.d);
+    std::copy(R.iters.begin(), R.iters.end(), a.out_iters);
+    *a.out_k_selected = R.k_sel;
+    *a.out_frobenius_norm_sq = R.frob;
+    if (o.center) std::copy(R.row_means.begin(), R.row_means.end(), a.out_row_means);
+    *a.out_wall_time_ms = ms;
+}
+}  // namespace
+
+#define RCPPML_SVD_RS_PARAMS                                                                                                      \
+    int *precision, int *k_max, int *max_iter, int *center, int *seed, double *L1_u, double *L1_v, double *L2_u, double *L2_v,      \
+        int *nonneg_u, int *nonneg_v, double *ub_u, double *ub_v, double *L21_u, double *L21_v, double *angular_u,                  \
+        double *angular_v, const int *graph_u_p, double *graph_u_lambda, const int *graph_v_p, double *graph_v_lambda,              \
+        double *test_fraction, const int *obs_mask_p, double *U, double *d, double *V, int *out_k_selected,                         \
+        int *out_iters_per_factor, double *out_frobenius_norm_sq, double *out_row_means, double *out_wall_time_ms, int *out_status
+#define RCPPML_SVD_RS_RAW                                                                                                         \
+    RsRaw{precision, k_max, max_iter, center, seed, L1_u, L1_v, L2_u, L2_v, nonneg_u, nonneg_v, ub_u, ub_v, L21_u, L21_v,         \
+          angular_u, angular_v, graph_u_p, graph_u_lambda, graph_v_p, graph_v_lambda, test_fraction, obs_mask_p, U, d, V,          \
+          out_k_selected, out_iters_per_factor, out_frobenius_norm_sq, out_row_means, out_wall_time_ms}
+
+extern "C" void rcppml_gpu_svd_randomized_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+                                             RCPPML_SVD_RS_PARAMS) {
+    entry_guard(out_status, [&] {
+        const RsRaw a = RCPPML_SVD_RS_RAW;
+        Opts o = make_rs_opts(a, m, n);
+        if (!nnz) throw std::invalid_argument("null pointer");
+        o.nnz = *nnz; o.p = col_ptr; o.i = row_idx; o.x = values;
+        check_csc_lenient(o.p, o.i, o.x, o.m, o.n, o.nnz);
+        all_finite(o.x, (size_t)o.nnz, "the matrix");
+        run_rs_entry(a, o);
+    });
+}
+// the dense matrix enumerated as a full CSC, as rcppml_gpu_svd_krylov_dense_ex does
+extern "C" void rcppml_gpu_svd_randomized_dense_ex(const double* A_data, int* m, int* n, RCPPML_SVD_RS_PARAMS) {
+    entry_guard(out_status, [&] {
+        const RsRaw a = RCPPML_SVD_RS_RAW;
+        Opts o = make_rs_opts(a, m, n);
+        if (!A_data) throw std::invalid_argument("null matrix");
+        o.nnz = (int64_t)o.m * o.n;
+        if (o.nnz >= INT_MAX) throw std::invalid_argument("nnz out of range");
+        all_finite(A_data, (size_t)o.nnz, "the matrix");
+        std::vector<int> p((size_t)o.n + 1), i((size_t)o.nnz);
+        for (int j = 0; j <= o.n; ++j) p[j] = (int)((int64_t)j * o.m);
+        for (int64_t e = 0; e < o.nnz; ++e) i[e] = (int)(e % o.m);
+        o.dense = A_data; o.p = p.data(); o.i = i.data(); o.x = A_data;
+        run_rs_entry(a, o);
     });
 }

@@ -24,7 +24,15 @@ passes in between: the seed and the transfers cancel) and the relative Frobenius
 angular; with those plus a banded Laplacian on the cell side (every cell joined to its next two, graph_lambda * lambda_max <= 0.25)
 -- the last two through rcppml_gpu_svd_reg_ex.  One JSON line: per run the wall ms (best of three after a warm-up), the total
 iterations and the ms per iteration, and the marginal ms per iteration from two fixed iteration counts (tol = 0, maxit 10 and 30:
-uploads, transposes and the per-factor work cancel), which is the figure to hold the on-terms against the plain run with."""
+uploads, transposes and the per-factor work cancel), which is the figure to hold the on-terms against the plain run with.
+
+--randomized runs one leg only: pca(k = 40, method = "randomized") through the Python surface (rcppml_gpu_svd_randomized_ex, 3 power
+iterations, sketch dimension 50) in fp32 and fp64, beside pca(k = 40, method = "lanczos") and beside the reference entry with
+algorithm 3 (Lanczos under the name randomized: what the same call ran before the block method existed, and what method = "auto"
+still runs at this k).  The calls alternate within one process, best of three after a warm-up each.  One JSON line: the wall times,
+the kernel launches of the randomized fit (10 q + 10: the sketch, 2 q + 2 products, 2 q + 1 orthonormalisations of four launches,
+the final Gram and two rotations), the Lanczos steps, the largest relative deviation of each d from the true singular values' top
+40 where --cpu computes them, and under --cpu the time of the numpy restatement (tests/svd_rand_ref.py; not the reference's C++)."""
 import argparse
 import json
 import os
@@ -134,14 +142,63 @@ def reg_leg(A):
     print(json.dumps(rec), flush=True)
 
 
+def randomized_leg(A, cpu):
+    import scipy.sparse as sp
+    from rcppml_amd import svd as S
+    M = sp.csc_matrix((A.x, A.i, A.p), shape=(A.rows, A.cols))
+    parts = (A.p, A.i, A.x, A.rows, A.cols)
+    k = 40
+    q = _abi.randomized_sizes(A.rows, A.cols, k)[2]
+    rec = dict(workload="pca k=40 randomized", m=A.rows, n=A.cols, nnz=int(A.x.shape[0]), sketch=_abi.randomized_sizes(A.rows, A.cols, k)[1],
+               power_iterations=q, launches=10 * q + 10, runs=[])
+    sv = None
+    if cpu:
+        import svd_rand_ref
+        dense = M.toarray()
+        t0 = time.perf_counter()
+        ref = svd_rand_ref.randomized_svd(dense, k, center=True)
+        rec["cpu_s"] = time.perf_counter() - t0
+        rec["cpu_label"] = "numpy restatement of the reference's randomized SVD in float64 (tests/svd_rand_ref.py), not the reference's C++"
+        sv = np.linalg.svd(dense - dense.mean(axis=1, keepdims=True), compute_uv=False)[:k]
+        rec["cpu_tail_below_true"] = float(1 - ref["d"][-1] / sv[-1])
+    for prec in ("float", "double"):
+        legs = [("randomized", lambda: S.pca(M, k=k, method="randomized", precision=prec)),
+                ("lanczos", lambda: S.pca(M, k=k, method="lanczos", precision=prec)),
+                ("algorithm 3 on the reference entry (Lanczos)",
+                 lambda: _abi.svd_pca(parts, k, precision=prec, tol=1e-5, max_iter=3, center=True, seed=0, algorithm=3))]
+        for _, fn in legs:
+            fn()                                                # warm-up
+        ts, out = {name: [] for name, _ in legs}, {}
+        for _ in range(3):                                      # alternate the three calls
+            for name, fn in legs:
+                t0 = time.perf_counter()
+                out[name] = fn()
+                ts[name].append(time.perf_counter() - t0)
+        for name, _ in legs:
+            r = out[name]
+            d = r["d"] if "misc" in r else r["d"][:r["k"]]
+            run = dict(run=name, precision=prec, wall_ms=min(ts[name]) * 1e3, wall_ms_all=[t * 1e3 for t in ts[name]],
+                       entry_wall_ms=r["misc"]["wall_time_ms"] if "misc" in r else r["wall_ms"],
+                       iterations=int((r["misc"]["iters_per_factor"] if "misc" in r else r["iters"])[0]), d_first=float(d[0]),
+                       d_last=float(d[-1]))
+            if sv is not None:
+                run["max_rel_d_from_true"] = float(np.max(np.abs(d - sv) / sv))
+            rec["runs"].append(run)
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cpu", action="store_true", help="also time the numpy restatements (slow)")
     ap.add_argument("--auto", action="store_true", help="only the pca(k = \"auto\") leg")
     ap.add_argument("--krylov", action="store_true", help="only the svd(k = 16, nonneg, method = \"krylov\") leg")
     ap.add_argument("--reg", action="store_true", help="only the pca(k = 6, deflation) leg with L21 / angular / graph regularisation")
+    ap.add_argument("--randomized", action="store_true", help="only the pca(k = 40, method = \"randomized\") leg")
     args = ap.parse_args()
     A = pbmc3k()
+    if args.randomized:
+        randomized_leg(A, args.cpu)
+        return
     if args.reg:
         reg_leg(A)
         return
