@@ -677,6 +677,42 @@ RCPPML_GPU_API void rcppml_gpu_zi_em_double(const int* col_ptr, const int* row_i
         int* k, const double* W_T, const double* d, const double* H, double* disp, int* loss_type, int* zi_mode, int* zi_em_iters,
         double* theta_min, double* pi, double* out_imputed, int* out_status);
 
+/* Classifier evaluation (rcppml_amd/csrc/ops_classify.hip): the device side of the reference's classify_embedding and
+ * classify_logistic (R/classifier_metrics.R:49-138, 219-291) and of their metrics (.build_eval_result, .compute_auc, :387-492).
+ * Build-defined: R does not call these entries.  Embeddings are row-major doubles (n x dim), labels int codes in [0, *n_classes).
+ * Refused (*out_status = -1, reason in rcppml_gpu_last_error, NO output buffer written): a null pointer (out_launches and row_blocks
+ * may be NULL), n_train < 1, n_test < 1, dim outside [1, 128], n_classes outside [2, 256], a label outside [0, n_classes), a
+ * non-finite value, k outside [1, n_train], distance other than 0 / 1, maxit < 1, no device, or a call that does not fit in the free
+ * device memory (the message carries the byte count).
+ *
+ * The metric outputs, shared by the three entries: out_predictions (n_test; the row argmax of the probabilities, first maximum on
+ * ties), out_confusion (n_classes x n_classes row-major int counts, rows true, columns predicted), out_precision / out_recall /
+ * out_f1 (n_classes; 0 when the denominator is 0), out_support (n_classes, the row sums), out_auc (n_classes; one-vs-rest, pairs
+ * (positive i, negative j) with s_i > s_j, or s_i = s_j and i < j, counted in 64-bit integers and divided by n_pos n_neg; 0.5 when a
+ * side is empty).
+ *
+ * rcppml_gpu_classify_metrics_ex: prob is n_test x n_classes row-major. */
+RCPPML_GPU_API void rcppml_gpu_classify_metrics_ex(const double* prob, const int* test_labels, int* n_test, int* n_classes,
+        int* out_predictions, int* out_confusion, double* out_precision, double* out_recall, double* out_f1, int* out_support,
+        double* out_auc, int* out_status);
+/* k nearest training rows of every test row (exact top-k by (fp32 squared distance, train index)); *distance 0 euclidean, 1 cosine
+ * (rows scaled to unit norm, a zero norm taken as 1).  out_votes: n_test x n_classes, neighbour label counts / k.  *out_launches
+ * (may be NULL): kernel launches of the call. */
+RCPPML_GPU_API void rcppml_gpu_classify_knn_ex(const double* train, const double* test, const int* train_labels,
+        const int* test_labels, int* n_train, int* n_test, int* dim, int* n_classes, int* k, int* distance, double* out_votes,
+        int* out_predictions, int* out_confusion, double* out_precision, double* out_recall, double* out_f1, int* out_support,
+        double* out_auc, int* out_launches, int* out_status);
+/* n_classes one-vs-rest binomial(logit) GLMs on [1 | train] by IRLS with R's glm.fit arithmetic (*maxit 25 and *epsilon 1e-8 are
+ * glm.control's), fp64, normal equations + Cholesky; a column whose pivot is <= 1e-11 x the largest diagonal entry is aliased
+ * (coefficient 0).  out_coef / out_aliased: n_classes x (dim + 1), intercept first; out_iters / out_converged / out_deviance:
+ * n_classes; out_prob: n_test x n_classes, rows divided by their sum (a zero sum taken as 1).  *row_blocks (may be NULL; 0: one
+ * per 128-row chunk): the workgroups of the per-iteration pass, a test switch -- the results do not depend on it. */
+RCPPML_GPU_API void rcppml_gpu_classify_logistic_ex(const double* train, const double* test, const int* train_labels,
+        const int* test_labels, int* n_train, int* n_test, int* dim, int* n_classes, int* maxit, double* epsilon, int* row_blocks,
+        double* out_coef, int* out_aliased, int* out_iters, int* out_converged, double* out_deviance, double* out_prob,
+        int* out_predictions, int* out_confusion, double* out_precision, double* out_recall, double* out_f1, int* out_support,
+        double* out_auc, int* out_launches, int* out_status);
+
 /* Last error text of the calling thread ("" if none). */
 RCPPML_GPU_API const char* rcppml_gpu_last_error(void);
 

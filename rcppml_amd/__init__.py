@@ -14,6 +14,8 @@ Layout (only what the path needs):
   refine.py  compute_target() / refine(): mirror of the R surface on the HIP label-guided refinement path (csrc/ops_refine.hip)
   zi.py      nmf_zi(): zero-inflated GP / NB NMF (zi = "row" / "col") on the HIP zero-inflation path (csrc/ops_zi.hip); nmf(zi = ...)
              itself still refuses, routing it here is a later change
+  classify.py classify_embedding() / classify_logistic() / classify_cv(): mirror of the R surface on the HIP classifier-evaluation
+             path (csrc/ops_classify.hip)
   als.py     one-process-per-GPU column-sharded ALS loop over torch.distributed (RCCL): Comm, ShardedALS, HipOps
   data.py    synthetic inputs (restatement of R/simulateNMF.R) and CSC helpers
 """
@@ -21,3 +23,4 @@ __version__ = "0.1.0"
 
 # the package attribute `refine` is the function from here on; the module's other names come with `from rcppml_amd.refine import ...`
 from .refine import compute_target, refine  # noqa: E402,F401
+from .classify import classify_cv, classify_embedding, classify_logistic  # noqa: E402,F401

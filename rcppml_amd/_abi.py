@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_consensus_double", "rcppml_gpu_hclust_average_double",
     "rcppml_gpu_compute_target_double", "rcppml_gpu_refine_correct_double", "rcppml_gpu_refine_wfit_double", "rcppml_gpu_refine_double",
     "rcppml_gpu_nmf_zi_double", "rcppml_gpu_zi_em_double",
+    "rcppml_gpu_classify_metrics_ex", "rcppml_gpu_classify_knn_ex", "rcppml_gpu_classify_logistic_ex",
 ]
 
 
@@ -1232,6 +1233,98 @@ def assess_plan(labels, n_classes, *, nstart=10, spc=200, folds=5, seed=42, capa
         tot = int(np.sum(np.maximum(counts[:n_classes], 0)))
         r.update(init=init[:max(nstart, 0) * n_classes].reshape(max(nstart, 0), n_classes), sil_counts=counts[:n_classes].copy(),
                  sil_samples=samples[:tot].copy(), fold_ids=folds_out[:n].copy())
+    return r
+
+
+# ----------------------------------------------------------------------------- classifier evaluation (ops_classify.hip)
+CLASSIFY_DISTANCE = {"euclidean": 0, "cosine": 1}
+_METRIC_OUT = ("predictions", "confusion", "precision", "recall", "f1", "support", "auc")
+
+
+def _metric_buffers(n_test, C, init):
+    nt, c = max(int(n_test), 1), max(int(C), 1)
+    return dict(predictions=np.full(nt, int(init), np.int32), confusion=np.full(c * c, int(init), np.int32), precision=np.full(c, init),
+                recall=np.full(c, init), f1=np.full(c, init), support=np.full(c, int(init), np.int32), auc=np.full(c, init))
+
+
+def _rows(a):
+    a = np.ascontiguousarray(a, np.float64)
+    return a[:, None] if a.ndim == 1 else a
+
+
+def classify_metrics(prob, test_labels, n_classes, *, init=-7.0, buffers=None):
+    """rcppml_gpu_classify_metrics_ex.  prob: n_test x n_classes.  Returns dict(status, error, predictions, confusion (C x C, rows
+    true), precision, recall, f1, support, auc (per class), buffers).  The outputs start at `init`; a refused call leaves them so."""
+    pr = _rows(prob)
+    tl = np.ascontiguousarray(test_labels, np.int32)
+    nt, Cn = tl.shape[0], int(n_classes)
+    if pr.shape != (nt, max(Cn, 1)) and Cn >= 1:
+        raise ValueError("prob must be n_test x n_classes")
+    b = buffers if buffers is not None else _metric_buffers(nt, Cn, init)
+    return _classify_call("rcppml_gpu_classify_metrics_ex", [_np_ptr(pr), _np_ptr(tl), _ci(nt), _ci(Cn)], b, _METRIC_OUT, [], nt, Cn,
+                          {}, (pr, tl))
+
+
+def _classify_call(name, head, b, order, tail, nt, Cn, extra_shapes, keep):
+    """keep: the input arrays, alive until the call returns."""
+    st = C.c_int(-99)
+    getattr(lib(), name)(*(head + [_np_ptr(b[k]) for k in order] + tail + [C.byref(st)]))
+    shapes = dict(predictions=(nt,), confusion=(Cn, Cn), precision=(Cn,), recall=(Cn,), f1=(Cn,), support=(Cn,), auc=(Cn,))
+    shapes.update(extra_shapes)
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=b)
+    if st.value == 0:
+        for k, shp in shapes.items():
+            r[k] = b[k][:int(np.prod(shp))].reshape(shp).copy()
+    return r
+
+
+def _classify_head(train, test, train_labels, test_labels, n_classes):
+    tr, te = _rows(train), _rows(test)
+    ltr, lte = np.ascontiguousarray(train_labels, np.int32), np.ascontiguousarray(test_labels, np.int32)
+    ntr, nte, dim = tr.shape[0], te.shape[0], tr.shape[1]
+    if te.shape[1] != dim or ltr.shape != (ntr,) or lte.shape != (nte,):
+        raise ValueError("train and test must have the same columns, and one label per row")
+    head = [_np_ptr(tr), _np_ptr(te), _np_ptr(ltr), _np_ptr(lte), _ci(ntr), _ci(nte), _ci(dim), _ci(n_classes)]
+    return head, (tr, te, ltr, lte), ntr, nte, dim
+
+
+def classify_knn(train, test, train_labels, test_labels, n_classes, k=5, distance="euclidean", *, init=-7.0, buffers=None):
+    """rcppml_gpu_classify_knn_ex: votes (n_test x C, neighbour label counts / k) and the metrics of classify_metrics, plus
+    launches.  distance: "euclidean" / "cosine" (or the raw code)."""
+    head, keep, ntr, nte, dim = _classify_head(train, test, train_labels, test_labels, n_classes)
+    Cn = int(n_classes)
+    b = buffers
+    if b is None:
+        b = _metric_buffers(nte, Cn, init)
+        b["votes"] = np.full(max(nte, 1) * max(Cn, 1), init)
+    launches = C.c_int(0)
+    head += [_ci(k), _ci(CLASSIFY_DISTANCE.get(distance, distance))]
+    r = _classify_call("rcppml_gpu_classify_knn_ex", head, b, ("votes",) + _METRIC_OUT, [C.byref(launches)], nte, Cn,
+                       dict(votes=(nte, Cn)), keep)
+    r["launches"] = launches.value
+    return r
+
+
+def classify_logistic(train, test, train_labels, test_labels, n_classes, maxit=25, epsilon=1e-8, *, row_blocks=0, init=-7.0,
+                      buffers=None):
+    """rcppml_gpu_classify_logistic_ex: coef (C x (dim + 1), intercept first), aliased, iters, converged, deviance (per class), prob
+    (n_test x C, row-normalised) and the metrics of classify_metrics, plus launches.  row_blocks: the workgroups of the
+    per-iteration pass (0: one per 128-row chunk); a test switch, the results do not depend on it."""
+    head, keep, ntr, nte, dim = _classify_head(train, test, train_labels, test_labels, n_classes)
+    Cn = int(n_classes)
+    P = dim + 1
+    b = buffers
+    if b is None:
+        b = _metric_buffers(nte, Cn, init)
+        c1 = max(Cn, 1)
+        b.update(coef=np.full(c1 * P, init), aliased=np.full(c1 * P, int(init), np.int32), iters=np.full(c1, int(init), np.int32),
+                 converged=np.full(c1, int(init), np.int32), deviance=np.full(c1, init), prob=np.full(max(nte, 1) * c1, init))
+    launches = C.c_int(0)
+    head += [_ci(maxit), _cd(epsilon), _ci(row_blocks)]
+    order = ("coef", "aliased", "iters", "converged", "deviance", "prob") + _METRIC_OUT
+    r = _classify_call("rcppml_gpu_classify_logistic_ex", head, b, order, [C.byref(launches)], nte, Cn,
+                       dict(coef=(Cn, P), aliased=(Cn, P), iters=(Cn,), converged=(Cn,), deviance=(Cn,), prob=(nte, Cn)), keep)
+    r["launches"] = launches.value
     return r
 
 

@@ -12,6 +12,7 @@
 // when duplicates push self out of its list.
 #include "entry_common.hip.h"
 #include "kernels_assess.hip.h"
+#include "knn_launch.hip.h"
 
 #include <climits>
 #include <cmath>
@@ -35,8 +36,11 @@ template <int DB> void launch_partial(const KnnArgs& a, int nsplit, size_t lds, 
     hipLaunchKernelGGL(knn_partial<DB>, grid, dim3(WAVE), lds, s, a);
 }
 
-// dQ nq x dim, dC nc x dim (device).  out: nq x kmax.  gk (device, mode 2) may be null.
-void knn_device(const float* dQ, int nq, const float* dC, int nc, int dim, int mode, const int* dgroup, const int* dgk, int k, int kmax,
+}  // namespace
+
+// dQ nq x dim, dC nc x dim (device).  out: nq x kmax.  gk (device, mode 2) may be null.  Declared in knn_launch.hip.h: the
+// classifier entries (ops_classify.hip) run the same top-k.
+void rcppml_plugin::knn_device(const float* dQ, int nq, const float* dC, int nc, int dim, int mode, const int* dgroup, const int* dgk, int k, int kmax,
                 int* d_oi, float* d_od, hipStream_t s) {
     KnnArgs a{};
     a.Q = dQ; a.C = dC; a.nq = nq; a.nc = nc; a.dim = dim; a.mode = mode; a.group = dgroup; a.gk = dgk; a.k = k; a.kmax = kmax;
@@ -72,6 +76,8 @@ void knn_device(const float* dQ, int nq, const float* dC, int nc, int dim, int m
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));   // the partial buffers are freed on return
 }
+
+namespace {
 
 // ------------------------------------------------------------------------------------------------------------ random plan
 std::vector<int> kmeans_init(int n, int K, int nstart, unsigned seed) {
