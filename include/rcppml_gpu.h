@@ -1055,6 +1055,12 @@ RCPPML_GPU_API int rcppml_hip_irls_loss(rcppml_hip_ctx* ctx, int dtype, int loss
  * (fp32 32x32x2 tiles, fp64 16x16x4 tiles) that stream A once; no BLAS library. */
 RCPPML_GPU_API int rcppml_hip_rhs_dense(rcppml_hip_ctx* ctx, int dtype, const void* A, int64_t m, int64_t n,
                                         int transposed, const void* F, int k, void* B);
+/* The launch geometry rcppml_hip_rhs_dense uses for this problem (host arithmetic, no device needed; what
+ * rcppml_hip_rhs_plan_info is to the sparse plans): out[0] = blocks of output columns, out[1] = slices the reduction is split
+ * into (1: B is written directly; > 1: per-slice partials summed in slice order), out[2] = reduction indices per slice (a
+ * multiple of the 32- (forward) or 16-index (backward) chunk; the last slice may hold fewer), out[3] = the kernels' row-tile
+ * template parameter (fp32: 1..4 tiles of 32 factor rows; fp64: 1, 2, 4 or 8 tiles of 16).  All zero for an empty problem. */
+RCPPML_GPU_API int rcppml_hip_rhs_dense_geometry(int dtype, int64_t m, int64_t n, int k, int transposed, int64_t* out);
 /* Same decoder on a byte buffer in host memory, into caller-allocated device arrays (layer 2; what the parity tests
  * call).  Format restated from streampress/sparsepress_v2.hpp:897-1090, codec/rans.hpp:128-247, codec/varint.hpp:43-52.
  * rcppml_hip_spz_info parses the 128-byte header only (host).  Both return the out_status codes above. */

@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_hip_solve_cd", "rcppml_hip_order_columns", "rcppml_hip_solve_chol", "rcppml_hip_row_norms", "rcppml_hip_apply_scaling",
     "rcppml_hip_sumsq", "rcppml_hip_loss_mse", "rcppml_hip_solve_masked", "rcppml_hip_loss_nonzeros", "rcppml_hip_loss_masked",
     "rcppml_hip_solve_irls_nb", "rcppml_hip_nb_size_update", "rcppml_hip_nb_size_update_loss", "rcppml_hip_nb_loss", "rcppml_hip_solve_irls", "rcppml_hip_rhs_plan_kind", "rcppml_hip_irls_loss", "rcppml_hip_apply_l21", "rcppml_hip_angular_posthoc", "rcppml_hip_solve_cv", "rcppml_hip_cv_test_error", "rcppml_hip_solve_cv_irls", "rcppml_hip_cv_irls_loss", "rcppml_hip_cv_gp_theta_update", "rcppml_hip_mul_rows", "rcppml_hip_apply_graph_reg", "rcppml_hip_dispersion_update", "rcppml_hip_vec_global", "rcppml_hip_spz_info", "rcppml_hip_spz_decode",
-    "rcppml_sp_read_gpu", "rcppml_sp_free_gpu", "rcppml_hip_rhs_dense", "rcppml_gpu_nmf_dense_unified_float",
+    "rcppml_sp_read_gpu", "rcppml_sp_free_gpu", "rcppml_hip_rhs_dense", "rcppml_hip_rhs_dense_geometry", "rcppml_gpu_nmf_dense_unified_float",
     "rcppml_gpu_nmf_dense_unified_double",
     "rcppml_hip_rhs_plan_create", "rcppml_hip_rhs_plan_create_indices", "rcppml_hip_rhs_plan_set_values", "rcppml_hip_rhs_plan_destroy", "rcppml_hip_rhs_plan_info", "rcppml_hip_rhs_planned",
     "rcppml_gpu_nmf_target", "rcppml_hip_axpy", "rcppml_hip_add_diag", "rcppml_hip_clip_upper",
@@ -650,12 +650,34 @@ class Context:
                                                 _dptr(H), C.c_int64(n), C.c_int(k), C.c_double(power), C.c_double(lo),
                                                 C.c_double(hi), _dptr(theta)), "dispersion_update")
 
+    def mul_rows(self, dt, X, k, ncols, d, Y):
+        """Y = diag(d) X."""
+        _chk(lib().rcppml_hip_mul_rows(self._h, C.c_int(dt), _dptr(X), C.c_int(k), C.c_int64(ncols), _dptr(d), _dptr(Y)), "mul_rows")
+
+    def axpy(self, dt, X, T, alpha, n, Y):
+        """Y = X + alpha T over n entries."""
+        _chk(lib().rcppml_hip_axpy(self._h, C.c_int(dt), _dptr(X), _dptr(T), C.c_double(alpha), C.c_int64(n), _dptr(Y)), "axpy")
+
+    def clip_upper(self, dt, X, n, ub):
+        """X = min(X, ub) over n entries, in place."""
+        _chk(lib().rcppml_hip_clip_upper(self._h, C.c_int(dt), _dptr(X), C.c_int64(n), C.c_double(ub)), "clip_upper")
+
     def vec_global(self, dt, stat, x, m):
         _chk(lib().rcppml_hip_vec_global(self._h, C.c_int(dt), C.c_int(stat), _dptr(x), C.c_int64(m)), "vec_global")
 
     def rhs_dense(self, dt, A, m, n, transposed, F, k, B):
         _chk(lib().rcppml_hip_rhs_dense(self._h, C.c_int(dt), _dptr(A), C.c_int64(m), C.c_int64(n), C.c_int(transposed), _dptr(F),
                                         C.c_int(k), _dptr(B)), "rhs_dense")
+
+    @staticmethod
+    def rhs_dense_geometry(dt, m, n, k, transposed):
+        """The launch geometry rhs_dense uses for this problem (host arithmetic only): blocks of output columns, slices of the
+        reduction (1 = B written directly, no reduce kernel), reduction indices per slice (a multiple of the 32- / 16-index chunk of
+        the forward / backward kernels) and the kernels' row-tile template parameter."""
+        out = (C.c_int64 * 4)()
+        _chk(lib().rcppml_hip_rhs_dense_geometry(C.c_int(dt), C.c_int64(m), C.c_int64(n), C.c_int(k), C.c_int(transposed), out),
+             "rhs_dense_geometry")
+        return dict(zip(("blocks", "slices", "rows_per_slice", "row_tiles"), (int(v) for v in out)))
 
     def spz_decode(self, file_bytes, d_col_ptr, d_row_idx, d_values):
         """file_bytes: uint8 numpy array (host); outputs: device int32 (n+1), int32 (nnz), float64 (nnz)."""

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import geometry_inputs as gi
 from tests.util import random_csc, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -45,6 +46,7 @@ def test_fuzz_rhs_gram_scaling(env, dtype):
         ctx.gram(dt, _dev(torch, F), k, rows, 1e-15, 0.0, dG)
         G = dG.cpu().numpy()
         assert np.array_equal(G, G.T) and rel_err(G, G_ref) < tol * 4, ("gram", k, rows)
+        gi.check_real(G, *gi.gram_hi_and_bound(F, 1e-15, torch.cuda.get_device_properties(0).multi_processor_count))          # entrywise, scaled by sqrt(G_aa G_bb)
         for norm_type in (0, 1):
             sums = torch.empty((k,), dtype=tt, device="cuda")
             ctx.row_norms(dt, _dev(torch, np.abs(F)), k, rows, norm_type, sums)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import geometry_inputs as gi
 from tests.util import load_fixture, lowrank_csc, random_csc, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -58,6 +59,9 @@ def test_gram(env, dtype, k, r):
     G = dG.cpu().numpy()
     assert np.array_equal(G, G.T), "Gram must be bitwise symmetric"
     assert rel_err(G, G_ref) < TOL[dtype] * 4
+    # entrywise, scaled by the two columns' own norms, so the column scaling cannot hide the low-index tiles behind G[k-1, k-1]:
+    # |G - G_hi|_ab <= gamma_n sqrt(G_aa G_bb) (>= gamma_n (|F|^T |F|)_ab by Cauchy-Schwarz; tests/geometry_inputs.py), plus eps on the diagonal
+    gi.check_real(G, *gi.gram_hi_and_bound(F, 1e-15, torch.cuda.get_device_properties(0).multi_processor_count))
     # eps / L2 on the diagonal
     ctx.gram(_dt(_abi, dtype), dF, k, r, 1e-15, 0.5, dG)
     G2 = dG.cpu().numpy()
