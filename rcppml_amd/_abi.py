@@ -887,6 +887,72 @@ def dclust_ex(p, i, x, m, n, *, min_samples, min_dist=0.0, max_iter=100, tol=1e-
 SVD_ALGORITHMS = {"deflation": 0, "irlba": 1, "lanczos": 2, "randomized": 3, "krylov": 4}
 
 
+def _svd_head(A, dense):
+    """(the matrix arguments every SVD entry begins with, the arrays to keep alive, m, n).  A: (p, i, x, m, n) CSC parts, or an
+    (m, n) array with dense=True (handed over column-major)."""
+    if dense:
+        Ad = np.asfortranarray(np.asarray(A, np.float64))
+        m, n = Ad.shape
+        return [_np_ptr(Ad.ravel(order="F")), _ci(m), _ci(n)], [Ad], m, n
+    p, i, x, m, n = A
+    p, i, x = _csc_args(p, i, x)
+    return [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0])], [p, i, x], m, n
+
+
+def _svd_buffers(m, n, kb, buffers, **extra):
+    """The output buffers of a call: U, d, V, row_means and the entry's further ones (name=size; iters holds ints), zeroed, with
+    the caller's buffers in their place as they are."""
+    sizes = dict(U=m * kb, d=kb, V=n * kb, row_means=m, **extra)
+    b = {key: np.zeros(size, np.int32 if key == "iters" else np.float64) for key, size in sizes.items()}
+    b.update(buffers or {})
+    return b
+
+
+def _svd_penalties(L1, L2, nonneg, upper_bound):
+    """L1_u .. ub_v: the eight element-constraint arguments, in the order every entry takes them."""
+    return [_cd(L1[0]), _cd(L1[1]), _cd(L2[0]), _cd(L2[1]), _ci(int(bool(nonneg[0]))), _ci(int(bool(nonneg[1]))),
+            _cd(upper_bound[0]), _cd(upper_bound[1])]
+
+
+def _svd_scalars(precision, k_max, tol, max_iter, center, seed, *penalties):
+    """precision .. ub_v: the scalars a build-defined entry takes after the matrix (tol=None: the entry has no tol)."""
+    return ([_ci(F32 if precision == "float" else F64), _ci(k_max)] + ([] if tol is None else [_cd(tol)]) +
+            [_ci(max_iter), _ci(int(bool(center))), _ci(seed)] + _svd_penalties(*penalties))
+
+
+def _svd_graph(g, keep, r_style=False):
+    """The six arguments of one graph, (p, i, x, dim, lambda) or None.  None hands over null pointers, or with r_style the
+    one-element arrays R hands over; a graph without entries keeps its col_ptr and hands over one-element arrays for the rest."""
+    if g is None and not r_style:
+        return [None] * 6
+    gp, gi, gx, dim, lam = g if g is not None else ([0], [], [], 0, 0.0)
+    gp, gi, gx = _csc_args(gp, gi, gx)
+    gi_arg, gx_arg = (gi, gx) if gx.shape[0] else (np.zeros(1, np.int32), np.zeros(1))
+    keep.extend([gp, gi_arg, gx_arg])
+    return [_np_ptr(gp), _np_ptr(gi_arg), _np_ptr(gx_arg), _ci(dim), _ci(gx.shape[0]), _cd(lam)]
+
+
+def _svd_mask(obs_mask, keep):
+    """The five arguments of a pattern obs-mask, (p, i, rows, cols) or None (null pointers)."""
+    if obs_mask is None:
+        return [None] * 5
+    op_, oi, rows, cols = obs_mask
+    op_ = np.ascontiguousarray(op_, np.int32)
+    oi = np.ascontiguousarray(oi, np.int32)
+    oi_arg = oi if oi.shape[0] else np.zeros(1, np.int32)
+    keep.extend([op_, oi_arg])
+    return [_np_ptr(op_), _np_ptr(oi_arg), _ci(rows), _ci(cols), _ci(oi.shape[0])]
+
+
+def _svd_result(st, b, m, n, kb, ksel, frob, wall, short_ok=False):
+    """What every wrapper returns after its call: status and error, U (m x kb) and V (n x kb) as views of their buffers (short_ok:
+    a buffer too short for that comes back as it is), d, k, frob, row_means, wall_ms and the buffers."""
+    U, V = (b[key] if short_ok and b[key].size < rows * kb else b[key][:rows * kb].reshape(kb, rows).T
+            for key, rows in (("U", m), ("V", n)))
+    return dict(status=st.value, error=last_error() if st.value else "", U=U, V=V, d=b["d"], k=ksel.value, frob=frob.value,
+                row_means=b["row_means"], wall_ms=wall.value, buffers=b)
+
+
 def svd_pca(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=200, center=False, seed=0, L1=(0.0, 0.0),
             L2=(0.0, 0.0), nonneg=(False, False), upper_bound=(0.0, 0.0), L21=(0.0, 0.0), angular=(0.0, 0.0), test_fraction=0.0,
             algorithm=0, graph_u=None, graph_v=None, obs_mask=None, robust_delta=0.0, buffers=None):
@@ -895,49 +961,23 @@ def svd_pca(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=200
     dense=True.  graph_u / graph_v: (p, i, x, dim, lambda); obs_mask: (p, i, x, rows, cols).  buffers: dict of preallocated outputs
     (tests watch what is left untouched).  Returns dict(status, error, U (m x k_max), d, V (n x k_max), k, iters, frob, row_means,
     wall_ms, test_loss)."""
-    if dense:
-        Ad = np.asfortranarray(np.asarray(A, np.float64))
-        m, n = Ad.shape
-        head = [_np_ptr(Ad.ravel(order="F")), _ci(m), _ci(n)]
-        keep = [Ad]
-    else:
-        p, i, x, m, n = A
-        p, i, x = _csc_args(p, i, x)
-        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0])]
-        keep = [p, i, x]
-    b = dict(U=np.zeros(m * k_max), d=np.zeros(k_max), V=np.zeros(n * k_max), test_loss=np.zeros(k_max),
-             iters=np.zeros(k_max, np.int32), row_means=np.zeros(m))
-    if buffers:
-        b.update(buffers)
-
-    def graph(g):
-        if g is None:
-            return [_np_ptr(np.zeros(1, np.int32)), _np_ptr(np.zeros(1, np.int32)), _np_ptr(np.zeros(1)), _ci(0), _ci(0), _cd(0.0)]
-        gp, gi, gx, dim, lam = g
-        gp, gi, gx = _csc_args(gp, gi, gx)
-        keep.extend([gp, gi, gx])
-        return [_np_ptr(gp), _np_ptr(gi), _np_ptr(gx), _ci(dim), _ci(gx.shape[0]), _cd(lam)]
-
-    if obs_mask is None:
-        om = [_np_ptr(np.zeros(1, np.int32)), _np_ptr(np.zeros(1, np.int32)), _np_ptr(np.zeros(1)), _ci(0), _ci(0), _ci(0)]
-    else:
-        op_, oi, ox, rows, cols = obs_mask
-        op_, oi, ox = _csc_args(op_, oi, ox)
-        keep.extend([op_, oi, ox])
-        om = [_np_ptr(op_), _np_ptr(oi), _np_ptr(ox), _ci(rows), _ci(cols), _ci(ox.shape[0])]
+    head, keep, m, n = _svd_head(A, dense)
+    b = _svd_buffers(m, n, k_max, buffers, test_loss=k_max, iters=k_max)      # R sizes them by k_max itself
+    op_, oi, ox, rows, cols = obs_mask if obs_mask is not None else ([0], [0], [0.0], 0, 0)      # or R's one-element placeholders
+    op_, oi, ox = _csc_args(op_, oi, ox)
+    keep.extend([op_, oi, ox])
     ksel, wall, frob, st = C.c_int(0), C.c_double(0.0), C.c_double(0.0), C.c_int(-99)
     args = head + [_ci(k_max), _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]), _cd(tol), _ci(max_iter), _ci(int(bool(center))),
-                   _ci(0), _ci(seed), _ci(0), _cd(L1[0]), _cd(L1[1]), _cd(L2[0]), _cd(L2[1]), _ci(int(bool(nonneg[0]))),
-                   _ci(int(bool(nonneg[1]))), _cd(upper_bound[0]), _cd(upper_bound[1]), _cd(L21[0]), _cd(L21[1]), _cd(angular[0]),
-                   _cd(angular[1]), _cd(test_fraction), _ci(0), _ci(5), _ci(0), _ci(algorithm)] + graph(graph_u) + graph(graph_v) + om + [
+                   _ci(0), _ci(seed), _ci(0)] + _svd_penalties(L1, L2, nonneg, upper_bound) + [
+                   _cd(L21[0]), _cd(L21[1]), _cd(angular[0]), _cd(angular[1]), _cd(test_fraction), _ci(0), _ci(5), _ci(0),
+                   _ci(algorithm)] + _svd_graph(graph_u, keep, r_style=True) + _svd_graph(graph_v, keep, r_style=True) + [
+                   _np_ptr(op_), _np_ptr(oi), _np_ptr(ox), _ci(rows), _ci(cols), _ci(ox.shape[0] if obs_mask is not None else 0),
                    C.byref(ksel), C.byref(wall), _np_ptr(b["test_loss"]), _np_ptr(b["iters"]), C.byref(frob), _np_ptr(b["row_means"]),
                    _cd(robust_delta), _ci(5), _cd(1e-4), C.byref(st)]
     assert len(args) == (58 if dense else 61)
     name = "rcppml_gpu_svd_pca_" + ("dense_" if dense else "") + ("float" if precision == "float" else "double")
     getattr(lib(), name)(*args)
-    return dict(status=st.value, error=last_error() if st.value else "", U=b["U"][:m * k_max].reshape(max(k_max, 0), m).T,
-                V=b["V"][:n * k_max].reshape(max(k_max, 0), n).T, d=b["d"], k=ksel.value, iters=b["iters"], frob=frob.value, row_means=b["row_means"],
-                wall_ms=wall.value, test_loss=b["test_loss"], buffers=b)
+    return dict(_svd_result(st, b, m, n, k_max, ksel, frob, wall), iters=b["iters"], test_loss=b["test_loss"])
 
 
 def svd_cv(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=200, center=False, seed=0, L1=(0.0, 0.0),
@@ -946,45 +986,19 @@ def svd_cv(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=200,
     """The build-defined rcppml_gpu_svd_cv_ex / rcppml_gpu_svd_cv_dense_ex: cross-validated / auto-rank and obs-masked deflation.
     A as in svd_pca; obs_mask: (p, i, rows, cols) pattern CSC or None.  buffers: dict of preallocated outputs.  Returns dict(status,
     error, U (m x k_max), d, V (n x k_max), k (selected), k_computed, test_loss, n_test, n_masked, iters, frob, row_means, wall_ms)."""
-    if dense:
-        Ad = np.asfortranarray(np.asarray(A, np.float64))
-        m, n = Ad.shape
-        head = [_np_ptr(Ad.ravel(order="F")), _ci(m), _ci(n)]
-        keep = [Ad]
-    else:
-        p, i, x, m, n = A
-        p, i, x = _csc_args(p, i, x)
-        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0])]
-        keep = [p, i, x]
+    head, keep, m, n = _svd_head(A, dense)
     kb = max(k_max, 1)
-    b = dict(U=np.zeros(m * kb), d=np.zeros(kb), V=np.zeros(n * kb), test_loss=np.zeros(kb), iters=np.zeros(kb, np.int32),
-             row_means=np.zeros(m))
-    if buffers:
-        b.update(buffers)
-    if obs_mask is None:
-        om = [None, None, None, None, None]
-    else:
-        op_, oi, rows, cols = obs_mask
-        op_ = np.ascontiguousarray(op_, np.int32)
-        oi = np.ascontiguousarray(oi, np.int32)
-        oi_arg = oi if oi.shape[0] else np.zeros(1, np.int32)
-        keep.extend([op_, oi_arg])
-        om = [_np_ptr(op_), _np_ptr(oi_arg), _ci(rows), _ci(cols), _ci(oi.shape[0])]
+    b = _svd_buffers(m, n, kb, buffers, test_loss=kb, iters=kb)
     ksel, kcomp, ntest, nmask = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
     wall, frob, st = C.c_double(0.0), C.c_double(0.0), C.c_int(-99)
-    args = head + [_ci(F32 if precision == "float" else F64), _ci(k_max), _cd(tol), _ci(max_iter), _ci(int(bool(center))), _ci(seed),
-                   _cd(L1[0]), _cd(L1[1]), _cd(L2[0]), _cd(L2[1]), _ci(int(bool(nonneg[0]))), _ci(int(bool(nonneg[1]))),
-                   _cd(upper_bound[0]), _cd(upper_bound[1]), _cd(test_fraction), _ci(cv_seed), _ci(patience),
-                   _ci(int(bool(mask_zeros)))] + om + [
-                   _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]), C.byref(ksel), C.byref(kcomp), _np_ptr(b["test_loss"]),
-                   C.byref(ntest), C.byref(nmask), _np_ptr(b["iters"]), C.byref(frob), _np_ptr(b["row_means"]), C.byref(wall),
-                   C.byref(st)]
+    args = head + _svd_scalars(precision, k_max, tol, max_iter, center, seed, L1, L2, nonneg, upper_bound) + [
+        _cd(test_fraction), _ci(cv_seed), _ci(patience), _ci(int(bool(mask_zeros)))] + _svd_mask(obs_mask, keep) + [
+        _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]), C.byref(ksel), C.byref(kcomp), _np_ptr(b["test_loss"]), C.byref(ntest),
+        C.byref(nmask), _np_ptr(b["iters"]), C.byref(frob), _np_ptr(b["row_means"]), C.byref(wall), C.byref(st)]
     assert len(args) == (39 if dense else 42)
     getattr(lib(), "rcppml_gpu_svd_cv_dense_ex" if dense else "rcppml_gpu_svd_cv_ex")(*args)
-    return dict(status=st.value, error=last_error() if st.value else "", U=b["U"][:m * kb].reshape(kb, m).T,
-                V=b["V"][:n * kb].reshape(kb, n).T, d=b["d"], k=ksel.value, k_computed=kcomp.value, test_loss=b["test_loss"],
-                n_test=ntest.value, n_masked=nmask.value, iters=b["iters"], frob=frob.value, row_means=b["row_means"],
-                wall_ms=wall.value, buffers=b)
+    return dict(_svd_result(st, b, m, n, kb, ksel, frob, wall), k_computed=kcomp.value, test_loss=b["test_loss"],
+                n_test=ntest.value, n_masked=nmask.value, iters=b["iters"])
 
 
 def svd_reg(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=200, center=False, seed=0, L1=(0.0, 0.0),
@@ -993,56 +1007,20 @@ def svd_reg(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=200
     """The build-defined rcppml_gpu_svd_reg_ex / rcppml_gpu_svd_reg_dense_ex: svd_cv plus L21, angular and graph regularisation in
     the deflation loop.  A, obs_mask, buffers and the result dict as in svd_cv; L21 / angular: (u, v); graph_u / graph_v: (p, i, x,
     dim, lambda) as svd_pca takes them, or None."""
-    if dense:
-        Ad = np.asfortranarray(np.asarray(A, np.float64))
-        m, n = Ad.shape
-        head = [_np_ptr(Ad.ravel(order="F")), _ci(m), _ci(n)]
-        keep = [Ad]
-    else:
-        p, i, x, m, n = A
-        p, i, x = _csc_args(p, i, x)
-        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0])]
-        keep = [p, i, x]
+    head, keep, m, n = _svd_head(A, dense)
     kb = max(k_max, 1)
-    b = dict(U=np.zeros(m * kb), d=np.zeros(kb), V=np.zeros(n * kb), test_loss=np.zeros(kb), iters=np.zeros(kb, np.int32),
-             row_means=np.zeros(m))
-    if buffers:
-        b.update(buffers)
-
-    def graph(g):
-        if g is None:
-            return [None] * 6
-        gp, gi, gx, dim, lam = g
-        gp, gi, gx = _csc_args(gp, gi, gx)
-        gi_arg, gx_arg = (gi, gx) if gx.shape[0] else (np.zeros(1, np.int32), np.zeros(1))
-        keep.extend([gp, gi_arg, gx_arg])
-        return [_np_ptr(gp), _np_ptr(gi_arg), _np_ptr(gx_arg), _ci(dim), _ci(gx.shape[0]), _cd(lam)]
-
-    if obs_mask is None:
-        om = [None, None, None, None, None]
-    else:
-        op_, oi, rows, cols = obs_mask
-        op_ = np.ascontiguousarray(op_, np.int32)
-        oi = np.ascontiguousarray(oi, np.int32)
-        oi_arg = oi if oi.shape[0] else np.zeros(1, np.int32)
-        keep.extend([op_, oi_arg])
-        om = [_np_ptr(op_), _np_ptr(oi_arg), _ci(rows), _ci(cols), _ci(oi.shape[0])]
+    b = _svd_buffers(m, n, kb, buffers, test_loss=kb, iters=kb)
     ksel, kcomp, ntest, nmask = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
     wall, frob, st = C.c_double(0.0), C.c_double(0.0), C.c_int(-99)
-    args = head + [_ci(F32 if precision == "float" else F64), _ci(k_max), _cd(tol), _ci(max_iter), _ci(int(bool(center))), _ci(seed),
-                   _cd(L1[0]), _cd(L1[1]), _cd(L2[0]), _cd(L2[1]), _ci(int(bool(nonneg[0]))), _ci(int(bool(nonneg[1]))),
-                   _cd(upper_bound[0]), _cd(upper_bound[1]), _cd(L21[0]), _cd(L21[1]), _cd(angular[0]), _cd(angular[1])
-                   ] + graph(graph_u) + graph(graph_v) + [
-                   _cd(test_fraction), _ci(cv_seed), _ci(patience), _ci(int(bool(mask_zeros)))] + om + [
-                   _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]), C.byref(ksel), C.byref(kcomp), _np_ptr(b["test_loss"]),
-                   C.byref(ntest), C.byref(nmask), _np_ptr(b["iters"]), C.byref(frob), _np_ptr(b["row_means"]), C.byref(wall),
-                   C.byref(st)]
+    args = head + _svd_scalars(precision, k_max, tol, max_iter, center, seed, L1, L2, nonneg, upper_bound) + [
+        _cd(L21[0]), _cd(L21[1]), _cd(angular[0]), _cd(angular[1])] + _svd_graph(graph_u, keep) + _svd_graph(graph_v, keep) + [
+        _cd(test_fraction), _ci(cv_seed), _ci(patience), _ci(int(bool(mask_zeros)))] + _svd_mask(obs_mask, keep) + [
+        _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]), C.byref(ksel), C.byref(kcomp), _np_ptr(b["test_loss"]), C.byref(ntest),
+        C.byref(nmask), _np_ptr(b["iters"]), C.byref(frob), _np_ptr(b["row_means"]), C.byref(wall), C.byref(st)]
     assert len(args) == (55 if dense else 58)
     getattr(lib(), "rcppml_gpu_svd_reg_dense_ex" if dense else "rcppml_gpu_svd_reg_ex")(*args)
-    return dict(status=st.value, error=last_error() if st.value else "", U=b["U"][:m * kb].reshape(kb, m).T,
-                V=b["V"][:n * kb].reshape(kb, n).T, d=b["d"], k=ksel.value, k_computed=kcomp.value, test_loss=b["test_loss"],
-                n_test=ntest.value, n_masked=nmask.value, iters=b["iters"], frob=frob.value, row_means=b["row_means"],
-                wall_ms=wall.value, buffers=b)
+    return dict(_svd_result(st, b, m, n, kb, ksel, frob, wall), k_computed=kcomp.value, test_loss=b["test_loss"],
+                n_test=ntest.value, n_masked=nmask.value, iters=b["iters"])
 
 
 def krylov_pass_limit(k, max_iter=0):
@@ -1055,20 +1033,9 @@ def svd_krylov(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=
     """The build-defined rcppml_gpu_svd_krylov_ex / rcppml_gpu_svd_krylov_dense_ex: the constrained block SVD (KSPR).  A as in
     svd_pca; V0: n x k_max seed or None (Lanczos).  buffers: dict of preallocated outputs.  Returns dict(status, error, U (m x k_max),
     d, V (n x k_max), k (k_actual), passes, dw (passes - 1 values), frob, row_means, wall_ms)."""
-    if dense:
-        Ad = np.asfortranarray(np.asarray(A, np.float64))
-        m, n = Ad.shape
-        head = [_np_ptr(Ad.ravel(order="F")), _ci(m), _ci(n)]
-        keep = [Ad]
-    else:
-        p, i, x, m, n = A
-        p, i, x = _csc_args(p, i, x)
-        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0])]
-        keep = [p, i, x]
+    head, keep, m, n = _svd_head(A, dense)
     kb = max(k_max, 1)
-    b = dict(U=np.zeros(m * kb), d=np.zeros(kb), V=np.zeros(n * kb), dw=np.zeros(krylov_pass_limit(kb, max_iter)), row_means=np.zeros(m))
-    if buffers:
-        b.update(buffers)
+    b = _svd_buffers(m, n, kb, buffers, dw=krylov_pass_limit(kb, max_iter))
     v0 = None
     if V0 is not None:
         v0 = np.asfortranarray(np.asarray(V0, np.float64))
@@ -1076,16 +1043,12 @@ def svd_krylov(A, k_max, *, dense=False, precision="double", tol=1e-5, max_iter=
         keep.append(v0)
     ksel, passes = C.c_int(0), C.c_int(0)
     wall, frob, st = C.c_double(0.0), C.c_double(0.0), C.c_int(-99)
-    args = head + [_ci(F32 if precision == "float" else F64), _ci(k_max), _cd(tol), _ci(max_iter), _ci(int(bool(center))), _ci(seed),
-                   _cd(L1[0]), _cd(L1[1]), _cd(L2[0]), _cd(L2[1]), _ci(int(bool(nonneg[0]))), _ci(int(bool(nonneg[1]))),
-                   _cd(upper_bound[0]), _cd(upper_bound[1]), _np_ptr(v0.ravel(order="F")) if v0 is not None else None,
-                   _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]), C.byref(ksel), C.byref(passes), _np_ptr(b["dw"]), C.byref(frob),
-                   _np_ptr(b["row_means"]), C.byref(wall), C.byref(st)]
+    args = head + _svd_scalars(precision, k_max, tol, max_iter, center, seed, L1, L2, nonneg, upper_bound) + [
+        _np_ptr(v0.ravel(order="F")) if v0 is not None else None, _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]), C.byref(ksel),
+        C.byref(passes), _np_ptr(b["dw"]), C.byref(frob), _np_ptr(b["row_means"]), C.byref(wall), C.byref(st)]
     assert len(args) == (28 if dense else 31)
     getattr(lib(), "rcppml_gpu_svd_krylov_dense_ex" if dense else "rcppml_gpu_svd_krylov_ex")(*args)
-    return dict(status=st.value, error=last_error() if st.value else "", U=b["U"][:m * kb].reshape(kb, m).T,
-                V=b["V"][:n * kb].reshape(kb, n).T, d=b["d"], k=ksel.value, passes=passes.value,
-                dw=b["dw"][:max(passes.value - 1, 0)], frob=frob.value, row_means=b["row_means"], wall_ms=wall.value, buffers=b)
+    return dict(_svd_result(st, b, m, n, kb, ksel, frob, wall), passes=passes.value, dw=b["dw"][:max(passes.value - 1, 0)])
 
 
 RANDOMIZED_MAX_SKETCH = 128
@@ -1105,22 +1068,9 @@ def svd_randomized(A, k_max, *, dense=False, precision="double", max_iter=0, cen
     preallocated outputs.  Everything after buffers is what the method does not support and the entry refuses: graph_u / graph_v:
     (p, lambda) or None, obs_mask: a column-pointer array or None.  Returns the dict of svd_pca: status, error, U (m x k_max), d,
     V (n x k_max), k, iters, frob, row_means, wall_ms, test_loss (empty)."""
-    if dense:
-        Ad = np.asfortranarray(np.asarray(A, np.float64))
-        m, n = Ad.shape
-        head = [_np_ptr(Ad.ravel(order="F")), _ci(m), _ci(n)]
-        keep = [Ad]
-    else:
-        p, i, x, m, n = A
-        p, i, x = _csc_args(p, i, x)
-        head = [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(m), _ci(n), _ci(x.shape[0])]
-        keep = [p, i, x]
+    head, keep, m, n = _svd_head(A, dense)
     kb = max(k_max, 1)
-    b = dict(buffers or {})
-    for key, size, dt in (("U", m * kb, np.float64), ("d", kb, np.float64), ("V", n * kb, np.float64), ("iters", kb, np.int32),
-                          ("row_means", m, np.float64)):
-        if key not in b:                # a buffer handed in is used as it is (a refused call may be shown a short one)
-            b[key] = np.zeros(size, dt)
+    b = _svd_buffers(m, n, kb, buffers, iters=kb)       # a buffer handed in is used as it is (a refused call may get a short one)
 
     def graph(g):
         if g is None:
@@ -1134,17 +1084,13 @@ def svd_randomized(A, k_max, *, dense=False, precision="double", max_iter=0, cen
         om = np.ascontiguousarray(obs_mask, np.int32)
         keep.append(om)
     ksel, wall, frob, st = C.c_int(0), C.c_double(0.0), C.c_double(0.0), C.c_int(-99)
-    args = head + [_ci(F32 if precision == "float" else F64), _ci(k_max), _ci(max_iter), _ci(int(bool(center))), _ci(seed),
-                   _cd(L1[0]), _cd(L1[1]), _cd(L2[0]), _cd(L2[1]), _ci(int(bool(nonneg[0]))), _ci(int(bool(nonneg[1]))),
-                   _cd(upper_bound[0]), _cd(upper_bound[1]), _cd(L21[0]), _cd(L21[1]), _cd(angular[0]), _cd(angular[1])
-                   ] + graph(graph_u) + graph(graph_v) + [
-                   _cd(test_fraction), _np_ptr(om) if om is not None else None, _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]),
-                   C.byref(ksel), _np_ptr(b["iters"]), C.byref(frob), _np_ptr(b["row_means"]), C.byref(wall), C.byref(st)]
+    args = head + _svd_scalars(precision, k_max, None, max_iter, center, seed, L1, L2, nonneg, upper_bound) + [
+        _cd(L21[0]), _cd(L21[1]), _cd(angular[0]), _cd(angular[1])] + graph(graph_u) + graph(graph_v) + [
+        _cd(test_fraction), _np_ptr(om) if om is not None else None, _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]),
+        C.byref(ksel), _np_ptr(b["iters"]), C.byref(frob), _np_ptr(b["row_means"]), C.byref(wall), C.byref(st)]
     assert len(args) == (35 if dense else 38)
     getattr(lib(), "rcppml_gpu_svd_randomized_dense_ex" if dense else "rcppml_gpu_svd_randomized_ex")(*args)
-    U, V = (b[key][:rows * kb].reshape(kb, rows).T if b[key].size >= rows * kb else b[key] for key, rows in (("U", m), ("V", n)))
-    return dict(status=st.value, error=last_error() if st.value else "", U=U, V=V, d=b["d"], k=ksel.value, iters=b["iters"],
-                frob=frob.value, row_means=b["row_means"], wall_ms=wall.value, test_loss=np.zeros(0), buffers=b)
+    return dict(_svd_result(st, b, m, n, kb, ksel, frob, wall, short_ok=True), iters=b["iters"], test_loss=np.zeros(0))
 
 
 # ----------------------------------------------------------------------------- embedding assessment (ops_assess.hip)

@@ -27,6 +27,12 @@
 // algorithm 3 on the four reference entries still runs Lanczos.
 //
 // Centering never densifies: A'u - (mu . u) 1 and A v - mu sum(v) are scalar corrections inside the epilogues.
+//
+// The host boundary of the fourteen entries is written once (section "boundary"): load_shared() / load_checked() fill the fields of
+// Opts every family shares and raise the shared refusals, attach_csc() / attach_dense() (with FullCsc for the block methods' dense
+// entries) hand the matrix over, fit() checks the device and runs Engine<float> or Engine<double> under the clock, and
+// write_shared() copies the outputs every family has.  A family adds its own pointer struct, make_*_opts, *_bytes and write_*.
+// Opts::method names what the engine runs; the reference entries' algorithm 1-4 become Method::lanczos at the boundary.
 #include "entry_common.hip.h"
 #include "kernels_svd.hip.h"
 #include "kernels_svd_cv.hip.h"
@@ -47,20 +53,25 @@ constexpr int kPoll = 8;
 int nblk(long len) { return (int)((len + CH - 1) / CH); }
 int wblk(long len) { return (int)((len + NW - 1) / NW); }
 
+// what Engine::run() runs; the reference entries' algorithm 1-4 are all lanczos
+enum class Method { deflation, lanczos, kspr, randomized };
+
+// the instantiation of a block kernel f<T, W> for w <= 128 columns: W sixteens, rounded up to a power of two
+#define RSV_BY_WIDTH(f, w) ((w) <= 16 ? f<T, 1> : (w) <= 32 ? f<T, 2> : (w) <= 64 ? f<T, 4> : f<T, 8>)
+
 struct Opts {
     int m, n, k;
     int64_t nnz;
     const int* p = nullptr; const int* i = nullptr; const double* x = nullptr;   // sparse CSC
     const double* dense = nullptr;                                              // or column-major dense
-    double tol; int max_iter; int center; unsigned seed; int algorithm;
+    double tol; int max_iter; int center; unsigned seed; Method method = Method::deflation;
     double L1_u, L1_v, L2_u, L2_v, ub_u, ub_v; int nonneg_u, nonneg_v;
     // the cv entries only: hold-out fraction (0: no CV), effective mask seed, patience, mask_zeros, obs-mask pattern CSC (or null)
     double test_fraction = 0; uint64_t cv_seed = 0; int patience = 0; int mask_zeros = 0;
     const int* mp = nullptr; const int* mi = nullptr; int64_t mnnz = 0;
-    // the krylov entries only: KSPR (kspr), its pass limit (0: the default) and the n x k seed (null: Lanczos); max_iter stays 0
-    bool kspr = false; int ks_iter = 0; const double* V0 = nullptr;
-    // the randomized entries only: the block method; max_iter is its q (<= 0: 3)
-    bool rand = false;
+    // the krylov entries only (Method::kspr): the pass limit (0: the default) and the n x k seed (null: Lanczos); max_iter stays 0.
+    // The randomized entries (Method::randomized) add no field: max_iter is the block method's q (<= 0: 3)
+    int ks_iter = 0; const double* V0 = nullptr;
     // the reg entries only: L21 and angular per side, and a square graph CSC per side (p = null or lambda <= 0: none)
     double L21_u = 0, L21_v = 0, ang_u = 0, ang_v = 0;
     struct Graph {
@@ -69,6 +80,9 @@ struct Opts {
     } gu, gv;
     bool cv() const { return test_fraction > 0; }
     bool trains() const { return cv() || mp; }      // the products read a training copy of A
+    // the products and block kernels read a CSC: the block methods read a dense matrix as a full CSC (KSPR's Lanczos seed still
+    // runs the dense products)
+    bool reads_csc() const { return !dense || method == Method::kspr || method == Method::randomized; }
 };
 
 struct Result {
@@ -266,11 +280,11 @@ template <class T> struct Engine {
     Engine(const Opts& o_) : o(o_), g(env_device()), s(g.s), m(o_.m), n(o_.n) {
         mu_h.assign(m, 0.0);
         if (o.dense) {
-            if (!o.rand) upload_cast<T>(g.c, o.dense, (size_t)m * n, Ad, s);
+            if (o.method != Method::randomized) upload_cast<T>(g.c, o.dense, (size_t)m * n, Ad, s);
             for (int j = 0; j < n; ++j)
                 for (int i = 0; i < m; ++i) mu_h[i] += o.dense[(size_t)j * m + i];
         }
-        if (!o.dense || o.kspr || o.rand) {   // the block methods read a dense matrix as a full CSC (KSPR's Lanczos seed still runs the dense products)
+        if (o.reads_csc()) {
             const size_t nz = (size_t)std::max<int64_t>(o.nnz, 1);
             upload_ints(o.p, (size_t)n + 1, Ap, s);
             upload_ints(o.i, nz, Ai, s);
@@ -284,7 +298,7 @@ template <class T> struct Engine {
             upload_cast<T>(g.c, tmp.data(), (size_t)m, mu, s);
         }
         if (o.trains()) hold_out();
-        if (!o.dense || o.kspr || o.rand) {
+        if (o.reads_csc()) {
             const size_t nz = (size_t)std::max<int64_t>(o.nnz, 1);
             grow<int>(Tp, (size_t)m + 1);
             grow<int>(Ti, nz);
@@ -748,7 +762,7 @@ template <class T> struct Engine {
                                S, it, side, last);
         };
         auto finish = [&](int nb, T* X, long len, const double* Pp, int nbh, int raw, const T* wt, const T* Xold, const int* stp, int it) {
-            auto* f = K <= 16 ? ks_finish_kernel<T, 1> : K <= 32 ? ks_finish_kernel<T, 2> : K <= 64 ? ks_finish_kernel<T, 4> : ks_finish_kernel<T, 8>;
+            auto* f = RSV_BY_WIDTH(ks_finish_kernel, K);
             hipLaunchKernelGGL(f, dim3(nb), dim3(WG), 0, s, X, len, K, Pp, nbh, eps100, raw, wt, Xold, d, PG, stp, it);
         };
         // the seed's Gram and column sums: only V of the seed is read (krylov.hpp:472-524 overwrite W and d)
@@ -842,9 +856,9 @@ template <class T> struct Engine {
         double* Ri = grow<double>(bRi, (size_t)l * l);
         double* Li = grow<double>(bLi, (size_t)l * l);
         double* G = grow<double>(bG, (size_t)l * l);
-        auto* f_omega = l <= 16 ? rs_omega_kernel<T, 1> : l <= 32 ? rs_omega_kernel<T, 2> : l <= 64 ? rs_omega_kernel<T, 4> : rs_omega_kernel<T, 8>;
-        auto* f_prod = l <= 16 ? rs_prod_kernel<T, 1> : l <= 32 ? rs_prod_kernel<T, 2> : l <= 64 ? rs_prod_kernel<T, 4> : rs_prod_kernel<T, 8>;
-        auto* f_apply = l <= 16 ? rs_apply_kernel<T, 1> : l <= 32 ? rs_apply_kernel<T, 2> : l <= 64 ? rs_apply_kernel<T, 4> : rs_apply_kernel<T, 8>;
+        auto* f_omega = RSV_BY_WIDTH(rs_omega_kernel, l);
+        auto* f_prod = RSV_BY_WIDTH(rs_prod_kernel, l);
+        auto* f_apply = RSV_BY_WIDTH(rs_apply_kernel, l);
         auto forward = [&] {        // Y = A~ Z
             hipLaunchKernelGGL(f_prod, dim3(nbm), dim3(WG), 0, s, (const int*)Tp.as<int>(), (const int*)Ti.as<int>(), (const T*)Tx.as<T>(),
                                (long)m, (const T*)Z, l, lp, (const double*)Pn, nbn, mup(), o.center ? 1 : 0, Y, Pm);
@@ -914,34 +928,110 @@ template <class T> struct Engine {
         R.frob = f;
         R.n_test = (int)n_test;
         R.n_masked = n_masked;          // masked stored entries; every mask entry on a dense input (deflation.hpp:452-487)
-        if (o.rand) randomized(R);
-        else if (o.kspr) kspr(R);
-        else if (o.algorithm == 0) deflation(R);
+        if (o.method == Method::randomized) randomized(R);
+        else if (o.method == Method::kspr) kspr(R);
+        else if (o.method == Method::deflation) deflation(R);
         else lanczos(R);
     }
 };
 
 // ------------------------------------------------------------------------------------------------------------ boundary
-struct Raw {   // the scalar pointers every entry shares, after the matrix arguments
-    int* k_max; double *U, *d, *V, *tol; int* max_iter; int *center, *verbose, *seed, *threads;
-    double *L1_u, *L1_v, *L2_u, *L2_v; int *nonneg_u, *nonneg_v; double *ub_u, *ub_v, *L21_u, *L21_v, *angular_u, *angular_v;
-    double* test_fraction; int *cv_seed, *patience, *mask_zeros, *algorithm;
-    int *graph_u_nnz; double* graph_u_lambda; int* graph_v_nnz; double* graph_v_lambda; int* obs_mask_nnz;
-    int* out_k_selected; double* out_wall_time_ms; int* out_iters_per_factor; double *out_frobenius_norm_sq, *out_row_means;
-    double* robust_delta;
+// Every check of an entry runs before any device work, and nothing is written on a refusal (status -1, the reason in
+// rcppml_gpu_last_error).  A family's checks run in this order: null pointers, precision, the shape, the k_max range (load_checked
+// / load_shared), then the family's own limit and its remaining checks (its make_*_opts), then the matrix (attach_csc /
+// attach_dense).
+struct Shared {   // the pointers every entry shares
+    int* k_max; int *center, *seed; double *L1_u, *L1_v, *L2_u, *L2_v; int *nonneg_u, *nonneg_v; double *ub_u, *ub_v;
+    double *U, *d, *V; int* out_k_selected; double *out_frobenius_norm_sq, *out_row_means, *out_wall_time_ms;
 };
+#define RCPPML_SVD_SHARED                                                                                                         \
+    Shared{k_max, center, seed, L1_u, L1_v, L2_u, L2_v, nonneg_u, nonneg_v, ub_u, ub_v, U, d, V, out_k_selected,                  \
+           out_frobenius_norm_sq, out_row_means, out_wall_time_ms}
 
-Opts make_opts(const Raw& a, int m, int n) {
+// The shared fields of Opts.  The four reference entries call this as it is: they stay R-shaped, without a null check.
+Opts load_shared(const Shared& a, int m, int n) {
     Opts o;
     o.m = m; o.n = n; o.k = *a.k_max;
-    o.tol = *a.tol; o.max_iter = *a.max_iter; o.center = *a.center != 0; o.seed = (unsigned)(uint32_t)*a.seed;
-    o.algorithm = a.algorithm ? *a.algorithm : 0;
+    o.center = *a.center != 0; o.seed = (unsigned)(uint32_t)*a.seed;
     o.L1_u = *a.L1_u; o.L1_v = *a.L1_v; o.L2_u = *a.L2_u; o.L2_v = *a.L2_v; o.ub_u = *a.ub_u; o.ub_v = *a.ub_v;
     o.nonneg_u = *a.nonneg_u != 0; o.nonneg_v = *a.nonneg_v != 0;
     if (m < 1 || n < 1) throw std::invalid_argument("the matrix must have at least one row and one column");
     if (o.k < 1 || o.k > std::min(m, n)) throw std::invalid_argument("k_max must be in [1, min(m, n)]");
+    return o;
+}
+// The build-defined entries: the null check (own_null: one of the family's own pointers is null) and the precision come first.
+Opts load_checked(const Shared& a, const int* m, const int* n, const int* precision, bool own_null) {
+    if (own_null || !m || !n || !precision || !a.k_max || !a.center || !a.seed || !a.L1_u || !a.L1_v || !a.L2_u || !a.L2_v ||
+        !a.nonneg_u || !a.nonneg_v || !a.ub_u || !a.ub_v || !a.U || !a.d || !a.V || !a.out_k_selected || !a.out_frobenius_norm_sq ||
+        !a.out_row_means || !a.out_wall_time_ms)
+        throw std::invalid_argument("null pointer");
+    if (*precision != RCPPML_F32 && *precision != RCPPML_F64)
+        throw std::invalid_argument("precision must be RCPPML_F32 or RCPPML_F64");
+    return load_shared(a, *m, *n);
+}
+
+void attach_csc(Opts& o, const int* col_ptr, const int* row_idx, const double* values, int64_t nnz) {
+    o.nnz = nnz; o.p = col_ptr; o.i = row_idx; o.x = values;
+    check_csc_lenient(o.p, o.i, o.x, o.m, o.n, o.nnz);
+}
+void attach_dense(Opts& o, const double* A) {
+    if (!A) throw std::invalid_argument("null matrix");
+    o.nnz = (int64_t)o.m * o.n; o.dense = A;
+}
+// An attached dense matrix enumerated as a full CSC too, as the reference's bridge does for krylov: what the block methods read.
+struct FullCsc {
+    std::vector<int> p, i;
+    void attach(Opts& o) {
+        if (o.nnz >= INT_MAX) throw std::invalid_argument("nnz out of range");
+        p.resize((size_t)o.n + 1); i.resize((size_t)o.nnz);
+        for (int j = 0; j <= o.n; ++j) p[j] = (int)((int64_t)j * o.m);
+        for (int64_t e = 0; e < o.nnz; ++e) i[e] = (int)(e % o.m);
+        o.p = p.data(); o.i = i.data(); o.x = o.dense;
+    }
+};
+
+struct Fit { Result R; double ms; };
+Fit timed_run(const Opts& o, bool f32) {
+    Fit f;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (f32) { Engine<float> E(o); E.run(f.R); }
+    else { Engine<double> E(o); E.run(f.R); }
+    f.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return f;
+}
+// The build-defined entries: the device and its free memory (need: a family's *_bytes estimate) are checked before the clock
+// starts.
+Fit fit(const Opts& o, int precision, size_t (*need)(const Opts&, size_t)) {
+    const bool f32 = precision == RCPPML_F32;
+    device_ready(need(o, f32 ? sizeof(float) : sizeof(double)), "the SVD");
+    return timed_run(o, f32);
+}
+
+void write_shared(const Shared& a, const Opts& o, const Fit& f) {
+    std::copy(f.R.U.begin(), f.R.U.end(), a.U);           // U: m x k_max, the first k_selected columns written
+    std::copy(f.R.V.begin(), f.R.V.end(), a.V);
+    std::copy(f.R.d.begin(), f.R.d.end(), a.d);
+    *a.out_k_selected = f.R.k_sel;
+    *a.out_frobenius_norm_sq = f.R.frob;
+    if (o.center) std::copy(f.R.row_means.begin(), f.R.row_means.end(), a.out_row_means);
+    *a.out_wall_time_ms = f.ms;
+}
+
+// ------------------------------------------------------------------------------------------------------------ reference entries
+struct Raw {   // what only the four reference entries take (and read)
+    double* tol; int* max_iter; double *L21_u, *L21_v, *angular_u, *angular_v;
+    double* test_fraction; int* algorithm;
+    int *graph_u_nnz; double* graph_u_lambda; int* graph_v_nnz; double* graph_v_lambda; int* obs_mask_nnz;
+    int* out_iters_per_factor; double* robust_delta;
+};
+
+Opts make_opts(const Shared& s, const Raw& a, int m, int n) {
+    Opts o = load_shared(s, m, n);
+    o.tol = *a.tol; o.max_iter = *a.max_iter;
+    const int algorithm = a.algorithm ? *a.algorithm : 0;
     if (o.k + 2 > NPMAX) throw std::invalid_argument("k_max above " + std::to_string(NPMAX - 2) + " is not supported");
-    if (o.algorithm < 0 || o.algorithm > 4) throw std::invalid_argument("algorithm must be 0 (deflation) .. 4 (krylov)");
+    if (algorithm < 0 || algorithm > 4) throw std::invalid_argument("algorithm must be 0 (deflation) .. 4 (krylov)");
+    o.method = algorithm == 0 ? Method::deflation : Method::lanczos;
     if (*a.test_fraction > 0) throw std::invalid_argument("test_fraction > 0 (cross-validation / auto-rank) is not supported on the GPU");
     if (a.obs_mask_nnz && *a.obs_mask_nnz > 0) throw std::invalid_argument("obs_mask is not supported on the GPU");
     if ((a.graph_u_nnz && *a.graph_u_nnz > 0 && *a.graph_u_lambda > 0) || (a.graph_v_nnz && *a.graph_v_nnz > 0 && *a.graph_v_lambda > 0))
@@ -950,36 +1040,34 @@ Opts make_opts(const Raw& a, int m, int n) {
     if ((a.angular_u && *a.angular_u != 0) || (a.angular_v && *a.angular_v != 0))
         throw std::invalid_argument("angular is not supported on the GPU");
     if (a.robust_delta && *a.robust_delta > 0) throw std::invalid_argument("robust SVD (robust_delta > 0) is not supported on the GPU");
-    if (o.algorithm != 0 && has_constraints(o))
+    if (o.method != Method::deflation && has_constraints(o))
         throw std::invalid_argument("element constraints (L1 / L2 / nonneg / upper bound) need algorithm 0 (deflation) on the GPU");
-    if (o.algorithm == 0 && o.max_iter < 1) throw std::invalid_argument("deflation needs max_iter >= 1");
+    if (o.method == Method::deflation && o.max_iter < 1) throw std::invalid_argument("deflation needs max_iter >= 1");
     if (!(o.tol >= 0)) throw std::invalid_argument("tol must be non-negative");
     return o;
 }
 
-void write_out(const Raw& a, const Opts& o, const Result& R, double ms) {
-    const int K = o.k;
-    std::copy(R.U.begin(), R.U.end(), a.U);           // U: m x k_max, the first k_selected columns written
-    std::copy(R.V.begin(), R.V.end(), a.V);
-    std::copy(R.d.begin(), R.d.end(), a.d);
-    for (int c = 0; c < (int)R.iters.size() && c < K; ++c) a.out_iters_per_factor[c] = R.iters[c];
-    *a.out_k_selected = R.k_sel;
-    *a.out_frobenius_norm_sq = R.frob;
-    if (o.center) std::copy(R.row_means.begin(), R.row_means.end(), a.out_row_means);
-    *a.out_wall_time_ms = ms;
+// the reference entries make no device_ready() call
+void run_entry(const Shared& s, const Raw& a, const Opts& o, bool f32) {
+    const Fit f = timed_run(o, f32);
+    write_shared(s, o, f);
+    for (int c = 0; c < (int)f.R.iters.size() && c < o.k; ++c) a.out_iters_per_factor[c] = f.R.iters[c];
 }
-
-template <class T> void run_entry(const Raw& a, Opts o) {
-    const auto t0 = std::chrono::steady_clock::now();
-    Result R;
-    {
-        Engine<T> E(o);
-        E.run(R);
-    }
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    write_out(a, o, R, ms);
+void svd_sparse(bool f32, const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz, const Shared& s,
+                const Raw& a, int* out_status) {
+    entry_guard(out_status, [&] {
+        Opts o = make_opts(s, a, *m, *n);
+        attach_csc(o, col_ptr, row_idx, values, *nnz);
+        run_entry(s, a, o, f32);
+    });
 }
-
+void svd_dense(bool f32, const double* A, int* m, int* n, const Shared& s, const Raw& a, int* out_status) {
+    entry_guard(out_status, [&] {
+        Opts o = make_opts(s, a, *m, *n);
+        attach_dense(o, A);
+        run_entry(s, a, o, f32);
+    });
+}
 }  // namespace
 
 #define RCPPML_SVD_PARAMS                                                                                                         \
@@ -993,81 +1081,44 @@ template <class T> void run_entry(const Raw& a, Opts o) {
         double *out_wall_time_ms, double *out_test_loss, int *out_iters_per_factor, double *out_frobenius_norm_sq,                  \
         double *out_row_means, double *robust_delta, int *irls_max_iter, double *irls_tol, int *out_status
 #define RCPPML_SVD_RAW                                                                                                            \
-    Raw{k_max, U, d, V, tol, max_iter, center, verbose, seed, threads, L1_u, L1_v, L2_u, L2_v, nonneg_u, nonneg_v, ub_u, ub_v,    \
-        L21_u, L21_v, angular_u, angular_v, test_fraction, cv_seed, patience, mask_zeros, algorithm, graph_u_nnz,                 \
-        graph_u_lambda_val, graph_v_nnz, graph_v_lambda_val, obs_mask_nnz, out_k_selected, out_wall_time_ms,                      \
-        out_iters_per_factor, out_frobenius_norm_sq, out_row_means, robust_delta}
-template <class T>
-static void svd_sparse(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz, const Raw& a,
-                       int* out_status) {
-    entry_guard(out_status, [&] {
-        Opts o = make_opts(a, *m, *n);
-        o.nnz = *nnz; o.p = col_ptr; o.i = row_idx; o.x = values;
-        check_csc_lenient(o.p, o.i, o.x, o.m, o.n, o.nnz);
-        run_entry<T>(a, o);
-    });
-}
-template <class T>
-static void svd_dense(const double* A, int* m, int* n, const Raw& a, int* out_status) {
-    entry_guard(out_status, [&] {
-        Opts o = make_opts(a, *m, *n);
-        if (!A) throw std::invalid_argument("null matrix");
-        o.nnz = (int64_t)*m * *n; o.dense = A;
-        run_entry<T>(a, o);
-    });
-}
+    Raw{tol, max_iter, L21_u, L21_v, angular_u, angular_v, test_fraction, algorithm, graph_u_nnz, graph_u_lambda_val, graph_v_nnz, \
+        graph_v_lambda_val, obs_mask_nnz, out_iters_per_factor, robust_delta}
 
 extern "C" void rcppml_gpu_svd_pca_double(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
                                           RCPPML_SVD_PARAMS) {
-    (void)out_test_loss; (void)irls_max_iter; (void)irls_tol;
-    svd_sparse<double>(col_ptr, row_idx, values, m, n, nnz, RCPPML_SVD_RAW, out_status);
+    svd_sparse(false, col_ptr, row_idx, values, m, n, nnz, RCPPML_SVD_SHARED, RCPPML_SVD_RAW, out_status);
 }
 extern "C" void rcppml_gpu_svd_pca_float(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
                                          RCPPML_SVD_PARAMS) {
-    (void)out_test_loss; (void)irls_max_iter; (void)irls_tol;
-    svd_sparse<float>(col_ptr, row_idx, values, m, n, nnz, RCPPML_SVD_RAW, out_status);
+    svd_sparse(true, col_ptr, row_idx, values, m, n, nnz, RCPPML_SVD_SHARED, RCPPML_SVD_RAW, out_status);
 }
 extern "C" void rcppml_gpu_svd_pca_dense_double(const double* A_data, int* m, int* n, RCPPML_SVD_PARAMS) {
-    (void)out_test_loss; (void)irls_max_iter; (void)irls_tol;
-    svd_dense<double>(A_data, m, n, RCPPML_SVD_RAW, out_status);
+    svd_dense(false, A_data, m, n, RCPPML_SVD_SHARED, RCPPML_SVD_RAW, out_status);
 }
 extern "C" void rcppml_gpu_svd_pca_dense_float(const double* A_data, int* m, int* n, RCPPML_SVD_PARAMS) {
-    (void)out_test_loss; (void)irls_max_iter; (void)irls_tol;
-    svd_dense<float>(A_data, m, n, RCPPML_SVD_RAW, out_status);
+    svd_dense(true, A_data, m, n, RCPPML_SVD_SHARED, RCPPML_SVD_RAW, out_status);
 }
 
-// ------------------------------------------------------------------------------------------------------------ cv entries
-// Build-defined: cross-validated / auto-rank and obs-masked deflation (the four entries above refuse both).  Every check runs
-// before any device work, and nothing is written on a refusal.
+// ------------------------------------------------------------------------------------------------------------ cv and reg entries
+// Build-defined.  cv: cross-validated / auto-rank and obs-masked deflation (the four entries above refuse both).  reg: the cv
+// entries plus L21, angular and a graph per side (refused above too); with every new term off it is the cv entry, launch for
+// launch.
 namespace {
 struct CvRaw {
-    int* precision; int* k_max; double* tol; int* max_iter; int *center, *seed;
-    double *L1_u, *L1_v, *L2_u, *L2_v; int *nonneg_u, *nonneg_v; double *ub_u, *ub_v;
-    double* test_fraction; int *cv_seed, *patience, *mask_zeros;
+    double* tol; int* max_iter; double* test_fraction; int *cv_seed, *patience, *mask_zeros;
     const int *obs_mask_p, *obs_mask_i; int *obs_mask_rows, *obs_mask_cols, *obs_mask_nnz;
-    double *U, *d, *V; int *out_k_selected, *out_k_computed; double* out_test_loss; int *out_n_test, *out_n_masked;
-    int* out_iters_per_factor; double *out_frobenius_norm_sq, *out_row_means, *out_wall_time_ms;
+    int* out_k_computed; double* out_test_loss; int *out_n_test, *out_n_masked, *out_iters_per_factor;
 };
 
-Opts make_cv_opts(const CvRaw& a, const int* m, const int* n) {
-    if (!m || !n || !a.precision || !a.k_max || !a.tol || !a.max_iter || !a.center || !a.seed || !a.L1_u || !a.L1_v || !a.L2_u ||
-        !a.L2_v || !a.nonneg_u || !a.nonneg_v || !a.ub_u || !a.ub_v || !a.test_fraction || !a.cv_seed || !a.patience || !a.mask_zeros ||
-        !a.U || !a.d || !a.V || !a.out_k_selected || !a.out_k_computed || !a.out_test_loss || !a.out_n_test || !a.out_n_masked ||
-        !a.out_iters_per_factor || !a.out_frobenius_norm_sq || !a.out_row_means || !a.out_wall_time_ms)
-        throw std::invalid_argument("null pointer");
-    if (*a.precision != RCPPML_F32 && *a.precision != RCPPML_F64) throw std::invalid_argument("precision must be RCPPML_F32 or RCPPML_F64");
-    Opts o;
-    o.m = *m; o.n = *n; o.k = *a.k_max;
-    o.tol = *a.tol; o.max_iter = *a.max_iter; o.center = *a.center != 0; o.seed = (unsigned)(uint32_t)*a.seed;
-    o.algorithm = 0;
-    o.L1_u = *a.L1_u; o.L1_v = *a.L1_v; o.L2_u = *a.L2_u; o.L2_v = *a.L2_v; o.ub_u = *a.ub_u; o.ub_v = *a.ub_v;
-    o.nonneg_u = *a.nonneg_u != 0; o.nonneg_v = *a.nonneg_v != 0;
+Opts make_cv_opts(const Shared& s, const CvRaw& a, const int* m, const int* n, const int* precision) {
+    const bool own_null = !a.tol || !a.max_iter || !a.test_fraction || !a.cv_seed || !a.patience || !a.mask_zeros ||
+                          !a.out_k_computed || !a.out_test_loss || !a.out_n_test || !a.out_n_masked || !a.out_iters_per_factor;
+    Opts o = load_checked(s, m, n, precision, own_null);
+    o.tol = *a.tol; o.max_iter = *a.max_iter;
     o.test_fraction = *a.test_fraction; o.patience = *a.patience; o.mask_zeros = *a.mask_zeros != 0;
     // core/svd_config.hpp:149-151
     const uint32_t cs = (uint32_t)*a.cv_seed;
     o.cv_seed = cs != 0 ? cs : (o.seed != 0 ? (uint32_t)(o.seed ^ 0xBEEFu) : 42u);
-    if (o.m < 1 || o.n < 1) throw std::invalid_argument("the matrix must have at least one row and one column");
-    if (o.k < 1 || o.k > std::min(o.m, o.n)) throw std::invalid_argument("k_max must be in [1, min(m, n)]");
     if (o.k + 2 > NPMAX) throw std::invalid_argument("k_max above " + std::to_string(NPMAX - 2) + " is not supported");
     if (o.max_iter < 1) throw std::invalid_argument("deflation needs max_iter >= 1");
     if (o.patience < 1) throw std::invalid_argument("patience must be >= 1");
@@ -1095,68 +1146,15 @@ size_t cv_bytes(const Opts& o, size_t ts) {
     return b;
 }
 
-void run_fit_entry(const CvRaw& a, const Opts& o, size_t (*bytes)(const Opts&, size_t)) {
-    const bool f32 = *a.precision == RCPPML_F32;
-    device_ready(bytes(o, f32 ? sizeof(float) : sizeof(double)), "the SVD");
-    const auto t0 = std::chrono::steady_clock::now();
-    Result R;
-    if (f32) { Engine<float> E(o); E.run(R); }
-    else { Engine<double> E(o); E.run(R); }
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    std::copy(R.U.begin(), R.U.end(), a.U);           // the first k_selected columns
-    std::copy(R.V.begin(), R.V.end(), a.V);
-    std::copy(R.d.begin(), R.d.end(), a.d);
-    std::copy(R.iters.begin(), R.iters.end(), a.out_iters_per_factor);
-    std::copy(R.test_loss.begin(), R.test_loss.end(), a.out_test_loss);
-    *a.out_k_selected = R.k_sel;
-    *a.out_k_computed = R.k_computed;
-    *a.out_n_test = R.n_test;
-    *a.out_n_masked = (int)R.n_masked;
-    *a.out_frobenius_norm_sq = R.frob;
-    if (o.center) std::copy(R.row_means.begin(), R.row_means.end(), a.out_row_means);
-    *a.out_wall_time_ms = ms;
-}
-void run_cv_entry(const CvRaw& a, const Opts& o) { run_fit_entry(a, o, cv_bytes); }
-}  // namespace
-
-#define RCPPML_SVD_CV_PARAMS                                                                                                      \
-    int *precision, int *k_max, double *tol, int *max_iter, int *center, int *seed, double *L1_u, double *L1_v, double *L2_u,       \
-        double *L2_v, int *nonneg_u, int *nonneg_v, double *ub_u, double *ub_v, double *test_fraction, int *cv_seed, int *patience, \
-        int *mask_zeros, const int *obs_mask_p, const int *obs_mask_i, int *obs_mask_rows, int *obs_mask_cols, int *obs_mask_nnz,   \
-        double *U, double *d, double *V, int *out_k_selected, int *out_k_computed, double *out_test_loss, int *out_n_test,          \
-        int *out_n_masked, int *out_iters_per_factor, double *out_frobenius_norm_sq, double *out_row_means,                         \
-        double *out_wall_time_ms, int *out_status
-#define RCPPML_SVD_CV_RAW                                                                                                         \
-    CvRaw{precision, k_max, tol, max_iter, center, seed, L1_u, L1_v, L2_u, L2_v, nonneg_u, nonneg_v, ub_u, ub_v, test_fraction,   \
-          cv_seed, patience, mask_zeros, obs_mask_p, obs_mask_i, obs_mask_rows, obs_mask_cols, obs_mask_nnz, U, d, V,              \
-          out_k_selected, out_k_computed, out_test_loss, out_n_test, out_n_masked, out_iters_per_factor, out_frobenius_norm_sq,    \
-          out_row_means, out_wall_time_ms}
-
-extern "C" void rcppml_gpu_svd_cv_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
-                                     RCPPML_SVD_CV_PARAMS) {
-    entry_guard(out_status, [&] {
-        const CvRaw a = RCPPML_SVD_CV_RAW;
-        Opts o = make_cv_opts(a, m, n);
-        if (!nnz) throw std::invalid_argument("null pointer");
-        o.nnz = *nnz; o.p = col_ptr; o.i = row_idx; o.x = values;
-        check_csc_lenient(o.p, o.i, o.x, o.m, o.n, o.nnz);
-        run_cv_entry(a, o);
-    });
-}
-extern "C" void rcppml_gpu_svd_cv_dense_ex(const double* A_data, int* m, int* n, RCPPML_SVD_CV_PARAMS) {
-    entry_guard(out_status, [&] {
-        const CvRaw a = RCPPML_SVD_CV_RAW;
-        Opts o = make_cv_opts(a, m, n);
-        if (!A_data) throw std::invalid_argument("null matrix");
-        o.nnz = (int64_t)o.m * o.n; o.dense = A_data;
-        run_cv_entry(a, o);
-    });
+void write_cv(const Shared& s, const CvRaw& a, const Opts& o, const Fit& f) {
+    write_shared(s, o, f);
+    std::copy(f.R.iters.begin(), f.R.iters.end(), a.out_iters_per_factor);
+    std::copy(f.R.test_loss.begin(), f.R.test_loss.end(), a.out_test_loss);
+    *a.out_k_computed = f.R.k_computed;
+    *a.out_n_test = f.R.n_test;
+    *a.out_n_masked = (int)f.R.n_masked;
 }
 
-// ------------------------------------------------------------------------------------------------------------ reg entries
-// Build-defined: the cv entries plus L21, angular and a graph per side (the four reference entries refuse all three).  Every check
-// runs before any device work, and nothing is written on a refusal.  With every new term off this is the cv entry, launch for launch.
-namespace {
 struct RegRaw {
     double *L21_u, *L21_v, *angular_u, *angular_v;
     const int *graph_u_p, *graph_u_i; const double* graph_u_x; int *graph_u_dim, *graph_u_nnz; double* graph_u_lambda;
@@ -1184,6 +1182,7 @@ Opts::Graph make_graph(const int* p, const int* i, const double* x, const int* d
     return gr;
 }
 
+// Unlike every other family's own checks, these run after the matrix is attached and checked: a bad CSC or a null matrix wins.
 void add_reg_opts(Opts& o, const RegRaw& r) {
     if (!r.L21_u || !r.L21_v || !r.angular_u || !r.angular_v) throw std::invalid_argument("null pointer");
     o.L21_u = *r.L21_u; o.L21_v = *r.L21_v; o.ang_u = *r.angular_u; o.ang_v = *r.angular_v;
@@ -1203,8 +1202,39 @@ size_t reg_bytes(const Opts& o, size_t ts) {
     b += 2 * (size_t)std::max(nblk(o.m), nblk(o.n)) * ((size_t)o.k + 2) * ts + (size_t)std::max(o.m, o.n) * ts;
     return b;
 }
-void run_reg_entry(const CvRaw& a, const Opts& o) { run_fit_entry(a, o, reg_bytes); }
 }  // namespace
+
+#define RCPPML_SVD_CV_PARAMS                                                                                                      \
+    int *precision, int *k_max, double *tol, int *max_iter, int *center, int *seed, double *L1_u, double *L1_v, double *L2_u,       \
+        double *L2_v, int *nonneg_u, int *nonneg_v, double *ub_u, double *ub_v, double *test_fraction, int *cv_seed, int *patience, \
+        int *mask_zeros, const int *obs_mask_p, const int *obs_mask_i, int *obs_mask_rows, int *obs_mask_cols, int *obs_mask_nnz,   \
+        double *U, double *d, double *V, int *out_k_selected, int *out_k_computed, double *out_test_loss, int *out_n_test,          \
+        int *out_n_masked, int *out_iters_per_factor, double *out_frobenius_norm_sq, double *out_row_means,                         \
+        double *out_wall_time_ms, int *out_status
+#define RCPPML_SVD_CV_RAW                                                                                                         \
+    CvRaw{tol, max_iter, test_fraction, cv_seed, patience, mask_zeros, obs_mask_p, obs_mask_i, obs_mask_rows, obs_mask_cols,      \
+          obs_mask_nnz, out_k_computed, out_test_loss, out_n_test, out_n_masked, out_iters_per_factor}
+
+extern "C" void rcppml_gpu_svd_cv_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+                                     RCPPML_SVD_CV_PARAMS) {
+    entry_guard(out_status, [&] {
+        const Shared s = RCPPML_SVD_SHARED;
+        const CvRaw a = RCPPML_SVD_CV_RAW;
+        Opts o = make_cv_opts(s, a, m, n, precision);
+        if (!nnz) throw std::invalid_argument("null pointer");
+        attach_csc(o, col_ptr, row_idx, values, *nnz);
+        write_cv(s, a, o, fit(o, *precision, cv_bytes));
+    });
+}
+extern "C" void rcppml_gpu_svd_cv_dense_ex(const double* A_data, int* m, int* n, RCPPML_SVD_CV_PARAMS) {
+    entry_guard(out_status, [&] {
+        const Shared s = RCPPML_SVD_SHARED;
+        const CvRaw a = RCPPML_SVD_CV_RAW;
+        Opts o = make_cv_opts(s, a, m, n, precision);
+        attach_dense(o, A_data);
+        write_cv(s, a, o, fit(o, *precision, cv_bytes));
+    });
+}
 
 #define RCPPML_SVD_REG_PARAMS                                                                                                     \
     int *precision, int *k_max, double *tol, int *max_iter, int *center, int *seed, double *L1_u, double *L1_v, double *L2_u,       \
@@ -1222,51 +1252,38 @@ void run_reg_entry(const CvRaw& a, const Opts& o) { run_fit_entry(a, o, reg_byte
 extern "C" void rcppml_gpu_svd_reg_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
                                       RCPPML_SVD_REG_PARAMS) {
     entry_guard(out_status, [&] {
+        const Shared s = RCPPML_SVD_SHARED;
         const CvRaw a = RCPPML_SVD_CV_RAW;
-        Opts o = make_cv_opts(a, m, n);
+        Opts o = make_cv_opts(s, a, m, n, precision);
         if (!nnz) throw std::invalid_argument("null pointer");
-        o.nnz = *nnz; o.p = col_ptr; o.i = row_idx; o.x = values;
-        check_csc_lenient(o.p, o.i, o.x, o.m, o.n, o.nnz);
+        attach_csc(o, col_ptr, row_idx, values, *nnz);
         add_reg_opts(o, RCPPML_SVD_REG_RAW);
-        run_reg_entry(a, o);
+        write_cv(s, a, o, fit(o, *precision, reg_bytes));
     });
 }
 extern "C" void rcppml_gpu_svd_reg_dense_ex(const double* A_data, int* m, int* n, RCPPML_SVD_REG_PARAMS) {
     entry_guard(out_status, [&] {
+        const Shared s = RCPPML_SVD_SHARED;
         const CvRaw a = RCPPML_SVD_CV_RAW;
-        Opts o = make_cv_opts(a, m, n);
-        if (!A_data) throw std::invalid_argument("null matrix");
-        o.nnz = (int64_t)o.m * o.n; o.dense = A_data;
+        Opts o = make_cv_opts(s, a, m, n, precision);
+        attach_dense(o, A_data);
         add_reg_opts(o, RCPPML_SVD_REG_RAW);
-        run_reg_entry(a, o);
+        write_cv(s, a, o, fit(o, *precision, reg_bytes));
     });
 }
 
 // ------------------------------------------------------------------------------------------------------------ krylov entries
 // Build-defined: the constrained block SVD (KSPR), which the four reference entries refuse as "algorithm 1-4 with element
-// constraints".  Every check runs before any device work, and nothing is written on a refusal.
+// constraints".
 namespace {
 struct KsRaw {
-    int* precision; int* k_max; double* tol; int* max_iter; int *center, *seed;
-    double *L1_u, *L1_v, *L2_u, *L2_v; int *nonneg_u, *nonneg_v; double *ub_u, *ub_v;
-    const double* V0;
-    double *U, *d, *V; int *out_k_selected, *out_passes; double *out_dw, *out_frobenius_norm_sq, *out_row_means, *out_wall_time_ms;
+    double* tol; int* max_iter; const double* V0; int* out_passes; double* out_dw;
 };
 
-Opts make_ks_opts(const KsRaw& a, const int* m, const int* n) {
-    if (!m || !n || !a.precision || !a.k_max || !a.tol || !a.max_iter || !a.center || !a.seed || !a.L1_u || !a.L1_v || !a.L2_u ||
-        !a.L2_v || !a.nonneg_u || !a.nonneg_v || !a.ub_u || !a.ub_v || !a.U || !a.d || !a.V || !a.out_k_selected || !a.out_passes ||
-        !a.out_dw || !a.out_frobenius_norm_sq || !a.out_row_means || !a.out_wall_time_ms)
-        throw std::invalid_argument("null pointer");
-    if (*a.precision != RCPPML_F32 && *a.precision != RCPPML_F64) throw std::invalid_argument("precision must be RCPPML_F32 or RCPPML_F64");
-    Opts o;
-    o.m = *m; o.n = *n; o.k = *a.k_max;
-    o.tol = *a.tol; o.max_iter = 0; o.ks_iter = *a.max_iter; o.center = *a.center != 0; o.seed = (unsigned)(uint32_t)*a.seed;
-    o.algorithm = 4; o.kspr = true; o.V0 = a.V0;
-    o.L1_u = *a.L1_u; o.L1_v = *a.L1_v; o.L2_u = *a.L2_u; o.L2_v = *a.L2_v; o.ub_u = *a.ub_u; o.ub_v = *a.ub_v;
-    o.nonneg_u = *a.nonneg_u != 0; o.nonneg_v = *a.nonneg_v != 0;
-    if (o.m < 1 || o.n < 1) throw std::invalid_argument("the matrix must have at least one row and one column");
-    if (o.k < 1 || o.k > std::min(o.m, o.n)) throw std::invalid_argument("k_max must be in [1, min(m, n)]");
+Opts make_ks_opts(const Shared& s, const KsRaw& a, const int* m, const int* n, const int* precision) {
+    Opts o = load_checked(s, m, n, precision, !a.tol || !a.max_iter || !a.out_passes || !a.out_dw);
+    o.tol = *a.tol; o.max_iter = 0; o.ks_iter = *a.max_iter;
+    o.method = Method::kspr; o.V0 = a.V0;
     if (o.k > KS_KMAX) throw std::invalid_argument("k_max above " + std::to_string(KS_KMAX) + " is not supported by the krylov method");
     if (!(o.tol >= 0)) throw std::invalid_argument("tol must be non-negative");
     if (!(o.L1_u >= 0 && o.L1_v >= 0)) throw std::invalid_argument("L1 penalties must be non-negative");
@@ -1291,23 +1308,10 @@ size_t ks_bytes(const Opts& o, size_t ts) {
     return b + 3 * K * K * sizeof(double);
 }
 
-void run_ks_entry(const KsRaw& a, const Opts& o) {
-    const bool f32 = *a.precision == RCPPML_F32;
-    device_ready(ks_bytes(o, f32 ? sizeof(float) : sizeof(double)), "the SVD");
-    const auto t0 = std::chrono::steady_clock::now();
-    Result R;
-    if (f32) { Engine<float> E(o); E.run(R); }
-    else { Engine<double> E(o); E.run(R); }
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    std::copy(R.U.begin(), R.U.end(), a.U);           // the first k_selected columns
-    std::copy(R.V.begin(), R.V.end(), a.V);
-    std::copy(R.d.begin(), R.d.end(), a.d);
-    std::copy(R.dw.begin(), R.dw.end(), a.out_dw);
-    *a.out_k_selected = R.k_sel;
-    *a.out_passes = R.passes;
-    *a.out_frobenius_norm_sq = R.frob;
-    if (o.center) std::copy(R.row_means.begin(), R.row_means.end(), a.out_row_means);
-    *a.out_wall_time_ms = ms;
+void write_ks(const Shared& s, const KsRaw& a, const Opts& o, const Fit& f) {
+    write_shared(s, o, f);
+    std::copy(f.R.dw.begin(), f.R.dw.end(), a.out_dw);
+    *a.out_passes = f.R.passes;
 }
 }  // namespace
 
@@ -1316,47 +1320,40 @@ void run_ks_entry(const KsRaw& a, const Opts& o) {
         double *L2_v, int *nonneg_u, int *nonneg_v, double *ub_u, double *ub_v, const double *V0, double *U, double *d, double *V,  \
         int *out_k_selected, int *out_passes, double *out_dw, double *out_frobenius_norm_sq, double *out_row_means,                 \
         double *out_wall_time_ms, int *out_status
-#define RCPPML_SVD_KS_RAW                                                                                                         \
-    KsRaw{precision, k_max, tol, max_iter, center, seed, L1_u, L1_v, L2_u, L2_v, nonneg_u, nonneg_v, ub_u, ub_v, V0, U, d, V,     \
-          out_k_selected, out_passes, out_dw, out_frobenius_norm_sq, out_row_means, out_wall_time_ms}
+#define RCPPML_SVD_KS_RAW KsRaw{tol, max_iter, V0, out_passes, out_dw}
 
 extern "C" void rcppml_gpu_svd_krylov_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
                                          RCPPML_SVD_KS_PARAMS) {
     entry_guard(out_status, [&] {
+        const Shared s = RCPPML_SVD_SHARED;
         const KsRaw a = RCPPML_SVD_KS_RAW;
-        Opts o = make_ks_opts(a, m, n);
+        Opts o = make_ks_opts(s, a, m, n, precision);
         if (!nnz) throw std::invalid_argument("null pointer");
-        o.nnz = *nnz; o.p = col_ptr; o.i = row_idx; o.x = values;
-        check_csc_lenient(o.p, o.i, o.x, o.m, o.n, o.nnz);
-        run_ks_entry(a, o);
+        attach_csc(o, col_ptr, row_idx, values, *nnz);
+        write_ks(s, a, o, fit(o, *precision, ks_bytes));
     });
 }
-// the dense matrix enumerated as a full CSC (as the reference's bridge does for krylov); the Lanczos seed runs the dense products
+// the block passes read the dense matrix as a full CSC; the Lanczos seed runs the dense products
 extern "C" void rcppml_gpu_svd_krylov_dense_ex(const double* A_data, int* m, int* n, RCPPML_SVD_KS_PARAMS) {
     entry_guard(out_status, [&] {
+        const Shared s = RCPPML_SVD_SHARED;
         const KsRaw a = RCPPML_SVD_KS_RAW;
-        Opts o = make_ks_opts(a, m, n);
-        if (!A_data) throw std::invalid_argument("null matrix");
-        o.nnz = (int64_t)o.m * o.n;
-        if (o.nnz >= INT_MAX) throw std::invalid_argument("nnz out of range");
-        std::vector<int> p((size_t)o.n + 1), i((size_t)o.nnz);
-        for (int j = 0; j <= o.n; ++j) p[j] = (int)((int64_t)j * o.m);
-        for (int64_t e = 0; e < o.nnz; ++e) i[e] = (int)(e % o.m);
-        o.dense = A_data; o.p = p.data(); o.i = i.data(); o.x = A_data;
-        run_ks_entry(a, o);
+        Opts o = make_ks_opts(s, a, m, n, precision);
+        attach_dense(o, A_data);
+        FullCsc full;
+        full.attach(o);
+        write_ks(s, a, o, fit(o, *precision, ks_bytes));
     });
 }
 
 // ------------------------------------------------------------------------------------------------------------ randomized entries
 // Build-defined: the randomized block SVD (svd/randomized.hpp:59-241), which the four reference entries run as Lanczos under
-// algorithm 3.  Every check runs before any device work, and nothing is written on a refusal.
+// algorithm 3.
 namespace {
 struct RsRaw {
-    int* precision; int* k_max; int* max_iter; int *center, *seed;
-    double *L1_u, *L1_v, *L2_u, *L2_v; int *nonneg_u, *nonneg_v; double *ub_u, *ub_v, *L21_u, *L21_v, *angular_u, *angular_v;
+    int* max_iter; double *L21_u, *L21_v, *angular_u, *angular_v;
     const int* graph_u_p; double* graph_u_lambda; const int* graph_v_p; double* graph_v_lambda; double* test_fraction;
-    const int* obs_mask_p;
-    double *U, *d, *V; int *out_k_selected, *out_iters; double *out_frobenius_norm_sq, *out_row_means, *out_wall_time_ms;
+    const int* obs_mask_p; int* out_iters;
 };
 
 int rs_sketch(int m, int n, int k) {        // randomized.hpp:73-74
@@ -1364,20 +1361,11 @@ int rs_sketch(int m, int n, int k) {        // randomized.hpp:73-74
     return k + std::max(p, 0);
 }
 
-Opts make_rs_opts(const RsRaw& a, const int* m, const int* n) {
-    if (!m || !n || !a.precision || !a.k_max || !a.max_iter || !a.center || !a.seed || !a.L1_u || !a.L1_v || !a.L2_u || !a.L2_v ||
-        !a.nonneg_u || !a.nonneg_v || !a.ub_u || !a.ub_v || !a.L21_u || !a.L21_v || !a.angular_u || !a.angular_v || !a.test_fraction ||
-        !a.U || !a.d || !a.V || !a.out_k_selected || !a.out_iters || !a.out_frobenius_norm_sq || !a.out_row_means || !a.out_wall_time_ms)
-        throw std::invalid_argument("null pointer");
-    if (*a.precision != RCPPML_F32 && *a.precision != RCPPML_F64) throw std::invalid_argument("precision must be RCPPML_F32 or RCPPML_F64");
-    Opts o;
-    o.m = *m; o.n = *n; o.k = *a.k_max;
-    o.tol = 0; o.max_iter = *a.max_iter; o.center = *a.center != 0; o.seed = (unsigned)(uint32_t)*a.seed;
-    o.algorithm = 3; o.rand = true;
-    o.L1_u = *a.L1_u; o.L1_v = *a.L1_v; o.L2_u = *a.L2_u; o.L2_v = *a.L2_v; o.ub_u = *a.ub_u; o.ub_v = *a.ub_v;
-    o.nonneg_u = *a.nonneg_u != 0; o.nonneg_v = *a.nonneg_v != 0;
-    if (o.m < 1 || o.n < 1) throw std::invalid_argument("the matrix must have at least one row and one column");
-    if (o.k < 1 || o.k > std::min(o.m, o.n)) throw std::invalid_argument("k_max must be in [1, min(m, n)]");
+Opts make_rs_opts(const Shared& s, const RsRaw& a, const int* m, const int* n, const int* precision) {
+    const bool own_null = !a.max_iter || !a.L21_u || !a.L21_v || !a.angular_u || !a.angular_v || !a.test_fraction || !a.out_iters;
+    Opts o = load_checked(s, m, n, precision, own_null);
+    o.tol = 0; o.max_iter = *a.max_iter;
+    o.method = Method::randomized;
     const int l = rs_sketch(o.m, o.n, o.k);
     if (l > RS_LMAX)
         throw std::invalid_argument("the randomized method's sketch dimension l = k + oversampling = " + std::to_string(l) +
@@ -1403,22 +1391,9 @@ size_t rs_bytes(const Opts& o, size_t ts) {
     return b + (3 * l * l + 2 * l * K) * sizeof(double);
 }
 
-void run_rs_entry(const RsRaw& a, const Opts& o) {
-    const bool f32 = *a.precision == RCPPML_F32;
-    device_ready(rs_bytes(o, f32 ? sizeof(float) : sizeof(double)), "the SVD");
-    const auto t0 = std::chrono::steady_clock::now();
-    Result R;
-    if (f32) { Engine<float> E(o); E.run(R); }
-    else { Engine<double> E(o); E.run(R); }
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    std::copy(R.U.begin(), R.U.end(), a.U);           // the first k_selected columns
-    std::copy(R.V.begin(), R.V.end(), a.V);
-    std::copy(R.d.begin(), R.d.end(), a.d);
-    std::copy(R.iters.begin(), R.iters.end(), a.out_iters);
-    *a.out_k_selected = R.k_sel;
-    *a.out_frobenius_norm_sq = R.frob;
-    if (o.center) std::copy(R.row_means.begin(), R.row_means.end(), a.out_row_means);
-    *a.out_wall_time_ms = ms;
+void write_rs(const Shared& s, const RsRaw& a, const Opts& o, const Fit& f) {
+    write_shared(s, o, f);
+    std::copy(f.R.iters.begin(), f.R.iters.end(), a.out_iters);       // one value: the power iterations run
 }
 }  // namespace
 
@@ -1429,35 +1404,32 @@ void run_rs_entry(const RsRaw& a, const Opts& o) {
         double *test_fraction, const int *obs_mask_p, double *U, double *d, double *V, int *out_k_selected,                         \
         int *out_iters_per_factor, double *out_frobenius_norm_sq, double *out_row_means, double *out_wall_time_ms, int *out_status
 #define RCPPML_SVD_RS_RAW                                                                                                         \
-    RsRaw{precision, k_max, max_iter, center, seed, L1_u, L1_v, L2_u, L2_v, nonneg_u, nonneg_v, ub_u, ub_v, L21_u, L21_v,         \
-          angular_u, angular_v, graph_u_p, graph_u_lambda, graph_v_p, graph_v_lambda, test_fraction, obs_mask_p, U, d, V,          \
-          out_k_selected, out_iters_per_factor, out_frobenius_norm_sq, out_row_means, out_wall_time_ms}
+    RsRaw{max_iter, L21_u, L21_v, angular_u, angular_v, graph_u_p, graph_u_lambda, graph_v_p, graph_v_lambda, test_fraction,      \
+          obs_mask_p, out_iters_per_factor}
 
+// the finite check of the matrix follows its other checks
 extern "C" void rcppml_gpu_svd_randomized_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
                                              RCPPML_SVD_RS_PARAMS) {
     entry_guard(out_status, [&] {
+        const Shared s = RCPPML_SVD_SHARED;
         const RsRaw a = RCPPML_SVD_RS_RAW;
-        Opts o = make_rs_opts(a, m, n);
+        Opts o = make_rs_opts(s, a, m, n, precision);
         if (!nnz) throw std::invalid_argument("null pointer");
-        o.nnz = *nnz; o.p = col_ptr; o.i = row_idx; o.x = values;
-        check_csc_lenient(o.p, o.i, o.x, o.m, o.n, o.nnz);
+        attach_csc(o, col_ptr, row_idx, values, *nnz);
         all_finite(o.x, (size_t)o.nnz, "the matrix");
-        run_rs_entry(a, o);
+        write_rs(s, a, o, fit(o, *precision, rs_bytes));
     });
 }
-// the dense matrix enumerated as a full CSC, as rcppml_gpu_svd_krylov_dense_ex does
 extern "C" void rcppml_gpu_svd_randomized_dense_ex(const double* A_data, int* m, int* n, RCPPML_SVD_RS_PARAMS) {
     entry_guard(out_status, [&] {
+        const Shared s = RCPPML_SVD_SHARED;
         const RsRaw a = RCPPML_SVD_RS_RAW;
-        Opts o = make_rs_opts(a, m, n);
-        if (!A_data) throw std::invalid_argument("null matrix");
-        o.nnz = (int64_t)o.m * o.n;
-        if (o.nnz >= INT_MAX) throw std::invalid_argument("nnz out of range");
-        all_finite(A_data, (size_t)o.nnz, "the matrix");
-        std::vector<int> p((size_t)o.n + 1), i((size_t)o.nnz);
-        for (int j = 0; j <= o.n; ++j) p[j] = (int)((int64_t)j * o.m);
-        for (int64_t e = 0; e < o.nnz; ++e) i[e] = (int)(e % o.m);
-        o.dense = A_data; o.p = p.data(); o.i = i.data(); o.x = A_data;
-        run_rs_entry(a, o);
+        Opts o = make_rs_opts(s, a, m, n, precision);
+        attach_dense(o, A_data);
+        FullCsc full;
+        full.attach(o);
+        all_finite(o.x, (size_t)o.nnz, "the matrix");
+        write_rs(s, a, o, fit(o, *precision, rs_bytes));
     });
 }
+

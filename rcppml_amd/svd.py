@@ -230,20 +230,26 @@ def svd(A, k=10, tol=1e-5, maxit=_MISSING, center=False, seed=None, L1=0, L2=0, 
         return _svd_randomized(M, dense, min(k, min(shape)), maxit, center, s, precision)
     kw = dict(precision=precision, tol=tol, max_iter=maxit, center=center, seed=s, L1=L1v, L2=L2v, nonneg=nn, upper_bound=ub,
               algorithm=_abi.SVD_ALGORITHMS[method])
-    if dense is not None:
-        r = _abi.svd_pca(dense, int(k), dense=True, **kw)
-        m = dense.shape[0]
-    else:
-        r = _abi.svd_pca((M.p, M.i, M.x, M.rows, M.cols), int(k), **kw)
-        m = M.rows
+    r = _fitted(_abi.svd_pca, M, dense, int(k), **kw)
+    return _packed(r, center, method, r["iters"][:int(np.sum(r["iters"] > 0)) or r["k"]])
+
+
+def _fitted(call, M, dense, k, **kw):
+    """The result of one _abi wrapper on the matrix, or BackendError with the entry's reason."""
+    r = call(dense if dense is not None else (M.p, M.i, M.x, M.rows, M.cols), k, dense=dense is not None, **kw)
     if r["status"] != 0:
         raise _abi.BackendError("GPU SVD/PCA failed: %s" % r["error"])
+    return r
+
+
+def _packed(r, center, method, iters, auto_rank=False, test_loss=None, n_test=0, cv_seed_effective=None, **extras):
+    """dict(u, d, v, misc) from the result of _fitted(), trimmed to the selected rank.  iters: the iteration counts that count;
+    extras: further misc entries (KSPR's)."""
     ks = r["k"]
-    iters = r["iters"]
-    nz = int(np.sum(iters > 0)) or ks
-    misc = dict(iters_per_factor=iters[:nz].copy(), frobenius_norm_sq=r["frob"],
-                row_means=r["row_means"][:m].copy() if center else None, method=method, wall_time_ms=r["wall_ms"],
-                auto_rank=False, k_selected=ks, test_loss=np.zeros(0), n_test=0, cv_seed_effective=None)
+    misc = dict(iters_per_factor=iters.copy(), frobenius_norm_sq=r["frob"],
+                row_means=r["row_means"][:r["U"].shape[0]].copy() if center else None, method=method, wall_time_ms=r["wall_ms"],
+                auto_rank=auto_rank, k_selected=ks, test_loss=np.zeros(0) if test_loss is None else test_loss.copy(), n_test=n_test,
+                cv_seed_effective=cv_seed_effective, **extras)
     return dict(u=r["U"][:, :ks].copy(), d=r["d"][:ks].copy(), v=r["V"][:, :ks].copy(), misc=misc)
 
 
@@ -254,53 +260,28 @@ def _svd_cv(M, dense, k, method, maxit, tol, center, seed, cons, precision, test
         raise _abi.BackendError("GPU SVD/PCA failed: cross-validation, auto-rank and a mask matrix need method 'deflation' on the GPU "
                                 "(got '%s')" % method)
     L1v, L2v, nn, ub = cons
-    src = dense if dense is not None else (M.p, M.i, M.x, M.rows, M.cols)
-    call = _abi.svd_cv if reg is None else _abi.svd_reg
-    r = call(src, k, dense=dense is not None, precision=precision, tol=tol, max_iter=maxit, center=center, seed=seed, L1=L1v,
-             L2=L2v, nonneg=nn, upper_bound=ub, test_fraction=test_fraction, cv_seed=cv_seed, patience=patience,
-             mask_zeros=mask_zeros, obs_mask=obs, **(reg or {}))
-    if r["status"] != 0:
-        raise _abi.BackendError("GPU SVD/PCA failed: %s" % r["error"])
-    ks, kc = r["k"], r["k_computed"]
-    m = dense.shape[0] if dense is not None else M.rows
+    r = _fitted(_abi.svd_cv if reg is None else _abi.svd_reg, M, dense, k, precision=precision, tol=tol, max_iter=maxit,
+                center=center, seed=seed, L1=L1v, L2=L2v, nonneg=nn, upper_bound=ub, test_fraction=test_fraction, cv_seed=cv_seed,
+                patience=patience, mask_zeros=mask_zeros, obs_mask=obs, **(reg or {}))
+    kc = r["k_computed"]
     s32, c32 = seed & 0xFFFFFFFF, cv_seed & 0xFFFFFFFF
     eff = (c32 if c32 != 0 else ((s32 ^ 0xBEEF) if s32 != 0 else 42)) if test_fraction > 0 else None    # core/svd_config.hpp:149-151
-    misc = dict(iters_per_factor=r["iters"][:kc].copy(), frobenius_norm_sq=r["frob"],
-                row_means=r["row_means"][:m].copy() if center else None, method=method, wall_time_ms=r["wall_ms"],
-                auto_rank=auto_rank, k_selected=ks, test_loss=r["test_loss"][:kc].copy() if test_fraction > 0 else np.zeros(0),
-                n_test=r["n_test"], cv_seed_effective=eff)
-    return dict(u=r["U"][:, :ks].copy(), d=r["d"][:ks].copy(), v=r["V"][:, :ks].copy(), misc=misc)
+    test_loss = r["test_loss"][:kc] if test_fraction > 0 else None
+    return _packed(r, center, method, r["iters"][:kc], auto_rank, test_loss, r["n_test"], eff)
 
 
 def _svd_krylov(M, dense, k, maxit, tol, center, seed, cons, precision):
     """The constrained krylov call: KSPR through _abi.svd_krylov."""
     L1v, L2v, nn, ub = cons
-    src = dense if dense is not None else (M.p, M.i, M.x, M.rows, M.cols)
-    r = _abi.svd_krylov(src, k, dense=dense is not None, precision=precision, tol=tol, max_iter=maxit, center=center, seed=seed,
-                        L1=L1v, L2=L2v, nonneg=nn, upper_bound=ub)
-    if r["status"] != 0:
-        raise _abi.BackendError("GPU SVD/PCA failed: %s" % r["error"])
-    ks = r["k"]
-    m = dense.shape[0] if dense is not None else M.rows
-    misc = dict(iters_per_factor=np.zeros(0, np.int32), frobenius_norm_sq=r["frob"],
-                row_means=r["row_means"][:m].copy() if center else None, method="krylov", wall_time_ms=r["wall_ms"],
-                auto_rank=False, k_selected=ks, test_loss=np.zeros(0), n_test=0, cv_seed_effective=None, passes=r["passes"],
-                dw=r["dw"].copy())
-    return dict(u=r["U"][:, :ks].copy(), d=r["d"][:ks].copy(), v=r["V"][:, :ks].copy(), misc=misc)
+    r = _fitted(_abi.svd_krylov, M, dense, k, precision=precision, tol=tol, max_iter=maxit, center=center, seed=seed, L1=L1v,
+                L2=L2v, nonneg=nn, upper_bound=ub)
+    return _packed(r, center, "krylov", np.zeros(0, np.int32), passes=r["passes"], dw=r["dw"].copy())
 
 
 def _svd_randomized(M, dense, k, maxit, center, seed, precision):
     """The named randomized call: the block method through _abi.svd_randomized."""
-    src = dense if dense is not None else (M.p, M.i, M.x, M.rows, M.cols)
-    r = _abi.svd_randomized(src, k, dense=dense is not None, precision=precision, max_iter=maxit, center=center, seed=seed)
-    if r["status"] != 0:
-        raise _abi.BackendError("GPU SVD/PCA failed: %s" % r["error"])
-    ks = r["k"]
-    m = dense.shape[0] if dense is not None else M.rows
-    misc = dict(iters_per_factor=r["iters"][:1].copy(), frobenius_norm_sq=r["frob"],
-                row_means=r["row_means"][:m].copy() if center else None, method="randomized", wall_time_ms=r["wall_ms"],
-                auto_rank=False, k_selected=ks, test_loss=np.zeros(0), n_test=0, cv_seed_effective=None)
-    return dict(u=r["U"][:, :ks].copy(), d=r["d"][:ks].copy(), v=r["V"][:, :ks].copy(), misc=misc)
+    r = _fitted(_abi.svd_randomized, M, dense, k, precision=precision, max_iter=maxit, center=center, seed=seed)
+    return _packed(r, center, "randomized", r["iters"][:1])
 
 
 def pca(A, k=10, **kw):
