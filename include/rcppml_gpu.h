@@ -1133,6 +1133,58 @@ RCPPML_GPU_API int rcppml_hip_cv_gp_theta_update(rcppml_hip_ctx* ctx, int dtype,
                                                  const void* H, int64_t n, int k, double holdout_fraction,
                                                  unsigned long long cv_seed, double theta_max, void* theta);
 
+/* Factor graphs (rcppml_amd/csrc/ops_graph.hip, kernels_graph.hip.h).  Build-defined: R has no hook for them.  The specification is the
+ * reference's multi-layer fit, inst/include/FactorNet/graph/fit.hpp:100-194 (effective_input) and :264-375 (fit_deep).  fp64.
+ *
+ * rcppml_hip_graph_assemble: the effective input X (n x c, column-major, device) of a deeper layer from n_branches (1..8) upstream
+ *   factors H[b] (k[b] x n, leading dimension k[b], device pointers in a HOST array) and an optional condition block Z (p x n,
+ *   column-major; NULL / p = 0: none).  mode 0 (concat; one branch = the plain chain): X = [t(H_0) | t(H_1) | ... | t(Z)],
+ *   c = sum k[b] + p.  mode 1 (add; all k[b] equal): X = [t(H_0 + H_1 + ...) | t(Z)], c = k[0] + p, summed in branch order.  One
+ *   launch, a transposing gather through an LDS tile; no atomics, exact.
+ * rcppml_hip_graph_layer_loss: out[0] (double, device) = scale * sum_ij (X_ij - sum_f W_T[f, i] d_f H[f, j])^2 for a dense X
+ *   (rows x c, column-major), W_T k x rows, d k, H k x c, k <= 128.  Two launches; the summation order depends on (rows, c, k)
+ *   only: bitwise-repeatable. */
+RCPPML_GPU_API int rcppml_hip_graph_assemble(rcppml_hip_ctx* ctx, int dtype, int mode, int n_branches, const void* const* H,
+                                             const int* k, int64_t n, const void* Z, int p, void* X);
+RCPPML_GPU_API int rcppml_hip_graph_layer_loss(rcppml_hip_ctx* ctx, int dtype, const void* X, int64_t rows, int c, const void* W_T,
+                                               const void* d, const void* H, int k, double scale, double* out);
+
+/* rcppml_gpu_factor_net_fit_ex: fit_deep on the device.  Every layer's factors stay on the device between the upload and the final
+ * download; the first layer's matrix, its transpose and the right-hand-side plans are built once per call; the host reads one
+ * scalar (the summed loss) per outer iteration, and one per warm-up iteration when *tol > 0 (the fit's own convergence rule).
+ *
+ * The first layer's data: a host CSC (col_ptr, row_idx, values, *nnz; row indices strictly increasing within a column) or a
+ * column-major *m x *n dense array, exactly one of the two.
+ * The graph, layers in topological order, layer i = 0 .. *n_layers - 1 (1 .. 64):
+ *   rank[i]                        1 .. 128 (1 .. 64 with the Cholesky solver: the fp64 Cholesky solve)
+ *   src_kind[i]                    0 input (the data), 1 layer, 2 concat, 3 add
+ *   branch_ptr (n_layers + 1), branch_idx   the upstream layers of layer i: branch_idx[branch_ptr[i] .. branch_ptr[i + 1]), each < i;
+ *                                  none for kind 0, one for kind 1, 2 .. 8 for kinds 2 and 3 (add: equal ranks).  All branches of a layer
+ *                                  have the same number of H columns.
+ *   cond_p[i], cond_Z              rows p of the layer's condition block (0: none; kinds 1 .. 3 only) and the blocks (p x rows_i,
+ *                                  column-major) packed in layer order
+ *   The layer factorises X_i (rows_i x cols_i) ~ W_i diag(d_i) H_i:  kind 0: m x n;  otherwise rows_i = the branches' H columns and
+ *   cols_i = sum of the branch ranks (concat, layer) or the common rank (add), plus p.
+ *   L1, L2, upper_bound, nonneg    2 * n_layers values each: [2 i] the W side, [2 i + 1] the H side of layer i
+ * *max_iter >= 1, *tol, *seed (0 means 42), *solver_mode (0 CD, 1 Cholesky + clip), *norm_type (0 L1, 1 L2, 2 none), *cd_maxit, *cd_tol.
+ * *start: 0 = the reference's warm-up pass (per layer: factors from one SplitMix64 stream seeded seed + i, W_T then H, and
+ *   min(10, *max_iter) iterations of the plain MSE fit with *tol and patience 5); 1 = W, d, H hold every layer's state on entry and
+ *   the warm-up is skipped.
+ * W, d, H (in with *start = 1, out always): per layer W_T (rank x rows_i), d (rank), H (rank x cols_i), column-major, packed in
+ *   layer order.  out_layer_loss (n_layers): the layers' mean squared reconstruction errors of the last outer iteration.
+ * *out_loss reproduces the reference's total_loss: the previous iteration's summed loss when the loop stops on
+ *   |prev - cur| / (|prev| + 1e-15) < *tol, the last one when it runs out (fit.hpp:345-359).
+ * out_counts (2 ints, may be NULL): device-op calls and own kernel launches of ONE outer iteration.
+ * Refused (*out_status = -1, reason in rcppml_gpu_last_error, no output written): a null pointer; a malformed graph, CSC or shape;
+ *   a non-finite value; a rank above 128 (64 with Cholesky); not enough free device memory (the message gives the byte count); no
+ *   HIP device. */
+RCPPML_GPU_API void rcppml_gpu_factor_net_fit_ex(const int* col_ptr, const int* row_idx, const double* values, int* nnz,
+        const double* dense, int* m, int* n, int* n_layers, const int* rank, const int* src_kind, const int* branch_ptr,
+        const int* branch_idx, const int* cond_p, const double* cond_Z, const double* L1, const double* L2,
+        const double* upper_bound, const int* nonneg, int* max_iter, double* tol, int* seed, int* solver_mode, int* norm_type,
+        int* cd_maxit, double* cd_tol, int* start, double* W, double* d, double* H, double* out_layer_loss, int* out_iter,
+        int* out_converged, double* out_loss, int* out_counts, int* out_status);
+
 #ifdef __cplusplus
 }
 #endif

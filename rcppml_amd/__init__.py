@@ -16,6 +16,9 @@ Layout (only what the path needs):
              itself still refuses, routing it here is a later change
   classify.py classify_embedding() / classify_logistic() / classify_cv(): mirror of the R surface on the HIP classifier-evaluation
              path (csrc/ops_classify.hip)
+  factor_net.py factor_input() / nmf_layer() / svd_layer() / factor_shared() / factor_concat() / factor_add() / factor_condition() /
+             factor_net() / fit() / predict(): mirror of the R factor-graph surface; multi-layer graphs run the reference's deep fit
+             resident on the device (csrc/ops_graph.hip)
   als.py     one-process-per-GPU column-sharded ALS loop over torch.distributed (RCCL): Comm, ShardedALS, HipOps
   data.py    synthetic inputs (restatement of R/simulateNMF.R) and CSC helpers
 """

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_compute_target_double", "rcppml_gpu_refine_correct_double", "rcppml_gpu_refine_wfit_double", "rcppml_gpu_refine_double",
     "rcppml_gpu_nmf_zi_double", "rcppml_gpu_zi_em_double",
     "rcppml_gpu_classify_metrics_ex", "rcppml_gpu_classify_knn_ex", "rcppml_gpu_classify_logistic_ex",
+    "rcppml_hip_graph_assemble", "rcppml_hip_graph_layer_loss", "rcppml_gpu_factor_net_fit_ex",
 ]
 
 
@@ -538,6 +539,20 @@ class Context:
         _chk(lib().rcppml_hip_tail_scale_gram_loss(self._h, C.c_int(dt), _dptr(W_T), C.c_int(k), C.c_int64(m), C.c_int(norm_type), _dptr(sums),
                                                    _dptr(d), _dptr(sweeps), _dptr(order), C.c_double(eps), _dptr(trAtA), _dptr(B_w),
                                                    _dptr(G_saved), _dptr(G_wt), _dptr(out)), "tail_scale_gram_loss")
+
+    def graph_assemble(self, mode, H, k, n, Z, p, X, dt=F64):
+        """X (n x c, column-major) from the branch factors H (a list of (n, k_b) tensors = column-major k_b x n) and the condition block
+        Z ((n, p) tensor or None); mode 0 concat, 1 add.  One launch, exact (rcppml_hip_graph_assemble)."""
+        ptrs = (C.c_void_p * len(H))(*[h.data_ptr() for h in H])
+        ks = (C.c_int * len(k))(*[int(v) for v in k])
+        _chk(lib().rcppml_hip_graph_assemble(self._h, C.c_int(dt), C.c_int(mode), C.c_int(len(H)), ptrs, ks, C.c_int64(n), _dptr(Z),
+                                             C.c_int(p), _dptr(X)), "graph_assemble")
+
+    def graph_layer_loss(self, X, rows, c, W_T, d, H, k, scale, out, dt=F64):
+        """out[0] = scale * ||X - W diag(d) H||_F^2 for a dense X (rows x c, column-major); two launches, bitwise-repeatable
+        (rcppml_hip_graph_layer_loss)."""
+        _chk(lib().rcppml_hip_graph_layer_loss(self._h, C.c_int(dt), _dptr(X), C.c_int64(rows), C.c_int(c), _dptr(W_T), _dptr(d), _dptr(H),
+                                               C.c_int(k), C.c_double(scale), _dptr(out)), "graph_layer_loss")
 
     def als_small_fit(self, dt, csc, csc_t, m, n, k, W, H, d, trAtA, *, L1_H=0.0, L1_W=0.0, L2_H=0.0, L2_W=0.0, ub_H=0.0, ub_W=0.0, nonneg_H=1,
                       nonneg_W=1, norm_type=0, solver_mode=0, cd_maxit=100, cd_tol=1e-8, max_iter=100, tol=1e-4, patience=5, iter0=0, loss_history=None,
@@ -1534,4 +1549,79 @@ def nmf_zi_double(p, i, x, m, n, k, W_T, H, *, zi_mode, zi_em_iters=1, loss_type
         r.update(iter=out_iter.value, converged=bool(out_conv.value), loss=out_loss.value, tol=out_tol.value,
                  theta=theta[:theta_len.value].copy(), pi=pi[:pi_len.value].copy(),
                  loss_history=hist[:out_iter.value].copy() if hist is not None else None)
+    return r
+
+
+# ----------------------------------------------------------------------------- factor graphs (ops_graph.hip)
+GRAPH_SRC = {"input": 0, "layer": 1, "concat": 2, "add": 3}
+
+
+def factor_net_dims(m, n, rank, src_kind, branches, cond_p):
+    """(rows_i, cols_i) of every layer's effective input, as rcppml_gpu_factor_net_fit_ex derives them."""
+    dims = []
+    for i, kind in enumerate(src_kind):
+        if kind == 0:
+            dims.append((int(m), int(n)))
+            continue
+        br = list(branches[i])
+        rows = dims[br[0]][1]
+        cols = (int(rank[br[0]]) if kind == 3 else sum(int(rank[b]) for b in br)) + int(cond_p[i])
+        dims.append((rows, cols))
+    return dims
+
+
+def factor_net_fit(csc, dense, m, n, rank, src_kind, branches, cond_Z, L1, L2, upper_bound, nonneg, *, max_iter=100, tol=1e-4, seed=0,
+                   solver_mode=1, norm_type=0, cd_maxit=100, cd_tol=1e-8, states=None, init=-7.0):
+    """rcppml_gpu_factor_net_fit_ex.  csc / dense as in score_test_double.  rank, src_kind (GRAPH_SRC codes): one per layer; branches:
+    per layer the list of upstream layer indices; cond_Z: per layer None or the condition block, p x rows_i; L1, L2, upper_bound,
+    nonneg: per layer a (W, H) pair.  states: None (the warm-up runs) or per layer (W (rows_i, k), d (k), H (k, cols_i)) -- the
+    warm-up is skipped.  Returns dict(status, error, layers = [(W, d, H)] in the same shapes, layer_loss, iter, converged, loss,
+    counts = (device-op calls, own launches) of one outer iteration, buffers).  Without states the packed buffers start at `init`
+    and a refused call leaves them so."""
+    head, keep = _matrix_head(csc, dense)
+    NL = len(rank)
+    rk = np.ascontiguousarray(rank, np.int32)
+    kind = np.ascontiguousarray(src_kind, np.int32)
+    bptr = np.zeros(NL + 1, np.int32)
+    for i in range(NL):
+        bptr[i + 1] = bptr[i] + len(branches[i])
+    bidx = np.ascontiguousarray([b for br in branches for b in br] or [0], np.int32)
+    Zs = [None if z is None else np.asarray(z, np.float64) for z in cond_Z]
+    cp = np.ascontiguousarray([0 if z is None else z.shape[0] for z in Zs], np.int32)
+    zflat = [np.ascontiguousarray(z.T).reshape(-1) for z in Zs if z is not None]
+    zbuf = np.concatenate(zflat) if zflat else None
+    pen = [np.ascontiguousarray(np.asarray(v, np.float64).reshape(NL, 2)).reshape(-1) for v in (L1, L2, upper_bound)]
+    nn = np.ascontiguousarray(np.asarray(nonneg).reshape(NL, 2).astype(np.int32)).reshape(-1)
+    try:
+        dims = factor_net_dims(m, n, rk, kind, branches, cp)
+    except (IndexError, TypeError):
+        dims = [(1, 1)] * NL                    # a malformed graph: the entry refuses it before it reads a factor
+    nW = sum(max(r, 1) * int(k) for (r, _), k in zip(dims, rk))
+    nH = sum(max(c, 1) * int(k) for (_, c), k in zip(dims, rk))
+    nd = int(rk.sum())
+    if states is not None:
+        W = np.concatenate([np.ascontiguousarray(s[0], np.float64).reshape(-1) for s in states])
+        d = np.concatenate([np.ascontiguousarray(s[1], np.float64).reshape(-1) for s in states])
+        H = np.concatenate([np.ascontiguousarray(np.asarray(s[2], np.float64).T).reshape(-1) for s in states])
+    else:
+        W, d, H = np.full(max(nW, 1), init), np.full(max(nd, 1), init), np.full(max(nH, 1), init)
+    ll = np.full(max(NL, 1), init)
+    counts = np.full(2, -7, np.int32)
+    it, conv, st = C.c_int(-7), C.c_int(-7), C.c_int(-99)
+    loss = C.c_double(init)
+    lib().rcppml_gpu_factor_net_fit_ex(*head, _ci(m), _ci(n), _ci(NL), _np_ptr(rk), _np_ptr(kind), _np_ptr(bptr), _np_ptr(bidx), _np_ptr(cp),
+                                       _opt_ptr(zbuf), _np_ptr(pen[0]), _np_ptr(pen[1]), _np_ptr(pen[2]), _np_ptr(nn), _ci(max_iter),
+                                       _cd(tol), _ci(seed), _ci(solver_mode), _ci(norm_type), _ci(cd_maxit), _cd(cd_tol),
+                                       _ci(0 if states is None else 1), _np_ptr(W), _np_ptr(d), _np_ptr(H), _np_ptr(ll), C.byref(it),
+                                       C.byref(conv), C.byref(loss), _np_ptr(counts), C.byref(st))
+    del keep
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(W, d, H, ll, it.value, conv.value, loss.value))
+    if st.value == 0:
+        layers, oW, od, oH = [], 0, 0, 0
+        for (rows, cols), k in zip(dims, rk):
+            k = int(k)
+            layers.append((W[oW:oW + rows * k].reshape(rows, k).copy(), d[od:od + k].copy(), H[oH:oH + cols * k].reshape(cols, k).T.copy()))
+            oW, od, oH = oW + rows * k, od + k, oH + cols * k
+        r.update(layers=layers, layer_loss=ll[:NL].copy(), iter=it.value, converged=bool(conv.value), loss=loss.value,
+                 counts=(int(counts[0]), int(counts[1])))
     return r
