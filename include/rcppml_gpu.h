@@ -1185,6 +1185,50 @@ RCPPML_GPU_API void rcppml_gpu_factor_net_fit_ex(const int* col_ptr, const int* 
         int* cd_maxit, double* cd_tol, int* start, double* W, double* d, double* H, double* out_layer_loss, int* out_iter,
         int* out_converged, double* out_loss, int* out_counts, int* out_status);
 
+/* Column similarities and factor matching (rcppml_amd/csrc/ops_similarity.hip): the compute side of the reference's cosine(),
+ * bipartiteMatch() and align() (R/cosine.R, R/bipartiteMatch.R, R/nmf_methods.R:261-271).  Build-defined: R has no hook for these
+ * entries and no GPU form of any of them.  fp64.  No atomics: every value has one fixed order of operations, every product and sum is
+ * rounded on its own (no FMA contraction), so results are bitwise-repeatable and do not depend on the launch.  A column of zero norm
+ * (zero centred norm for the correlation) has similarity 0 to every column, itself included.
+ * Refused (*out_status = -1, reason in rcppml_gpu_last_error, no output written): a null pointer, a size below 1, a malformed CSC
+ * (row indices strictly increasing within a column), a non-finite value, kx or ky above 128, a method outside {0, 1}, groups < 0, not
+ * enough free device memory (the message gives the byte count), no HIP device (the two device entries).
+ *
+ * rcppml_gpu_cosine_sparse_ex: out_C (*nx x *ny, column-major) with C[i, j] = <x_i, y_j> / (|x_i| |y_j|) for the columns of X (*m x
+ * *nx) and Y (*m x *ny), both CSC.  y_col_ptr NULL: Y = X (the y arguments and *ny are not read, the result is *nx x *nx and exactly
+ * symmetric: C[i, j] and C[j, i] are the same chain of operations).  No dense copy of X or Y exists on either side.  <x_i, y_j>: the
+ * products of the rows both columns store, added in ascending row order starting from 0; |x|: the squares of a column added in
+ * ascending row order, then the square root; C = dot / (|x_i| * |y_j|), 0 where that product is 0.  Sums of squares above the fp64
+ * range, or norm products below it, are the caller's to avoid.  *groups: the workgroups of the main kernel, 0 (or NULL) for the
+ * default launch; a test switch, the result does not depend on it.  out_launches (may be NULL): kernels launched, the transpose's
+ * own excluded.  out_ms (2 doubles, may be NULL): device time from the end of the upload to the last kernel, and the time of the
+ * download of C, in milliseconds.  Device memory: 8 nx ny for C, three times the CSC of X, the CSC of Y, 4 m (ceil(nx / T) + 1).
+ *
+ * rcppml_gpu_cosine_geometry: out[0] = T, the columns of X one wavefront keeps in LDS at a time; out[1] = the wavefronts of a
+ * workgroup; out[2] = the workgroups of the default launch before it is capped by the work (one per CU; 0 without a device).
+ * Returns 0 (-1 for a null pointer); needs no device for out[0] and out[1].
+ *
+ * rcppml_gpu_cosine_dense_ex: W holds *reps matrices *m x *kx, R one matrix *m x *ky, all column-major; out holds *reps matrices
+ * *kx x *ky column-major, out[q][a, b] = the similarity of column a of W_q and column b of R.  *method 0: cosine.  *method 1:
+ * Pearson correlation: the column means first (lane l of a wavefront adds rows l, l + 64, ..., then a butterfly over the 64
+ * partials, / m), then the centred dot products and the centred norms; never sum(xy) - m mean(x) mean(y).  Norms: the same lane
+ * and butterfly order.  Dot products: rows in chunks of 256 ceil(ceil(m / 256) / 64) rows, ascending inside a chunk, the chunk
+ * partials added in chunk order.  A replicate's result does not depend on the other replicates of the stack.  out_launches: 3.
+ *
+ * rcppml_gpu_bipartite_match_ex: host only, no device work.  cost: *batch matrices *nr x *nc, row-major; negative entries count as 0
+ * (R/bipartiteMatch.R:22-25).  Minimum-cost assignment by shortest augmenting paths with dual potentials (Jonker-Volgenant /
+ * Hungarian), O(min(nr, nc)^2 max(nr, nc)); rows enter in order and every scan keeps its first minimum, so equal inputs give equal
+ * assignments.  out_assignment (*batch x *nr): the column matched to each row, 0-based, -1 for a row left unmatched (nr > nc);
+ * out_cost (*batch): the matched entries added in row order. */
+RCPPML_GPU_API void rcppml_gpu_cosine_sparse_ex(const int* x_col_ptr, const int* x_row_idx, const double* x_values, int* x_nnz,
+        const int* y_col_ptr, const int* y_row_idx, const double* y_values, int* y_nnz, int* m, int* nx, int* ny, int* groups,
+        double* out_C, int* out_launches, double* out_ms, int* out_status);
+RCPPML_GPU_API int rcppml_gpu_cosine_geometry(int64_t* out);
+RCPPML_GPU_API void rcppml_gpu_cosine_dense_ex(const double* W, const double* R, int* m, int* kx, int* ky, int* reps, int* method,
+        double* out, int* out_launches, int* out_status);
+RCPPML_GPU_API void rcppml_gpu_bipartite_match_ex(const double* cost, int* nr, int* nc, int* batch, int* out_assignment,
+        double* out_cost, int* out_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,11 @@ Layout (only what the path needs):
              itself still refuses, routing it here is a later change
   classify.py classify_embedding() / classify_logistic() / classify_cv(): mirror of the R surface on the HIP classifier-evaluation
              path (csrc/ops_classify.hip)
+  similarity.py cosine() / bipartiteMatch() / align(): mirror of the R surface on the HIP similarity path (csrc/ops_similarity.hip):
+             sparse column cosines (rcppml_gpu_cosine_sparse_ex, tile geometry from rcppml_gpu_cosine_geometry), batched dense
+             cosines / correlations (rcppml_gpu_cosine_dense_ex) and the host assignment solver (rcppml_gpu_bipartite_match_ex).  A
+             zero-norm column has similarity 0 to every column; two deviations from R (cosine(vector, matrix) returns the cosine,
+             align() applies the inverse of the matching), see the module docstring
   factor_net.py factor_input() / nmf_layer() / svd_layer() / factor_shared() / factor_concat() / factor_add() / factor_condition() /
              factor_net() / fit() / predict(): mirror of the R factor-graph surface; multi-layer graphs run the reference's deep fit
              resident on the device (csrc/ops_graph.hip)
@@ -27,3 +32,4 @@ __version__ = "0.1.0"
 # the package attribute `refine` is the function from here on; the module's other names come with `from rcppml_amd.refine import ...`
 from .refine import compute_target, refine  # noqa: E402,F401
 from .classify import classify_cv, classify_embedding, classify_logistic  # noqa: E402,F401
+from .similarity import align, bipartiteMatch, cosine  # noqa: E402,F401

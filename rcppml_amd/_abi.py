@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_nmf_zi_double", "rcppml_gpu_zi_em_double",
     "rcppml_gpu_classify_metrics_ex", "rcppml_gpu_classify_knn_ex", "rcppml_gpu_classify_logistic_ex",
     "rcppml_hip_graph_assemble", "rcppml_hip_graph_layer_loss", "rcppml_gpu_factor_net_fit_ex",
+    "rcppml_gpu_cosine_sparse_ex", "rcppml_gpu_cosine_geometry", "rcppml_gpu_cosine_dense_ex", "rcppml_gpu_bipartite_match_ex",
 ]
 
 
@@ -1624,4 +1625,87 @@ def factor_net_fit(csc, dense, m, n, rank, src_kind, branches, cond_Z, L1, L2, u
             oW, od, oH = oW + rows * k, od + k, oH + cols * k
         r.update(layers=layers, layer_loss=ll[:NL].copy(), iter=it.value, converged=bool(conv.value), loss=loss.value,
                  counts=(int(counts[0]), int(counts[1])))
+    return r
+
+
+# ----------------------------------------------------------------------------- column similarities and matching (ops_similarity.hip)
+SIMILARITY_METHOD = {"cosine": 0, "cor": 1}
+
+
+def cosine_geometry():
+    """rcppml_gpu_cosine_geometry: dict(tile (columns of x per LDS tile), waves (wavefronts per workgroup), groups (workgroups of the
+    default launch before the cap by the work; 0 without a device))."""
+    out = (C.c_int64 * 3)()
+    f = lib().rcppml_gpu_cosine_geometry
+    f.restype = C.c_int
+    _chk(f(out), "cosine_geometry")
+    return dict(tile=int(out[0]), waves=int(out[1]), groups=int(out[2]))
+
+
+def _csc_ptrs(a):
+    """(col_ptr, row_idx, values, nnz) pointers of a CSC-like object with p / i / x, and the arrays to keep alive."""
+    p, i, x = np.ascontiguousarray(a.p, np.int32), np.ascontiguousarray(a.i, np.int32), np.ascontiguousarray(a.x, np.float64)
+    return [_np_ptr(p), _np_ptr(i), _np_ptr(x), _ci(x.shape[0])], (p, i, x)
+
+
+def cosine_sparse(x, y=None, *, m=None, nx=None, ny=None, groups=0, init=-7.0, out=None):
+    """rcppml_gpu_cosine_sparse_ex.  x, y: objects with p / i / x and shape (data.CSC), y None for y = x.  m, nx, ny override the
+    shapes (tests of the refusals).  out: the result buffer (nx x ny, Fortran order; default a new one filled with `init`).  Returns
+    dict(status, error, C (nx x ny), launches, device_ms, download_ms, buffers); a refused call leaves `out` as it was."""
+    m = x.shape[0] if m is None else m
+    nx = x.shape[1] if nx is None else nx
+    ny = (nx if y is None else y.shape[1]) if ny is None else ny
+    hx, keep_x = _csc_ptrs(x)
+    hy, keep_y = _csc_ptrs(y) if y is not None else ([None, None, None, None], ())
+    if out is None:
+        out = np.full((max(int(nx), 1), max(int(ny), 1)), init, order="F")
+    launches, st = C.c_int(0), C.c_int(-99)
+    ms = (C.c_double * 2)(0.0, 0.0)
+    lib().rcppml_gpu_cosine_sparse_ex(*hx, *hy, _ci(m), _ci(nx), _ci(ny), _ci(groups), _np_ptr(out), C.byref(launches), ms,
+                                      C.byref(st))
+    del keep_x, keep_y
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(out,))
+    if st.value == 0:
+        r.update(C=out, launches=launches.value, device_ms=ms[0], download_ms=ms[1])
+    return r
+
+
+def cosine_dense(W, R, method="cosine", *, m=None, kx=None, ky=None, reps=None, init=-7.0):
+    """rcppml_gpu_cosine_dense_ex.  W: (reps, kx, m) C-contiguous (each replicate m x kx column-major), R: (ky, m) C-contiguous
+    (m x ky column-major).  method: "cosine" / "cor" or the raw code.  Returns dict(status, error, sim (reps, kx, ky), launches,
+    buffers); out[q][a, b] = similarity of column a of W_q and column b of R."""
+    W = np.ascontiguousarray(W, np.float64)
+    R = np.ascontiguousarray(R, np.float64)
+    reps = W.shape[0] if reps is None else reps
+    kx = W.shape[1] if kx is None else kx
+    m = W.shape[2] if m is None else m
+    ky = R.shape[0] if ky is None else ky
+    out = np.full((max(int(reps), 1), max(int(ky), 1), max(int(kx), 1)), init)       # each replicate kx x ky column-major
+    launches, st = C.c_int(0), C.c_int(-99)
+    lib().rcppml_gpu_cosine_dense_ex(_np_ptr(W), _np_ptr(R), _ci(m), _ci(kx), _ci(ky), _ci(reps), _ci(SIMILARITY_METHOD.get(method, method)),
+                                     _np_ptr(out), C.byref(launches), C.byref(st))
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(out,))
+    if st.value == 0:
+        r.update(sim=np.ascontiguousarray(out.transpose(0, 2, 1)), launches=launches.value)
+    return r
+
+
+def bipartite_match(cost, *, nr=None, nc=None, batch=None, init=-7):
+    """rcppml_gpu_bipartite_match_ex (host only, no device).  cost: (nr, nc) or (batch, nr, nc), or None (a null pointer).  Returns
+    dict(status, error, assignment ((batch,) nr ints, -1 for an unmatched row), cost ((batch,) doubles), buffers)."""
+    cm = None if cost is None else np.ascontiguousarray(cost, np.float64)
+    single = cm is not None and cm.ndim == 2
+    if cm is not None:
+        c3 = cm[None] if single else cm
+        batch = c3.shape[0] if batch is None else batch
+        nr = c3.shape[1] if nr is None else nr
+        nc = c3.shape[2] if nc is None else nc
+    asg = np.full((max(int(batch), 1), max(int(nr), 1)), int(init), np.int32)
+    tot = np.full(max(int(batch), 1), float(init))
+    st = C.c_int(-99)
+    lib().rcppml_gpu_bipartite_match_ex(_np_ptr(cm) if cm is not None else None, _ci(nr), _ci(nc), _ci(batch), _np_ptr(asg), _np_ptr(tot),
+                                        C.byref(st))
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(asg, tot))
+    if st.value == 0:
+        r.update(assignment=asg[0] if single else asg, cost=float(tot[0]) if single else tot)
     return r
