@@ -490,6 +490,39 @@ RCPPML_GPU_API void rcppml_gpu_svd_randomized_dense_ex(const double* A_data, int
         const int* obs_mask_p, double* U, double* d, double* V, int* out_k_selected, int* out_iters_per_factor,
         double* out_frobenius_norm_sq, double* out_row_means, double* out_wall_time_ms, int* out_status);
 
+/* SVD-seeded NMF start (rcppml_amd/csrc/ops_svd.hip, nmf_start_kernel in kernels_svd.hip.h).  BUILD-DEFINED: the reference's
+ * initialize_lanczos / initialize_irlba (nmf/nmf_init.hpp:45-158), which its fits run for init_mode 1 / 2 (R: nmf(seed = "lanczos" |
+ * "irlba")).  The plugin's NMF ABI (gpu/bridge_nmf.hpp) carries no init_mode: a caller runs this entry and hands W_T and H to a
+ * fit entry as its start.
+ *   svd       Golub-Kahan-Lanczos as rcppml_gpu_svd_pca_* run it under algorithm 2, in *precision, with the reference's fixed
+ *             options: tol 1e-10, max_iter 0 (at most max(3k, k + 50) steps), no centring, the start vector of *seed (0: 42).
+ *             *mode: 1 Lanczos, 2 IRLBA -- both run this engine, as algorithm 1 does on the svd entries.
+ *   start     for c < *out_k_svd: W_T(c, i) = |u_c(i)| sqrt(sigma_c), H(c, j) = |v_c(j)| sqrt(sigma_c), the square root taken of
+ *             sigma_c in the compute type, written on the device straight into the k x m / k x n column-major layout.
+ *   fill      rows *out_k_svd .. k - 1 (Lanczos broke down early: a rank-deficient matrix) are uniform draws in the compute type
+ *             from one sequential SplitMix64 stream seeded (uint32)*seed == 0 ? 54321 : (uint32)(*seed + 999) (0 after the wrap:
+ *             12345, rng.hpp:73-74): first the (k - k_svd) x m block of W_T column by column, then the block of H
+ *             (nmf_init.hpp:82-90).
+ * Outputs: W_T (k x m) and H (k x n) column-major, every value written; d: the *out_k_svd singular values (d[c] for
+ * c >= *out_k_svd is not written); *out_iters: the Lanczos steps run.  Two runs are bitwise equal.
+ * Refused with *out_status = -1 (rcppml_gpu_last_error), nothing written: a null pointer, *precision not RCPPML_F32 / RCPPML_F64,
+ * *k outside [1, min(m, n)], *mode not 1 or 2, more than 4095 Lanczos steps, a malformed CSC, a non-finite value, more device
+ * memory than is free, no device. */
+RCPPML_GPU_API void rcppml_gpu_nmf_svd_init_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+        int* precision, int* k, int* seed, int* mode, double* W_T, double* H, double* d, int* out_k_svd, int* out_iters,
+        double* out_wall_time_ms, int* out_status);
+/* The same for a column-major dense matrix, through the engine's dense products (no CSC copy is made). */
+RCPPML_GPU_API void rcppml_gpu_nmf_svd_init_dense_ex(const double* A_data, int* m, int* n,
+        int* precision, int* k, int* seed, int* mode, double* W_T, double* H, double* d, int* out_k_svd, int* out_iters,
+        double* out_wall_time_ms, int* out_status);
+
+/* BUILD-DEFINED, for tools/init_bench.py: device milliseconds of one nmf_start_kernel launch and of the one ritz_kernel launch it
+ * replaces, on a *len x *ja basis of uniform draws with *kc of *k columns wanted: each the median of *reps launches after a warm-up,
+ * timed between two events on the stream.  Refused (-1, nothing written): a null pointer, a bad *precision, *len < 1, *ja or *k
+ * outside [1, 4095], *kc outside [1, *k], *reps outside [1, 1000], more device memory than is free, no device. */
+RCPPML_GPU_API void rcppml_hip_nmf_start_time(int* precision, int* len, int* ja, int* kc, int* k, int* reps, double* out_start_ms,
+        double* out_ritz_ms, int* out_status);
+
 /* Embedding assessment (rcppml_amd/csrc/ops_assess.hip): the reference plugin's rcppml_gpu_assess (src/gpu_bridge_assess.cu:358-753)
  * with its 26 pointers, called by R's assess() (R/assess.R:708-769).  embedding: n x dim row-major doubles, cast to fp32.  Seeds are
  * (unsigned)*seed plus an offset (restart r: + r; silhouette: + 100; folds: + 200), each driving std::mt19937 + std::shuffle.

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_svd_pca_double", "rcppml_gpu_svd_pca_float", "rcppml_gpu_svd_pca_dense_double", "rcppml_gpu_svd_pca_dense_float",
     "rcppml_gpu_svd_cv_ex", "rcppml_gpu_svd_cv_dense_ex", "rcppml_gpu_svd_krylov_ex", "rcppml_gpu_svd_krylov_dense_ex",
     "rcppml_gpu_svd_reg_ex", "rcppml_gpu_svd_reg_dense_ex", "rcppml_gpu_svd_randomized_ex", "rcppml_gpu_svd_randomized_dense_ex",
+    "rcppml_gpu_nmf_svd_init_ex", "rcppml_gpu_nmf_svd_init_dense_ex", "rcppml_hip_nmf_start_time",
     "rcppml_gpu_assess", "rcppml_gpu_assess_ex", "rcppml_gpu_knn_float", "rcppml_gpu_assess_plan",
     "rcppml_gpu_score_test_double", "rcppml_gpu_zero_inflation_double", "rcppml_gpu_dispersion_double",
     "rcppml_gpu_consensus_double", "rcppml_gpu_hclust_average_double",
@@ -1107,6 +1108,37 @@ def svd_randomized(A, k_max, *, dense=False, precision="double", max_iter=0, cen
     assert len(args) == (35 if dense else 38)
     getattr(lib(), "rcppml_gpu_svd_randomized_dense_ex" if dense else "rcppml_gpu_svd_randomized_ex")(*args)
     return dict(_svd_result(st, b, m, n, kb, ksel, frob, wall, short_ok=True), iters=b["iters"], test_loss=np.zeros(0))
+
+
+def nmf_svd_init(A, k, *, dense=False, precision="double", seed=0, mode=1, buffers=None):
+    """The build-defined rcppml_gpu_nmf_svd_init_ex / rcppml_gpu_nmf_svd_init_dense_ex: the SVD-seeded start of an NMF fit
+    (nmf/nmf_init.hpp:45-158).  A as in svd_pca; seed: the uint32 the reference's config carries; mode: 1 Lanczos, 2 IRLBA (the same
+    engine).  buffers: dict of preallocated outputs W_T (m * k), H (n * k), d (k).  Returns dict(status, error, W_T ((m, k) C-order:
+    the column-major k x m the fit entries take), H ((n, k)), d (k_svd values), k_svd, iters, wall_ms, buffers)."""
+    head, keep, m, n = _svd_head(A, dense)
+    kb = max(k, 1)
+    b = dict(W_T=np.zeros(m * kb), H=np.zeros(n * kb), d=np.zeros(kb))
+    b.update(buffers or {})
+    ksvd, iters, wall, st = C.c_int(0), C.c_int(0), C.c_double(0.0), C.c_int(-99)
+    args = head + [_ci(F32 if precision == "float" else F64), _ci(k), C.byref(C.c_int(int(seed) & 0xFFFFFFFF)), _ci(mode),
+                   _np_ptr(b["W_T"]), _np_ptr(b["H"]), _np_ptr(b["d"]), C.byref(ksvd), C.byref(iters), C.byref(wall), C.byref(st)]
+    assert len(args) == (14 if dense else 17)
+    getattr(lib(), "rcppml_gpu_nmf_svd_init_dense_ex" if dense else "rcppml_gpu_nmf_svd_init_ex")(*args)
+    full = b["W_T"].size >= m * kb and b["H"].size >= n * kb
+    return dict(status=st.value, error=last_error() if st.value else "", W_T=b["W_T"][:m * kb].reshape(m, kb) if full else b["W_T"],
+                H=b["H"][:n * kb].reshape(n, kb) if full else b["H"], d=b["d"][:ksvd.value], k_svd=ksvd.value, iters=iters.value,
+                wall_ms=wall.value, buffers=b)
+
+
+def nmf_start_time(length, ja, kc, k, *, precision="double", reps=20):
+    """rcppml_hip_nmf_start_time: (ms of one nmf_start_kernel launch, ms of the one ritz_kernel launch it replaces), medians of
+    `reps` launches on a length x ja basis with kc of k columns wanted."""
+    a, b, st = C.c_double(0.0), C.c_double(0.0), C.c_int(-99)
+    lib().rcppml_hip_nmf_start_time(_ci(F32 if precision == "float" else F64), _ci(length), _ci(ja), _ci(kc), _ci(k), _ci(reps),
+                                    C.byref(a), C.byref(b), C.byref(st))
+    if st.value != 0:
+        raise BackendError("rcppml_hip_nmf_start_time failed: %s" % last_error())
+    return a.value, b.value
 
 
 # ----------------------------------------------------------------------------- embedding assessment (ops_assess.hip)

@@ -436,6 +436,10 @@ __global__ __launch_bounds__(WG) void lz_norm_kernel(const T* __restrict__ x, lo
     block_partials(xs, out, r0, cnt, C, Pout);
 }
 
+// one term of a Ritz product.  ritz_kernel and nmf_start_kernel both accumulate through this function, from s = 0 over l ascending,
+// so the compiler contracts (or does not contract) the multiply-add of both the same way and their sums agree bit for bit
+template <class T> __device__ inline T ritz_step(T s, T b, T w) { return s + b * w; }
+
 // out (len x kc, column-major) = B (len x ja) W (ja x kc): the Ritz vectors
 template <class T>
 __global__ __launch_bounds__(WG) void ritz_kernel(const T* __restrict__ B, long len, int ja, const T* __restrict__ W, int kc,
@@ -444,8 +448,62 @@ __global__ __launch_bounds__(WG) void ritz_kernel(const T* __restrict__ B, long 
     const int c = blockIdx.y;
     if (i >= len || c >= kc) return;
     T s = 0;
-    for (int l = 0; l < ja; ++l) s += B[(long)l * len + i] * W[(long)c * ja + l];
+    for (int l = 0; l < ja; ++l) s = ritz_step(s, B[(long)l * len + i], W[(long)c * ja + l]);
     out[(long)c * len + i] = s;
+}
+
+// The Ritz product written as an NMF start (nmf/nmf_init.hpp:71-79): out[i * k + c] = |sum_l B[l len + i] W[c ja + l]| * sq[c] for
+// c < kc, sq[c] = sqrt(sigma_c) in T; out is row-major len x k, the column-major k x len factor the fit entries take.  Columns
+// c >= kc of a row are not touched.
+//   A thread owns row i and one chunk of NS_CW = 32 columns (blockIdx.y), whose sums it keeps in registers while it walks l once:
+//   the basis is read ceil(kc / 32) times, not kc times.  32 accumulators are 32 VGPRs in fp32 and 64 in fp64; with the step's
+//   staged coefficients the kernel takes 62 VGPRs in fp32 (8 waves a SIMD) and 127 in fp64 (4 waves), and nothing spills.  A chunk
+//   of 64 would halve the basis reads again only from k = 65 on and leave fp64 two waves a SIMD.
+//   The coefficients of the chunk sit in LDS, NS_LT = 64 steps of l at a time (W[l][c], every lane reads the same address: a
+//   broadcast); tiles follow each other in l order, so the sum of (i, c) runs over l ascending exactly as ritz_kernel's.
+//   The rows leave through LDS, NS_SC = 16 columns at a time (the tile reuses the coefficient storage): sixteen consecutive lanes
+//   store sixteen consecutive values of one row, where a lane-per-row store would stride by k.
+// No atomics and no dependence on the grid: two runs are bitwise equal.
+constexpr int NS_CW = 32, NS_LT = 64, NS_SC = 16;
+__device__ inline float ns_abs(float x) { return __builtin_fabsf(x); }
+__device__ inline double ns_abs(double x) { return __builtin_fabs(x); }
+template <class T>
+__global__ __launch_bounds__(WG) void nmf_start_kernel(const T* __restrict__ B, long len, int ja, const T* __restrict__ W, int kc,
+                                                       const T* __restrict__ sq, int k, T* __restrict__ out) {
+    constexpr int LDS_W = NS_LT * NS_CW, LDS_T = WG * (NS_SC + 1);
+    __shared__ T sh[LDS_W > LDS_T ? LDS_W : LDS_T];
+    const long r0 = (long)blockIdx.x * WG;
+    const long i = r0 + threadIdx.x;
+    const long ic = i < len ? i : len - 1;             // a lane past the end reads the last row and stores nothing
+    const int c0 = blockIdx.y * NS_CW;
+    T acc[NS_CW];
+#pragma unroll
+    for (int c = 0; c < NS_CW; ++c) acc[c] = T(0);
+    for (int l0 = 0; l0 < ja; l0 += NS_LT) {
+        const int nl = min(NS_LT, ja - l0);
+        __syncthreads();
+        for (int q = threadIdx.x; q < nl * NS_CW; q += WG) {
+            const int lt = q % nl, c = q / nl;          // consecutive threads read consecutive l of one column of W
+            sh[lt * NS_CW + c] = c0 + c < kc ? W[(long)(c0 + c) * ja + l0 + lt] : T(0);
+        }
+        __syncthreads();
+        for (int lt = 0; lt < nl; ++lt) {
+            const T b = B[(long)(l0 + lt) * len + ic];
+#pragma unroll
+            for (int c = 0; c < NS_CW; ++c) acc[c] = ritz_step(acc[c], b, sh[lt * NS_CW + c]);
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < NS_CW / NS_SC; ++h) {
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < NS_SC; ++c) sh[threadIdx.x * (NS_SC + 1) + c] = acc[h * NS_SC + c];
+        __syncthreads();
+        for (int q = threadIdx.x; q < WG * NS_SC; q += WG) {
+            const int r = q / NS_SC, c = q % NS_SC, cg = c0 + h * NS_SC + c;
+            if (r0 + r < len && cg < kc) out[(r0 + r) * k + cg] = ns_abs(sh[r * (NS_SC + 1) + c]) * sq[cg];
+        }
+    }
 }
 
 }  // namespace rsv

@@ -26,13 +26,18 @@
 // l = k + oversampling <= 128 vectors, CholeskyQR2 between them, and one host synchronisation for the l x l eigenproblem at the end.
 // algorithm 3 on the four reference entries still runs Lanczos.
 //
+// The SVD-seeded start of an NMF fit (nmf/nmf_init.hpp:45-158; kernel: nmf_start_kernel in kernels_svd.hip.h) runs through the
+// build-defined entries rcppml_gpu_nmf_svd_init_ex / rcppml_gpu_nmf_svd_init_dense_ex at the end of this file: Lanczos with the
+// reference's fixed options in an output mode (Opts::nmf_start) that writes the Ritz product as W_T and H of the fit entries.
+//
 // Centering never densifies: A'u - (mu . u) 1 and A v - mu sum(v) are scalar corrections inside the epilogues.
 //
-// The host boundary of the fourteen entries is written once (section "boundary"): load_shared() / load_checked() fill the fields of
-// Opts every family shares and raise the shared refusals, attach_csc() / attach_dense() (with FullCsc for the block methods' dense
-// entries) hand the matrix over, fit() checks the device and runs Engine<float> or Engine<double> under the clock, and
-// write_shared() copies the outputs every family has.  A family adds its own pointer struct, make_*_opts, *_bytes and write_*.
-// Opts::method names what the engine runs; the reference entries' algorithm 1-4 become Method::lanczos at the boundary.
+// The host boundary of the fourteen SVD entries and the two NMF-start entries is written once (section "boundary"): load_shared() /
+// load_checked() fill the fields of Opts every family shares and raise the shared refusals, attach_csc() / attach_dense() (with
+// FullCsc for the block methods' dense entries) hand the matrix over, fit() checks the device and runs Engine<float> or
+// Engine<double> under the clock, and write_shared() copies the outputs every family has.  A family adds its own pointer struct,
+// make_*_opts, *_bytes and write_*.  Opts::method names what the engine runs; the reference entries' algorithm 1-4 become
+// Method::lanczos at the boundary.
 #include "entry_common.hip.h"
 #include "kernels_svd.hip.h"
 #include "kernels_svd_cv.hip.h"
@@ -72,6 +77,9 @@ struct Opts {
     // the krylov entries only (Method::kspr): the pass limit (0: the default) and the n x k seed (null: Lanczos); max_iter stays 0.
     // The randomized entries (Method::randomized) add no field: max_iter is the block method's q (<= 0: 3)
     int ks_iter = 0; const double* V0 = nullptr;
+    // the NMF-start entries only (Method::lanczos): the Ritz product leaves as W_T (k x m) and H (k x n) of nmf/nmf_init.hpp:71-90
+    // in Result::U / V, and init_seed seeds the fill of the rows Lanczos did not deliver
+    bool nmf_start = false; uint32_t init_seed = 0;
     // the reg entries only: L21 and angular per side, and a square graph CSC per side (p = null or lambda <= 0: none)
     double L21_u = 0, L21_v = 0, ang_u = 0, ang_v = 0;
     struct Graph {
@@ -262,6 +270,16 @@ std::vector<double> times_small(const std::vector<double>& Q, int rows, int k, c
             for (int t = 0; t < rows; ++t) y[t] += q[t] * w;
         }
     return out;
+}
+
+// svd/lanczos.hpp: jmax = min(min(m, n) - 1, max(3k, k + 50, max_iter)); k = min(m, n) may use all min(m, n) steps.  Throws when the
+// partial columns of jmax + 1 steps would not fit a consumer's LDS.
+int lanczos_steps(int m, int n, int K, int max_iter) {
+    const int mn = std::min(m, n);
+    const int cap = K >= mn ? mn : mn - 1;
+    const int jmax = std::min(cap, std::max(std::max(3 * K, K + 50), max_iter > 0 ? max_iter : 0));
+    if (jmax + 1 > NPMAX) throw std::invalid_argument("Lanczos would need more than " + std::to_string(NPMAX - 1) + " steps");
+    return jmax;
 }
 
 // ------------------------------------------------------------------------------------------------------------ engine
@@ -594,11 +612,8 @@ template <class T> struct Engine {
 
     // -------------------------------------------------------------------------------------------------------- Lanczos
     void lanczos(Result& R) {
-        const int K = o.k, mn = std::min(m, n);
-        // svd/lanczos.hpp: jmax = min(min(m, n) - 1, max(3k, k + 50, max_iter)); k = min(m, n) may use all min(m, n) steps
-        const int cap = K >= mn ? mn : mn - 1;
-        const int jmax = std::min(cap, std::max(std::max(3 * K, K + 50), o.max_iter > 0 ? o.max_iter : 0));
-        if (jmax + 1 > NPMAX) throw std::invalid_argument("Lanczos would need more than " + std::to_string(NPMAX - 1) + " steps");
+        const int K = o.k;
+        const int jmax = lanczos_steps(m, n, K, o.max_iter);
         const int nbm = nblk(m), nbn = nblk(n);
         const T eps = std::numeric_limits<T>::epsilon() * T(100);
         const double conv_tol = o.tol > 0 ? o.tol : 1e-10;
@@ -679,7 +694,10 @@ template <class T> struct Engine {
         const int kc = std::min(K, ja);
         R.k_sel = kc;
         R.d.clear(); R.U.clear(); R.V.clear();
-        if (kc == 0) return;
+        if (kc == 0) {
+            if (o.nmf_start) nmf_start(R, nullptr, nullptr, 0, 0, {}, {}, {});
+            return;
+        }
         // An alpha breakdown at step ja (A p_ja in span Q) leaves beta_ja coupling p_ja: A [P_ja p_ja] = Q_ja [B_ja | beta_ja e],
         // so the small problem is the (ja + 1)-column bidiagonal with a trailing alpha = 0 (its extra singular value is 0 and the
         // last row of its left vectors vanishes).  svd/lanczos.hpp drops beta_ja there, which is wrong on low-rank input.
@@ -694,6 +712,10 @@ template <class T> struct Engine {
             for (int l = 0; l < ja; ++l) wu[(size_t)c * ja + l] = (T)Ub[(size_t)c * nbd + l];
             for (int l = 0; l < nbd; ++l) wv[(size_t)c * nbd + l] = (T)Vb[(size_t)c * nbd + l];
         }
+        if (o.nmf_start) {
+            nmf_start(R, Q, Pm, ja, nbd, wu, wv, sig);
+            return;
+        }
         DevBuf dwu, dwv, ou, ov;
         upload_vec(wu, dwu);
         upload_vec(wv, dwv);
@@ -707,6 +729,47 @@ template <class T> struct Engine {
         R.V.resize((size_t)n * kc);
         download_cast<T>(g.c, ou, (size_t)m * kc, R.U.data(), s);
         download_cast<T>(g.c, ov, (size_t)n * kc, R.V.data(), s);
+    }
+    // The output mode of the NMF-start entries, in place of the two ritz_kernel launches: R.U = W_T (k x m column-major) with
+    // W_T(c, i) = |u_c(i)| sqrt(sigma_c) and R.V = H (k x n) likewise for the R.k_sel = kc delivered triplets (nmf/nmf_init.hpp:71-79),
+    // one launch a side and one download of len x k values a side.  Rows kc .. k - 1 are the reference's fill (:82-90): one
+    // sequential SplitMix64 stream, the (k - kc) x m block of W column by column (rng.hpp:195-201), then the block of H.
+    void nmf_start(Result& R, const T* Q, const T* Pm, int ja, int nbd, const std::vector<T>& wu, const std::vector<T>& wv,
+                   const std::vector<double>& sig) {
+        const int K = o.k, kc = R.k_sel;
+        std::vector<T> hu((size_t)m * K, T(0)), hv((size_t)n * K, T(0));
+        if (kc > 0) {
+            std::vector<T> sq(kc);
+            for (int c = 0; c < kc; ++c) sq[c] = std::sqrt((T)sig[c]);
+            DevBuf dwu, dwv, dsq, ou, ov;
+            upload_vec(wu, dwu);
+            upload_vec(wv, dwv);
+            upload_vec(sq, dsq);
+            grow<T>(ou, hu.size()); grow<T>(ov, hv.size());
+            HIPCHK(hipMemsetAsync(ou.p, 0, hu.size() * sizeof(T), s));
+            HIPCHK(hipMemsetAsync(ov.p, 0, hv.size() * sizeof(T), s));
+            const int chunks = (kc + NS_CW - 1) / NS_CW;
+            hipLaunchKernelGGL(nmf_start_kernel<T>, dim3((m + WG - 1) / WG, chunks), dim3(WG), 0, s, Q, (long)m, ja,
+                               (const T*)dwu.as<T>(), kc, (const T*)dsq.as<T>(), K, ou.as<T>());
+            hipLaunchKernelGGL(nmf_start_kernel<T>, dim3((n + WG - 1) / WG, chunks), dim3(WG), 0, s, Pm, (long)n, nbd,
+                               (const T*)dwv.as<T>(), kc, (const T*)dsq.as<T>(), K, ov.as<T>());
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(hu.data(), ou.p, hu.size() * sizeof(T), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(hv.data(), ov.p, hv.size() * sizeof(T), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        if (kc < K) {
+            const size_t rows = (size_t)(K - kc);
+            const uint32_t fs = o.init_seed == 0 ? 54321u : o.init_seed + 999u;        // wraps in uint32, as the reference's does
+            const std::vector<T> f = splitmix<T>(fs == 0 ? 12345ull : (uint64_t)fs, 0, rows * ((size_t)m + n));    // rng.hpp:73-74
+            size_t q = 0;
+            for (int j = 0; j < m; ++j)
+                for (size_t i = 0; i < rows; ++i) hu[(size_t)j * K + kc + i] = f[q++];
+            for (int j = 0; j < n; ++j)
+                for (size_t i = 0; i < rows; ++i) hv[(size_t)j * K + kc + i] = f[q++];
+        }
+        R.U.assign(hu.begin(), hu.end());
+        R.V.assign(hv.begin(), hv.end());
     }
     void upload_vec(const std::vector<T>& h, DevBuf& b) {
         grow<T>(b, h.size());
@@ -1433,3 +1496,119 @@ extern "C" void rcppml_gpu_svd_randomized_dense_ex(const double* A_data, int* m,
     });
 }
 
+// ------------------------------------------------------------------------------------------------------------ NMF-start entries
+// Build-defined: the SVD-seeded start of an NMF fit (nmf/nmf_init.hpp:45-158 initialize_lanczos / initialize_irlba, which R's
+// nmf(seed = "lanczos" | "irlba") reaches as init_mode 1 / 2; the plugin's NMF ABI has no slot for init_mode).  The Lanczos engine
+// with the reference's fixed options -- tol 1e-10, max_iter 0, no centring, the start vector of *seed -- in its NMF-start output
+// mode.  Mode 2 runs the same engine, as algorithm 1 (irlba) does on the rcppml_gpu_svd_pca_* entries.
+namespace {
+struct NiRaw { int *k, *seed, *mode; double *W_T, *H, *d; int *out_k_svd, *out_iters; double* out_wall_time_ms; };
+
+// device bytes of a call, generously: the matrix with its fp64 staging copy (and the CSR of a CSC), the two Lanczos bases, the
+// work vectors and partials, the two k-wide outputs
+size_t ni_bytes(const Opts& o, size_t ts) {
+    const size_t len = (size_t)o.nnz, steps = (size_t)lanczos_steps(o.m, o.n, o.k, 0) + 2, mn = (size_t)o.m + o.n;
+    size_t b = len * ((o.dense ? 1 : 2) * (sizeof(int) + ts) + sizeof(double)) + (mn + 2) * sizeof(int);
+    b += mn * steps * ts + 4 * ((size_t)std::max(nblk(o.m), nblk(o.n))) * steps * ts + 3 * mn * ts;
+    return b + mn * (size_t)o.k * ts;
+}
+
+template <class Attach> void nmf_svd_init(const int* m, const int* n, const int* precision, const NiRaw& a, Attach attach) {
+    if (!a.k || !a.seed || !a.mode || !a.W_T || !a.H || !a.d || !a.out_k_svd || !a.out_iters || !a.out_wall_time_ms)
+        throw std::invalid_argument("null pointer");
+    // the shared fields the start does not have: no centring, no element constraints, and two outputs nobody reads
+    int zero_i = 0;
+    double zero_d = 0, frob = 0, no_means = 0;
+    const Shared s{a.k, &zero_i, a.seed, &zero_d, &zero_d, &zero_d, &zero_d, &zero_i, &zero_i, &zero_d, &zero_d,
+                   a.W_T, a.d, a.H, a.out_k_svd, &frob, &no_means, a.out_wall_time_ms};
+    Opts o = load_checked(s, m, n, precision, false);
+    if (*a.mode != 1 && *a.mode != 2) throw std::invalid_argument("mode must be 1 (lanczos) or 2 (irlba)");
+    o.tol = 1e-10; o.max_iter = 0;
+    o.method = Method::lanczos;
+    o.nmf_start = true; o.init_seed = (uint32_t)*a.seed;
+    (void)lanczos_steps(o.m, o.n, o.k, o.max_iter);        // the engine's own step limit, before any device work
+    attach(o);
+    all_finite(o.dense ? o.dense : o.x, (size_t)o.nnz, "the matrix");
+    const Fit f = fit(o, *precision, ni_bytes);
+    write_shared(s, o, f);
+    *a.out_iters = f.R.iters.empty() ? 0 : f.R.iters[0];
+}
+}  // namespace
+
+#define RCPPML_NMF_INIT_PARAMS                                                                                                    \
+    int *precision, int *k, int *seed, int *mode, double *W_T, double *H, double *d, int *out_k_svd, int *out_iters,               \
+        double *out_wall_time_ms, int *out_status
+#define RCPPML_NMF_INIT_RAW NiRaw{k, seed, mode, W_T, H, d, out_k_svd, out_iters, out_wall_time_ms}
+
+extern "C" void rcppml_gpu_nmf_svd_init_ex(const int* col_ptr, const int* row_idx, const double* values, int* m, int* n, int* nnz,
+                                           RCPPML_NMF_INIT_PARAMS) {
+    entry_guard(out_status, [&] {
+        nmf_svd_init(m, n, precision, RCPPML_NMF_INIT_RAW, [&](Opts& o) {
+            if (!nnz) throw std::invalid_argument("null pointer");
+            attach_csc(o, col_ptr, row_idx, values, *nnz);
+        });
+    });
+}
+extern "C" void rcppml_gpu_nmf_svd_init_dense_ex(const double* A_data, int* m, int* n, RCPPML_NMF_INIT_PARAMS) {
+    entry_guard(out_status, [&] { nmf_svd_init(m, n, precision, RCPPML_NMF_INIT_RAW, [&](Opts& o) { attach_dense(o, A_data); }); });
+}
+
+// Build-defined, for tools/init_bench.py: the device time of nmf_start_kernel beside the ritz_kernel launch it replaces, on one
+// side of a start (a len x ja basis of uniform draws, kc of k columns), each the median of *reps timed launches after a warm-up,
+// between two events on the stream.  Nothing of a fit runs here.
+namespace {
+template <class T> void start_time(long len, int ja, int kc, int k, int reps, double* start_ms, double* ritz_ms) {
+    CtxGuard g(env_device());
+    hipStream_t s = g.s;
+    const std::vector<T> hb = splitmix<T>(42, 0, (size_t)len * ja), hw = splitmix<T>(43, 0, (size_t)ja * kc), hs = splitmix<T>(44, 0, (size_t)kc);
+    DevBuf dB, dW, dS, o1, o2;
+    const T* B = upload<T>(dB, hb.data(), hb.size(), s);
+    const T* W = upload<T>(dW, hw.data(), hw.size(), s);
+    const T* sq = upload<T>(dS, hs.data(), hs.size(), s);
+    T* out_start = zeros<T>(o1, (size_t)len * k, s);
+    T* out_ritz = zeros<T>(o2, (size_t)len * kc, s);
+    HIPCHK(hipStreamSynchronize(s));
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    auto median = [&](bool start) {
+        std::vector<double> ms;
+        for (int r = 0; r <= reps; ++r) {              // run 0 is the warm-up
+            HIPCHK(hipEventRecord(e0, s));
+            if (start)
+                hipLaunchKernelGGL(nmf_start_kernel<T>, dim3((unsigned)((len + WG - 1) / WG), (kc + NS_CW - 1) / NS_CW), dim3(WG), 0, s, B, len,
+                                   ja, W, kc, sq, k, out_start);
+            else
+                hipLaunchKernelGGL(ritz_kernel<T>, dim3((unsigned)((len + WG - 1) / WG), kc), dim3(WG), 0, s, B, len, ja, W, kc, out_ritz);
+            HIPCHK(hipEventRecord(e1, s));
+            HIPCHK(hipEventSynchronize(e1));
+            HIPCHK(hipGetLastError());
+            float t = 0;
+            HIPCHK(hipEventElapsedTime(&t, e0, e1));
+            if (r > 0) ms.push_back(t);
+        }
+        std::sort(ms.begin(), ms.end());
+        return ms[ms.size() / 2];
+    };
+    *start_ms = median(true);
+    *ritz_ms = median(false);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+}
+}  // namespace
+
+extern "C" void rcppml_hip_nmf_start_time(int* precision, int* len, int* ja, int* kc, int* k, int* reps, double* out_start_ms,
+                                          double* out_ritz_ms, int* out_status) {
+    entry_guard(out_status, [&] {
+        if (!precision || !len || !ja || !kc || !k || !reps || !out_start_ms || !out_ritz_ms) throw std::invalid_argument("null pointer");
+        if (*precision != RCPPML_F32 && *precision != RCPPML_F64) throw std::invalid_argument("precision must be RCPPML_F32 or RCPPML_F64");
+        if (*len < 1 || *ja < 1 || *ja >= NPMAX || *kc < 1 || *kc > *k || *k >= NPMAX || *reps < 1 || *reps > 1000)
+            throw std::invalid_argument("len >= 1, 1 <= ja < 4096, 1 <= kc <= k < 4096 and 1 <= reps <= 1000 are required");
+        const size_t ts = *precision == RCPPML_F32 ? sizeof(float) : sizeof(double);
+        device_ready(((size_t)*len * ((size_t)*ja + *k + *kc) + (size_t)*ja * *kc + *kc) * ts, "the timing");
+        double a = 0, b = 0;
+        if (*precision == RCPPML_F32) start_time<float>(*len, *ja, *kc, *k, *reps, &a, &b);
+        else start_time<double>(*len, *ja, *kc, *k, *reps, &a, &b);
+        *out_start_ms = a; *out_ritz_ms = b;
+    });
+}

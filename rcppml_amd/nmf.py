@@ -3,6 +3,7 @@
 Same argument names, meaning, defaults and error behaviour as the R functions (R/nmf_thin.R:219-229,
 R/solve.R:84, R/predict_nmf.R:48, R/nmf_methods.R:356), restricted to what the MI355X plugin implements
 (MSE and NB loss, CD or Cholesky+clip, L1/L2/upper bounds, non-negativity flags, explicit mask, L1/L2/no normalisation).
+String seeds (R/nmf_thin.R:390-403) start a fit from a truncated SVD computed on the device (rcppml_gpu_nmf_svd_init_ex).
 All compute goes through RcppML_gpu.so (rcppml_amd._abi); anything else raises -- there is no CPU path here.
 """
 import numpy as np
@@ -66,6 +67,38 @@ def select_solver(solver, k, L1, loss="mse", use_gpu=True):
     return "cholesky" if (k < 32 and all(v == 0 for v in L1)) else "cd"
 
 
+# R/nmf_thin.R:390-403: the string seeds and the init_mode each maps to (0: the random start, 1: Lanczos, 2: IRLBA)
+_SEED_STRINGS = {"random": 0, "lanczos": 1, "svd": 1, "randomized": 1, "irlba": 2}
+
+
+def _seed_init_mode(seed):
+    """init_mode of a seed argument: None for anything but a string, else R's mapping or R's error."""
+    if not isinstance(seed, str):
+        return None
+    if seed not in _SEED_STRINGS:
+        raise ValueError("Unknown seed string '%s'. Valid: NULL, integer, matrix, 'lanczos', 'irlba', 'randomized', 'svd'" % seed)
+    return _SEED_STRINGS[seed]
+
+
+def _check_svd_seed(svd_seed, init_mode):
+    if svd_seed is None:
+        return None
+    if isinstance(svd_seed, (bool, np.bool_)) or not isinstance(svd_seed, (int, np.integer)) or not (0 <= int(svd_seed) <= 0xFFFFFFFF):
+        raise ValueError("'svd_seed' must be a single integer in [0, 2^32)")
+    if not init_mode:
+        raise ValueError("'svd_seed' needs an SVD seed: seed = 'lanczos', 'irlba', 'randomized' or 'svd'")
+    return int(svd_seed)
+
+
+def _svd_start(data, A, dense, k, seed_int, init_mode, precision):
+    """nmf/nmf_init.hpp:45-158 on the device, in the fit's precision: (W_T (m, k), H (n, k), the init fields of misc)."""
+    r = _abi.nmf_svd_init(np.asarray(data, np.float64) if dense else (A.p, A.i, A.x, A.shape[0], A.shape[1]), k, dense=dense,
+                          precision="float" if precision == "fp32" else "double", seed=seed_int, mode=init_mode)
+    if r["status"] != 0:
+        raise _abi.BackendError("GPU NMF SVD start failed: %s" % r.get("error"))
+    return r["W_T"], r["H"], dict(init_k_svd=r["k_svd"], init_iters=r["iters"], init_wall_ms=r["wall_ms"])
+
+
 class CVTable(list):
     """The reference's `nmfCrossValidate` data.frame (R/nmf_thin.R:1074-1090): a list of rows {rep, k, train_mse, test_mse, best_iter,
     total_iter, mean_theta}; `col(name)` returns one column."""
@@ -77,7 +110,8 @@ class CVTable(list):
 def _cv_across_ranks(data, ranks, seed, cv_seed, test_fraction, kw):
     """R/nmf_thin.R:803-812, :1034-1090: test_fraction defaults to 0.1, the replicates' CV seeds default to the fit's seed, and every
     (replicate, rank) fit starts from the reference's own initialize_factors stream SplitMix64((cv_seed + rank) mod INT_MAX) -- one
-    stream fills W_T and continues into H (nmf/nmf_init.hpp:166-182) -- with the replicate's holdout pattern."""
+    stream fills W_T and continues into H (nmf/nmf_init.hpp:166-182) -- with the replicate's holdout pattern.  Under an SVD seed
+    every fit starts from its own SVD start instead, seeded the same way (nmf/fit_cv.hpp:152-156)."""
     from .data import init_factors
     if isinstance(seed, (list, tuple)) or (seed is not None and np.ndim(seed) == 2):
         raise ValueError("Multiple initializations are not compatible with cross-validation. Use a single seed or matrix.")
@@ -85,16 +119,26 @@ def _cv_across_ranks(data, ranks, seed, cv_seed, test_fraction, kw):
         test_fraction = 0.1
     A = _as_csc(data)
     m, n = A.shape
-    seed_int = int(np.random.SeedSequence().generate_state(1)[0] % (2 ** 31 - 1)) + 1 if seed is None else int(np.atleast_1d(seed)[0])
+    svd_seed = kw.pop("svd_seed")
+    svd = bool(_seed_init_mode(seed))
+    if isinstance(seed, str):          # a string draws the fit's seed as seed = None does, unless svd_seed pins it
+        seed_int = svd_seed
+    else:
+        seed_int = None if seed is None else int(np.atleast_1d(seed)[0])
+    if seed_int is None:
+        seed_int = int(np.random.SeedSequence().generate_state(1)[0] % (2 ** 31 - 1)) + 1
     cv_seeds = [seed_int] if cv_seed is None else [int(v) for v in np.atleast_1d(cv_seed)]
     rows = CVTable()
     for rep, cs in enumerate(cv_seeds, start=1):
         for rank in ranks:
             init_seed = int((cs + rank) % (2 ** 31 - 1))
-            # (the stream is drawn in the compute Scalar: initialize_factors<float> when the fit runs in fp32, as the single fit does)
-            W0, H0 = init_factors(init_seed, rank, m, n, np.float32 if kw.get("precision", "fp32") == "fp32" else np.float64)
-            W0, H0 = W0.astype(np.float64), H0.astype(np.float64)
-            mod = nmf(data, rank, seed=W0, h_init=H0.T, test_fraction=test_fraction, cv_seed=cs, **kw)
+            if svd:
+                mod = nmf(data, rank, seed=seed, svd_seed=init_seed, test_fraction=test_fraction, cv_seed=cs, **kw)
+            else:
+                # (the stream is drawn in the compute Scalar: initialize_factors<float> when the fit runs in fp32, as the single fit does)
+                W0, H0 = init_factors(init_seed, rank, m, n, np.float32 if kw.get("precision", "fp32") == "fp32" else np.float64)
+                W0, H0 = W0.astype(np.float64), H0.astype(np.float64)
+                mod = nmf(data, rank, seed=W0, h_init=H0.T, test_fraction=test_fraction, cv_seed=cs, **kw)
             th = mod.misc.get("theta")
             rows.append(dict(rep=rep, k=rank, train_mse=mod.misc["loss"], test_mse=mod.misc.get("best_test_loss", mod.misc["test_loss"]),
                              best_iter=int(mod.misc.get("best_iter", 0)) + 1, total_iter=mod.misc["iter"],
@@ -108,12 +152,17 @@ def nmf(data, k, tol=1e-4, maxit=100, L1=(0.0, 0.0), L2=(0.0, 0.0), seed=None, m
         patience=5, h_init=None, precision="fp32", resource="gpu", dispersion="per_row", irls_max_iter=5, irls_tol=1e-4,
         nb_size_init=10.0, nb_size_max=1e6, nb_size_min=0.01, tweedie_power=1.5, L21=(0.0, 0.0), angular=(0.0, 0.0),
         graph_W=None, graph_H=None, graph_lambda=(0.0, 0.0), target_H=None, target_lambda=0.0, theta_init=0.1, theta_max=5.0,
-        theta_min=0.0, cv_seed=None):
+        theta_min=0.0, cv_seed=None, svd_seed=None):
     """Non-negative matrix factorisation A ~ w diag(d) h by alternating NNLS on the MI355X.
 
     `L1`, `L2`, `upper_bound`, `nonneg` are c(w, h) pairs (src/RcppFunctions_nmf.cpp:59-62).
     `seed`: None / int -> W_init = matrix(runif(m*k), m, k) after set.seed(seed) (R/nmf_thin.R:790-797) and
-    H from SplitMix64(seed) (nmf/fit_cpu.hpp:200-207); or an m x k (or k x m) matrix used as W_init.
+    H from SplitMix64(seed) (nmf/fit_cpu.hpp:200-207); or an m x k (or k x m) matrix used as W_init; or a string
+    (R/nmf_thin.R:390-403): "random" is None, "lanczos" / "svd" / "randomized" (init_mode 1) and "irlba" (init_mode 2) start the fit
+    from a rank-k truncated SVD computed on the device in the fit's precision, W = |U| sqrt(S), H = sqrt(S) |V|'
+    (nmf/nmf_init.hpp:45-158; rcppml_gpu_nmf_svd_init_ex, both modes run Lanczos).  The fit's integer seed is then drawn as for
+    None; `svd_seed` (an int) pins it, as set.seed() does in R.  `h_init` cannot be combined with an SVD seed.
+    misc gains init (the string), init_k_svd, init_iters and init_wall_ms.
     `precision`: "fp32" is what the reference computes in (F1); "fp64" is the parity mode.
     `robust`: False | True (Huber delta 1.345) | "mae" (1e-4) | positive delta (R/nmf_thin.R:343-352).
     `graph_W` (m x m) / `graph_H` (n x n): sparse graph Laplacians, `graph_lambda` = c(w, h) (R/nmf_thin.R:67-68, 500-506).
@@ -126,10 +175,17 @@ def nmf(data, k, tol=1e-4, maxit=100, L1=(0.0, 0.0), L2=(0.0, 0.0), seed=None, m
     `seed` a vector of integers or a list of W matrices: one fit per initialisation, the one with the lowest loss is returned
     (R/nmf_thin.R:744-786, :828-917; misc$all_init_losses / best_init_idx).
     """
+    # ---- string seeds (R/nmf_thin.R:390-403), checked before anything runs
+    init_mode = _seed_init_mode(seed)
+    svd_seed = _check_svd_seed(svd_seed, init_mode)
+    if init_mode and h_init is not None:
+        raise ValueError("h_init cannot be combined with an SVD seed: the seed sets both factors")
+    if init_mode == 0:
+        seed = None
     # ---- several ranks: cross-validation table (R/nmf_thin.R:803-812, 1034-1090)
     if np.ndim(k) == 1 and len(k) > 1:
         kw = dict(locals())
-        for drop in ("data", "k", "seed", "cv_seed", "test_fraction", "h_init"):
+        for drop in ("data", "k", "seed", "cv_seed", "test_fraction", "h_init", "init_mode"):
             kw.pop(drop)
         return _cv_across_ranks(data, [int(v) for v in k], seed, cv_seed, test_fraction, kw)
     if np.ndim(k) == 1:
@@ -146,7 +202,7 @@ def nmf(data, k, tol=1e-4, maxit=100, L1=(0.0, 0.0), L2=(0.0, 0.0), seed=None, m
         if test_fraction and test_fraction > 0:
             raise ValueError("Multiple initializations are not compatible with cross-validation. Use a single seed or matrix.")
         kw = dict(locals())
-        for drop in ("data", "k", "seed", "multi"):
+        for drop in ("data", "k", "seed", "multi", "init_mode"):
             kw.pop(drop)
         fits = [nmf(data, k, seed=sd, **kw) for sd in multi]
         losses = [f.misc["loss"] for f in fits]
@@ -267,7 +323,10 @@ def nmf(data, k, tol=1e-4, maxit=100, L1=(0.0, 0.0), L2=(0.0, 0.0), seed=None, m
     if graph_args and (loss != "mse" or robust_delta > 0 or (mask is not None and not isinstance(mask, str)) or k > 128):
         raise NotImplementedError("graph regularisation is implemented for the plain MSE path, k <= 128")
     # ---- initialisation
-    if seed is None:
+    if init_mode:
+        seed_int = svd_seed if svd_seed is not None else int(np.random.SeedSequence().generate_state(1)[0] % (2 ** 31 - 1)) + 1
+        W0 = None          # built from the SVD below, once the entry the fit takes is known
+    elif seed is None:
         seed_int = int(np.random.SeedSequence().generate_state(1)[0] % (2 ** 31 - 1)) + 1
         W0 = r_runif(seed_int, m * k).reshape(k, m).T.copy()          # matrix(runif(m*k), m, k): column-major fill
     elif np.ndim(seed) == 2:
@@ -285,8 +344,10 @@ def nmf(data, k, tol=1e-4, maxit=100, L1=(0.0, 0.0), L2=(0.0, 0.0), seed=None, m
     else:
         seed_int = int(seed)
         W0 = r_runif(seed_int, m * k).reshape(k, m).T.copy()
-    W_T = np.ascontiguousarray(W0, dtype=np.float64)                   # (m, k) C-order == column-major k x m
-    if h_init is not None:
+    W_T = None if init_mode else np.ascontiguousarray(W0, dtype=np.float64)   # (m, k) C-order == column-major k x m
+    if init_mode:
+        H = None
+    elif h_init is not None:
         H = np.ascontiguousarray(np.asarray(h_init, dtype=np.float64).T)   # h_init is k x n
         if H.shape != (n, k):
             raise ValueError("h_init must be k x n")
@@ -307,6 +368,12 @@ def nmf(data, k, tol=1e-4, maxit=100, L1=(0.0, 0.0), L2=(0.0, 0.0), seed=None, m
             if M.shape != A.shape:
                 raise ValueError("mask dimensions must match data")
             mask_arg = (M.p, M.i)
+    dense_entry_ok = mask_arg is None and not graph_args and sort_model and target_H is None and float(cd_tol) == 1e-8
+    init_misc = {}
+    if init_mode:
+        # the dense fit entry starts from the dense init entry: no CSC copy of a dense matrix is read
+        W_T, H, init_misc = _svd_start(data, A, dense_in and not cv and dense_entry_ok, k, seed_int, init_mode, precision)
+        init_misc = dict(init=seed, **init_misc)
     if cv:
         # nmf/fit_cv.hpp: speckled holdout mask (seed = the fit's seed), per-column Gram correction, early stopping on the
         # test loss with `patience`; mask = "zeros" <=> mask_zeros (only nonzeros can be held out)
@@ -339,11 +406,10 @@ def nmf(data, k, tol=1e-4, maxit=100, L1=(0.0, 0.0), L2=(0.0, 0.0), seed=None, m
                     best_test_loss=res["best_test_loss"], best_iter=res["best_iter"], loss_history=res.get("train_history"),
                     test_loss_history=res.get("test_history"), solver=solver, solver_mode=0 if solver == "cd" else 1,
                     L1=(L1w, L1h), L2=(L2w, L2h), seed=seed_int, cv_seed=(int(cv_seed) if cv_seed is not None else seed_int) & 0x7FFFFFFF,
-                    precision=precision, resource="gpu", loss_type=loss, test_fraction=float(test_fraction))
+                    precision=precision, resource="gpu", loss_type=loss, test_fraction=float(test_fraction), **init_misc)
         if irls_cv and loss == "gp":
             misc["theta"] = res.get("theta")
         return NMFModel(w=W_T.copy(), d=res["d"], h=H.T.copy(), misc=misc)
-    dense_entry_ok = mask_arg is None and not graph_args and sort_model and target_H is None and float(cd_tol) == 1e-8
     if dense_in and (loss != "mse" or robust_delta > 0) and not dense_entry_ok:
         # a dense matrix under a distribution loss / robust modifier is weighted ENTRY BY ENTRY, zeros included (nnls_batch_irls_dense,
         # fit_cpu.hpp:607-614); the sparse entry gives zeros weight 1 -- another model.  Unrelated arguments must not switch between the
@@ -372,7 +438,7 @@ def nmf(data, k, tol=1e-4, maxit=100, L1=(0.0, 0.0), L2=(0.0, 0.0), seed=None, m
         misc = dict(tol=res["tol"], iter=res["iter"], loss=res["loss"], converged=res["converged"], solver=solver,
                     solver_mode=0 if solver == "cd" else 1, L1=(L1w, L1h), L2=(L2w, L2h), seed=seed_int, precision=precision,
                     resource="gpu", loss_type=loss, input="dense", loss_history=None,
-                    entry="rcppml_gpu_nmf_dense_unified_" + ("float" if precision == "fp32" else "double"))
+                    entry="rcppml_gpu_nmf_dense_unified_" + ("float" if precision == "fp32" else "double"), **init_misc)
         if loss != "mse":
             misc["theta"] = res["theta"]
         return NMFModel(w=W_T.copy(), d=res["d"], h=H.T.copy(), misc=misc)
@@ -401,7 +467,7 @@ def nmf(data, k, tol=1e-4, maxit=100, L1=(0.0, 0.0), L2=(0.0, 0.0), seed=None, m
     misc = dict(tol=res["tol"], iter=res["iter"], loss=res["loss"], loss_history=res.get("loss_history"),
                 converged=res["converged"], solver=solver, solver_mode=0 if solver == "cd" else 1, L1=(L1w, L1h),
                 L2=(L2w, L2h), seed=seed_int, precision=precision, resource="gpu", loss_type=loss,
-                entry="rcppml_gpu_nmf_target" if target_args else "rcppml_gpu_nmf_ex")
+                entry="rcppml_gpu_nmf_target" if target_args else "rcppml_gpu_nmf_ex", **init_misc)
     if loss != "mse":
         misc["theta"] = res["theta"]                                   # R: misc$theta (RcppFunctions_nmf.cpp:156-158)
     return NMFModel(w=W_T.copy(), d=res["d"], h=H.T.copy(), misc=misc)
