@@ -12,7 +12,7 @@
 //             the current column without a warm-start correction of b, exactly as the reference does.
 // ============================================================================
 #pragma once
-#include "kernels.hip.h"
+#include "mfma_gram_tile.hip.h"
 
 namespace rk {
 
@@ -117,199 +117,12 @@ __global__ __launch_bounds__(256) void cv_solve_kernel(
 // or rank-4 (fp64) updates  G_local -= f f^T  on an accumulator tile initialised with G (A operand = -f, B operand = f) --
 // against k shuffles and k LDS read-modify-writes per held-out row in cv_solve_kernel.  With zeros held out a column of a
 // 20 000-row matrix has ~2 000 such rows.
-//
-// A tile policy owns the accumulators of one wave and says how they meet LDS:
-//   Scalar, KP (padded rank of G_local), FS (stride of a staged row), tile_elems, wave_elems (LDS elements of one wave: the
-//   staging area, aliased by G_local afterwards, then the row queue -- the host sizes the launch from it);
-//   init(Gfull, k), flush(cnt, hq, F, k) (apply the first cnt <= 32 queued rows), park(Gl) (G_local to LDS, [c][r]) and
-//   solve_cd(Gl, b, x, ...).
+// The accumulators, their way to LDS and the CD solve are a Gram tile policy of mfma_gram_tile.hip.h; behind the tile's LDS
+// (the staging area, aliased by G_local afterwards) stands the row queue.
 // ---------------------------------------------------------------------------
 constexpr int CV_QCAP = 96;   // row queue (ints): at most 31 rows waiting + 64 appended
-
-// fp32, k <= 32 (k % 4 == 0): one 32 x 32 tile, v_mfma_f32_32x32x2_f32; staging: lane = row t, feature half hh
-struct CvTile32 {
-    typedef float Scalar;
-    static constexpr int KP = 32, FS = 36;
-    static constexpr int tile_elems = 32 * FS, wave_elems = tile_elems + CV_QCAP;
-    float* Fst;
-    int lane, r, hh;
-    f32x16 acc;
-    __device__ __forceinline__ CvTile32(float* st, int lane_) : Fst(st), lane(lane_), r(lane_ & 31), hh(lane_ >> 5) {}
-    __device__ __forceinline__ void init(const float* __restrict__ Gfull, int k) {
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int gi = (v & 3) + 8 * (v >> 2) + 4 * hh, gj = r;
-            acc[v] = (gi < k && gj < k) ? Gfull[(int64_t)gj * k + gi] : (gi == gj ? 1.f : 0.f);
-        }
-    }
-    __device__ __forceinline__ void flush(int cnt, const int* hq, const float* __restrict__ F, int k) {
-        const bool ok = r < cnt;
-        const int row = ok ? hq[r] : 0;
-        const float* fsrc = F + (int64_t)row * k + 16 * hh;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int c0 = 16 * hh + 4 * q;
-            const float4 v = (ok && c0 < k) ? *reinterpret_cast<const float4*>(fsrc + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-            *reinterpret_cast<float4*>(Fst + r * FS + c0) = v;
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int nst = (cnt + 1) >> 1;
-#pragma unroll 4
-        for (int s2 = 0; s2 < nst; ++s2) {
-            const float fv = Fst[(2 * s2 + hh) * FS + r];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(-fv, fv, acc, 0, 0, 0);
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    __device__ __forceinline__ void park(float* Gl) const {
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int gi = (v & 3) + 8 * (v >> 2) + 4 * hh;
-            Gl[gi * KP + r] = acc[v];
-        }
-    }
-    // the lane's column of the corrected Gram in registers: the sweep picks row i with a wave-uniform register-indexed
-    // move instead of an LDS read on the dependent chain of every step (as irls_nb_mfma32_kernel does)
-    __device__ __forceinline__ void solve_cd(const float* Gl, float& b, float& x, bool fok, float l1, int nonneg, int maxit) const {
-        const int ll = lane < KP ? lane : 0;
-        const float gd = Gl[ll * KP + ll];
-        typedef float f32x32 __attribute__((ext_vector_type(32)));
-        f32x32 gcol;
-#pragma unroll
-        for (int c = 0; c < KP; ++c) gcol[c] = Gl[c * KP + ll];
-        float gg[KP];
-#pragma unroll
-        for (int c = 0; c < KP; ++c) gg[c] = gcol[c];
-        cd_static_sweeps_scaled_f32<KP>(b, x, gd, fok, l1, nonneg, maxit, gg);
-    }
-};
-
-// fp32, 32 < k <= 64 (k % 4 == 0): a 2 x 2 grid of 32 x 32 tiles (three MFMAs per pair of held-out rows; the lower-left tile is
-// the transpose of the upper-right one and is never computed), lane = feature over the whole wave in the solve; 16 KiB of LDS
-// per wave for G_local, whose head doubles as the 32 x FS staging area (two blocks per CU)
-struct CvTile32x2 {
-    typedef float Scalar;
-    static constexpr int KP = 64, FS = 68;
-    static constexpr int tile_elems = KP * KP, wave_elems = tile_elems + CV_QCAP;
-    float* Fst;
-    int lane, r, hh;
-    f32x16 a00, a01, a11;
-    __device__ __forceinline__ CvTile32x2(float* st, int lane_) : Fst(st), lane(lane_), r(lane_ & 31), hh(lane_ >> 5) {}
-    __device__ __forceinline__ void init(const float* __restrict__ Gfull, int k) {
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int gi = (v & 3) + 8 * (v >> 2) + 4 * hh, gj = r;
-            auto base = [&](int i2, int j2) { return (i2 < k && j2 < k) ? Gfull[(int64_t)j2 * k + i2] : (i2 == j2 ? 1.f : 0.f); };
-            a00[v] = base(gi, gj); a01[v] = base(gi, gj + 32); a11[v] = base(gi + 32, gj + 32);
-        }
-    }
-    __device__ __forceinline__ void flush(int cnt, const int* hq, const float* __restrict__ F, int k) {
-        const bool ok = r < cnt;
-        const int row = ok ? hq[r] : 0;
-        const float* fsrc = F + (int64_t)row * k + 32 * hh;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int c0 = 32 * hh + 4 * q;
-            const float4 v = (ok && c0 < k) ? *reinterpret_cast<const float4*>(fsrc + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-            *reinterpret_cast<float4*>(Fst + r * FS + c0) = v;
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int nst = (cnt + 1) >> 1;
-#pragma unroll 2
-        for (int s2 = 0; s2 < nst; ++s2) {
-            const float f0 = Fst[(2 * s2 + hh) * FS + r], f1 = Fst[(2 * s2 + hh) * FS + 32 + r];
-            a00 = __builtin_amdgcn_mfma_f32_32x32x2f32(-f0, f0, a00, 0, 0, 0);
-            a01 = __builtin_amdgcn_mfma_f32_32x32x2f32(-f0, f1, a01, 0, 0, 0);
-            a11 = __builtin_amdgcn_mfma_f32_32x32x2f32(-f1, f1, a11, 0, 0, 0);
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    __device__ __forceinline__ void park(float* Gl) const {
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int gi = (v & 3) + 8 * (v >> 2) + 4 * hh;
-            Gl[gi * KP + r] = a00[v];
-            Gl[gi * KP + 32 + r] = a01[v];                    // G(row gi, col 32 + r) and its mirror
-            Gl[(32 + r) * KP + gi] = a01[v];
-            Gl[(gi + 32) * KP + 32 + r] = a11[v];
-        }
-    }
-    // as CvTile32::solve_cd, the column in two halves: hipcc indexes 32-element vectors with s_set_gpr_idx, 64-element ones
-    // through scratch
-    __device__ __forceinline__ void solve_cd(const float* Gl, float& b, float& x, bool fok, float l1, int nonneg, int maxit) const {
-        const int ll = lane;
-        const float gd = Gl[ll * KP + ll];
-        typedef float f32x32 __attribute__((ext_vector_type(32)));
-        f32x32 gcol0, gcol1;
-#pragma unroll
-        for (int c = 0; c < 32; ++c) { gcol0[c] = Gl[c * KP + ll]; gcol1[c] = Gl[(32 + c) * KP + ll]; }
-        float gg[KP];
-#pragma unroll
-        for (int c = 0; c < 32; ++c) { gg[c] = gcol0[c]; gg[32 + c] = gcol1[c]; }
-        cd_static_sweeps_scaled_f32<KP>(b, x, gd, fok, l1, nonneg, maxit, gg);
-    }
-};
-
-// fp64, k <= 32 (k % 2 == 0): 2 x 2 tiles of 16 x 16, v_mfma_f64_16x16x4_f64 (four held-out rows per instruction step, C/D map
-// col = lane&15, row = (lane>>4) + 4v); MFMA phase: feature slot r16, K-slot kk
-struct CvTile64 {
-    typedef double Scalar;
-    static constexpr int KP = 32, FS = 34;
-    static constexpr int tile_elems = 32 * FS, wave_elems = tile_elems + CV_QCAP / 2;
-    double* Fst;
-    int lane, r, hh, r16, kk;
-    f64x4 acc[2][2];
-    __device__ __forceinline__ CvTile64(double* st, int lane_)
-        : Fst(st), lane(lane_), r(lane_ & 31), hh(lane_ >> 5), r16(lane_ & 15), kk(lane_ >> 4) {}
-    __device__ __forceinline__ void init(const double* __restrict__ Gfull, int k) {
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int gi = 16 * ti + kk + 4 * v, gj = 16 * tj + r16;
-                    acc[ti][tj][v] = (gi < k && gj < k) ? Gfull[(int64_t)gj * k + gi] : (gi == gj ? 1.0 : 0.0);
-                }
-    }
-    __device__ __forceinline__ void flush(int cnt, const int* hq, const double* __restrict__ F, int k) {
-        const bool ok = r < cnt;
-        const int row = ok ? hq[r] : 0;
-        const double* fsrc = F + (int64_t)row * k + 16 * hh;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int c0 = 16 * hh + 2 * q;
-            const double2 v = (ok && c0 < k) ? *reinterpret_cast<const double2*>(fsrc + 2 * q) : make_double2(0.0, 0.0);
-            *reinterpret_cast<double2*>(Fst + r * FS + c0) = v;
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int nst = (cnt + 3) >> 2;
-#pragma unroll 2
-        for (int s4 = 0; s4 < nst; ++s4) {
-            const int t = 4 * s4 + kk;
-            const double f0 = Fst[t * FS + r16], f1 = Fst[t * FS + 16 + r16];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(-f0, f0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(-f0, f1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(-f1, f0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(-f1, f1, acc[1][1], 0, 0, 0);
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    __device__ __forceinline__ void park(double* Gl) const {
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) Gl[(16 * ti + kk + 4 * v) * KP + 16 * tj + r16] = acc[ti][tj][v];
-    }
-    // static coordinate sweeps (cd_static_sweeps, kernels.hip.h), the lane's Gram column read from the wave's LDS tile
-    __device__ __forceinline__ void solve_cd(const double* Gl, double& b, double& x, bool fok, double l1, int nonneg, int maxit) const {
-        const int ll = lane < KP ? lane : 0;
-        const double gd = Gl[ll * KP + ll];
-        cd_static_sweeps<double, KP>(b, x, gd, fok, l1, nonneg, maxit, [&](auto IC) { return Gl[decltype(IC)::value * KP + ll]; });
-    }
-};
+// LDS elements of one wave: the host sizes the launch from it
+template <class Tile> constexpr int cv_wave_elems = Tile::tile_elems + CV_QCAP * (int)sizeof(int) / (int)sizeof(typename Tile::Scalar);
 
 template <class Tile>
 __device__ __forceinline__ void cv_solve_mfma_body(
@@ -320,7 +133,7 @@ __device__ __forceinline__ void cv_solve_mfma_body(
     typedef typename Tile::Scalar T;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    T* Gl = reinterpret_cast<T*>(smem_raw) + (size_t)wave * Tile::wave_elems;   // staged rows first, G_local [c][r] afterwards
+    T* Gl = reinterpret_cast<T*>(smem_raw) + (size_t)wave * cv_wave_elems<Tile>;   // staged rows first, G_local [c][r] afterwards
     int* hq = reinterpret_cast<int*>(Gl + Tile::tile_elems);
     const int64_t j = (int64_t)blockIdx.x * 4 + wave;
     if (j >= ncols) return;
@@ -373,14 +186,14 @@ __device__ __forceinline__ void cv_solve_mfma_body(
         }
     }
     if (qn > 0) tile.flush(qn, hq, F, k);
-    tile.park(Gl);
+    tile.park(Gl, T(0), k);
     __builtin_amdgcn_wave_barrier();
     T x = fok ? X[j * (int64_t)k + lane] : T(0);
     if (solver_mode == 1) {
         if (l1 > T(0) && fok) b -= l1;
         x = wave_chol_clip<T, Tile::KP>(Gl, b, k, nonneg, lane);
     } else {
-        tile.solve_cd(Gl, b, x, fok, l1, nonneg, maxit);
+        tile.template solve_cd<false>(Gl, b, x, fok, l1, nonneg, maxit);
     }
     if (fok) X[j * (int64_t)k + lane] = x;
 }
@@ -390,21 +203,21 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8
     const int* __restrict__ colptr, const int* __restrict__ rowidx, const float* __restrict__ vals, int64_t ncols, int nrows,
     const float* __restrict__ F, const float* __restrict__ Gfull, float* __restrict__ X, int k, unsigned long long seed,
     unsigned long long threshold, int mask_zeros, int transposed, float l1, int nonneg, int maxit, int solver_mode) {
-    cv_solve_mfma_body<CvTile32>(colptr, rowidx, vals, ncols, nrows, F, Gfull, X, k, seed, threshold, mask_zeros, transposed, l1, nonneg,
+    cv_solve_mfma_body<GramTile32>(colptr, rowidx, vals, ncols, nrows, F, Gfull, X, k, seed, threshold, mask_zeros, transposed, l1, nonneg,
                                maxit, solver_mode);
 }
 static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void cv_solve_mfma32x2_kernel(
     const int* __restrict__ colptr, const int* __restrict__ rowidx, const float* __restrict__ vals, int64_t ncols, int nrows,
     const float* __restrict__ F, const float* __restrict__ Gfull, float* __restrict__ X, int k, unsigned long long seed,
     unsigned long long threshold, int mask_zeros, int transposed, float l1, int nonneg, int maxit, int solver_mode) {
-    cv_solve_mfma_body<CvTile32x2>(colptr, rowidx, vals, ncols, nrows, F, Gfull, X, k, seed, threshold, mask_zeros, transposed, l1, nonneg,
+    cv_solve_mfma_body<GramTile32x2>(colptr, rowidx, vals, ncols, nrows, F, Gfull, X, k, seed, threshold, mask_zeros, transposed, l1, nonneg,
                                  maxit, solver_mode);
 }
 static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void cv_solve_mfma64_kernel(
     const int* __restrict__ colptr, const int* __restrict__ rowidx, const double* __restrict__ vals, int64_t ncols, int nrows,
     const double* __restrict__ F, const double* __restrict__ Gfull, double* __restrict__ X, int k, unsigned long long seed,
     unsigned long long threshold, int mask_zeros, int transposed, double l1, int nonneg, int maxit, int solver_mode) {
-    cv_solve_mfma_body<CvTile64>(colptr, rowidx, vals, ncols, nrows, F, Gfull, X, k, seed, threshold, mask_zeros, transposed, l1, nonneg,
+    cv_solve_mfma_body<GramTile64>(colptr, rowidx, vals, ncols, nrows, F, Gfull, X, k, seed, threshold, mask_zeros, transposed, l1, nonneg,
                                maxit, solver_mode);
 }
 

@@ -14,7 +14,7 @@
 // cd_nnls_col_fixed with ballot skipping of no-op coordinates (all cd_maxit sweeps: the reference passes cd_tol = 0).
 // ============================================================================
 #pragma once
-#include "kernels.hip.h"
+#include "mfma_gram_tile.hip.h"
 
 namespace rk {
 
@@ -220,6 +220,12 @@ __global__ __launch_bounds__(256) void irls_nb_solve_kernel(
 //   The CD solve is unchanged (exact sequential sweep with ballot skipping); G_w is written from the accumulator tile
 //   straight into its LDS slab, which aliases the staging buffer.
 // ---------------------------------------------------------------------------
+// LDS elements of one wave of the one-column kernels below: the tile's staging area (G_w afterwards) | (w - 1, w a) pairs | x.
+// The kernels lay their LDS out with it and the host sizes the launches from it.
+template <class Tile> constexpr int irls_wave_elems = Tile::tile_elems + 2 * Tile::CH + Tile::KP;
+static_assert(irls_wave_elems<GramTile32> == 32 * 36 + 2 * 32 + 32, "LDS layout of irls_nb_mfma32_kernel");
+static_assert(irls_wave_elems<GramTile32x2> == 64 * 64 + 2 * 32 + 64, "LDS layout of irls_nb_mfma32x2_kernel");
+static_assert(irls_wave_elems<GramTile64> == 32 * 34 + 2 * 32 + 32, "LDS layout of irls_nb_mfma64_kernel");
 // LT >= 0: the loss is known at compile time and there is no robust modifier (LT = 5: negative binomial, what C5 runs) -- the
 // weight function then holds neither the fp64 pow() of the power-variance losses nor the Huber branch, whose registers the
 // generic instantiation (LT = -1) pays for in every lane whatever loss it runs (64-VGPR budget at eight waves per SIMD).
@@ -230,8 +236,8 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8
     int nonneg, int cd_maxit, int irls_max_iter, float irls_tol, const float* __restrict__ theta_row,
     const float* __restrict__ theta_col, int loss_type, float power, float robust,
     unsigned long long* __restrict__ stats) {
-    constexpr int KP = 32, CH = 32, FS = 36;          // FS: padded row stride of the staged F rows (bank spread)
-    constexpr int WAVE_FLOATS = CH * FS + 2 * CH + KP;  // staged rows | (w-1, w a) pairs | x
+    constexpr int KP = GramTile32::KP, CH = GramTile32::CH, FS = GramTile32::FS;   // FS: padded row stride of the staged F rows
+    constexpr int WAVE_FLOATS = irls_wave_elems<GramTile32>;  // staged rows | (w-1, w a) pairs | x
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float* Fst = reinterpret_cast<float*>(smem_raw) + (size_t)wave * WAVE_FLOATS;
@@ -253,23 +259,8 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8
     int passes = 0, nsw = 0;      // IRLS passes; CD sweeps executed over all passes (work counters)
     for (int irls = 0; irls < irls_max_iter; ++irls) {
         ++passes;
-        // accumulator tile <- base Gram (identity padding), C/D map: col = lane&31, row = (v&3) + 8(v>>2) + 4(lane>>5)
-        // (four 16-byte loads off one per-lane pointer: k % 4 == 0 keeps a group of four rows on one side of k)
-        f32x16 acc;
-        {
-            const float* gb = Gbase + (int64_t)r * k + 4 * hh;
-            asm volatile("" : "+v"(gb));                 // per pass, not 16 hoisted addresses
-#pragma unroll
-            for (int v4 = 0; v4 < 4; ++v4) {
-                const int gi0 = 8 * v4 + 4 * hh;
-                const float4 g = (gi0 < k && r < k) ? *reinterpret_cast<const float4*>(gb + 8 * v4) : make_float4(0.f, 0.f, 0.f, 0.f);
-                const bool pad = r >= k;
-                acc[4 * v4 + 0] = pad && gi0 + 0 == r ? 1.f : g.x;
-                acc[4 * v4 + 1] = pad && gi0 + 1 == r ? 1.f : g.y;
-                acc[4 * v4 + 2] = pad && gi0 + 2 == r ? 1.f : g.z;
-                acc[4 * v4 + 3] = pad && gi0 + 3 == r ? 1.f : g.w;
-            }
-        }
+        GramTile32 tile(Fst, lane);                     // accumulator tile <- base Gram, 16-byte loads
+        tile.init_vec4(Gbase, k);
         if (lin) xs[lane] = x;
         float bw = 0.f;
         __builtin_amdgcn_wave_barrier();
@@ -315,26 +306,7 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8
             const float w = irls_weight_full_dev<float>(LT >= 0 ? LT : loss_type, a - recon, recon, th, power, LT >= 0 ? 0.f : robust);
             if (hh == 0) sc[r] = make_float2(ok ? w - 1.f : 0.f, ok ? w * a : 0.f);
             __builtin_amdgcn_wave_barrier();
-            // ---- phase B: nonzeros (2s, 2s+1) of the chunk per MFMA
-            const int cnt = ae - t0 < CH ? ae - t0 : CH;
-            const int nst = (cnt + 1) >> 1;
-            // (groups of four: the eight LDS reads of a group are issued ahead of its MFMAs; the nonzeros past cnt are staged as zero
-            //  rows with zero weights, so rounding the count up adds exact zeros)
-            for (int s2 = 0; s2 < nst; s2 += 4) {
-                float fv[4];
-                float2 ws[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int t = 2 * (s2 + u) + hh;
-                    fv[u] = Fst[t * FS + r];
-                    ws[u] = sc[t];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    bw = tfma(ws[u].y, fv[u], bw);                                    // b_w += f * (w a)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ws[u].x * fv[u], fv[u], acc, 0, 0, 0);   // G_w += (f (w-1)) f^T
-                }
-            }
+            tile.update_staged(ae - t0 < CH ? ae - t0 : CH, sc, bw);         // ---- phase B
             __builtin_amdgcn_wave_barrier();
         }
         bw += __shfl_xor(bw, 32, 64);
@@ -342,7 +314,7 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
             const int gi = (v & 3) + 8 * (v >> 2) + 4 * hh;
-            float val = acc[v];
+            float val = tile.acc[v];
             if (l2 > 0.f && gi == r && gi < k) val += l2;
             Gl[gi * KP + r] = val;
         }
@@ -394,7 +366,13 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8
 // (tests/test_gpu_nb.py::test_quad_equals_single).  A column that converged keeps its iterate: its row holds a zero Gram and a
 // zero residual from then on, so the sweeps the other columns still need do not move it.
 // 128 VGPRs (four waves per SIMD = 16 columns per SIMD against 8), 9.75 KiB of LDS per wave.
+// The tile's init and update are the shared ones (the update reads whatever rows are staged: 64 here); phase A, the park (the
+// slab is [col][row] with stride FS, written and picked up with 16-byte accesses) and the DPP solve are this kernel's own.
 // ---------------------------------------------------------------------------
+constexpr int IRLS_QUAD_CH = 64;
+// LDS of one wave: staged rows / G_w slab | (w-1, w a) pairs | x | b_w
+constexpr int IRLS_QUAD_WAVE_ELEMS = IRLS_QUAD_CH * GramTile32::FS + 2 * IRLS_QUAD_CH + 2 * GramTile32::KP;
+static_assert(IRLS_QUAD_WAVE_ELEMS == 64 * 36 + 2 * 64 + 2 * 32, "LDS layout of irls_nb_mfma32q_kernel");
 template <int LT>
 static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void irls_nb_mfma32q_kernel(
     const int* __restrict__ colptr, const int* __restrict__ rowidx, const float* __restrict__ vals, int64_t ncols,
@@ -402,11 +380,10 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4
     int nonneg, int cd_maxit, int irls_max_iter, float irls_tol, const float* __restrict__ theta_row,
     const float* __restrict__ theta_col, int loss_type, float power, float robust,
     unsigned long long* __restrict__ stats) {
-    constexpr int KP = 32, CH = 64, FS = 36;          // FS: padded row stride of the staged F rows and of the G_w slab
-    constexpr int WAVE_FLOATS = CH * FS + 2 * CH + 2 * KP;  // staged rows | (w-1, w a) pairs | x | b_w
+    constexpr int KP = GramTile32::KP, CH = IRLS_QUAD_CH, FS = GramTile32::FS;   // FS: also the stride of the G_w slab
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float* Fst = reinterpret_cast<float*>(smem_raw) + (size_t)wave * WAVE_FLOATS;
+    float* Fst = reinterpret_cast<float*>(smem_raw) + (size_t)wave * IRLS_QUAD_WAVE_ELEMS;
     float2* sc = reinterpret_cast<float2*>(Fst + CH * FS);
     float* xs = Fst + CH * FS + 2 * CH;
     float* bws = xs + KP;
@@ -438,21 +415,8 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4
             const int as = colptr[j], ae = colptr[j + 1];
             const float th_col = theta_col ? theta_col[j] : 0.f;
             if (qme == q) { xs[l] = x0; xs[l + 16] = x1; }
-            // accumulator tile <- base Gram (identity padding), C/D map: col = lane&31, row = (v&3) + 8(v>>2) + 4(lane>>5)
-            // (four 16-byte loads off one per-lane pointer: k % 4 == 0 keeps a group of four rows on one side of k)
-            f32x16 acc;
-            const float* gb = Gbase + (int64_t)r * k + 4 * hh;
-            asm volatile("" : "+v"(gb));                 // per pass, not 16 hoisted addresses
-#pragma unroll
-            for (int v4 = 0; v4 < 4; ++v4) {
-                const int gi0 = 8 * v4 + 4 * hh;
-                const float4 g = (gi0 < k && r < k) ? *reinterpret_cast<const float4*>(gb + 8 * v4) : make_float4(0.f, 0.f, 0.f, 0.f);
-                const bool pad = r >= k;
-                acc[4 * v4 + 0] = pad && gi0 + 0 == r ? 1.f : g.x;
-                acc[4 * v4 + 1] = pad && gi0 + 1 == r ? 1.f : g.y;
-                acc[4 * v4 + 2] = pad && gi0 + 2 == r ? 1.f : g.z;
-                acc[4 * v4 + 3] = pad && gi0 + 3 == r ? 1.f : g.w;
-            }
+            GramTile32 tile(Fst, lane);
+            tile.init_vec4(Gbase, k);
             float bw = 0.f;
             __builtin_amdgcn_wave_barrier();
             const float4 xq = *reinterpret_cast<const float4*>(xs + 4 * p8);    // the lane's piece of x
@@ -492,26 +456,7 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4
                 const float w = irls_weight_full_dev<float>(LT >= 0 ? LT : loss_type, a_me - recon_me, recon_me, th, power, LT >= 0 ? 0.f : robust);
                 sc[lane] = make_float2(ok_me ? w - 1.f : 0.f, ok_me ? w * a_me : 0.f);
                 __builtin_amdgcn_wave_barrier();
-                // ---- phase B: nonzeros (2s, 2s+1) of the chunk per MFMA
-                const int cnt = ae - t0 < CH ? ae - t0 : CH;
-                const int nst = (cnt + 1) >> 1;
-                // (groups of four: the eight LDS reads of a group are issued ahead of its MFMAs; the nonzeros past cnt are staged as
-                //  zero rows with zero weights, so rounding the count up adds exact zeros)
-                for (int s2 = 0; s2 < nst; s2 += 4) {
-                    float fv[4];
-                    float2 ws[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int t = 2 * (s2 + u) + hh;
-                        fv[u] = Fst[t * FS + r];
-                        ws[u] = sc[t];
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        bw = tfma(ws[u].y, fv[u], bw);                                // b_w += f * (w a)
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ws[u].x * fv[u], fv[u], acc, 0, 0, 0);   // G_w += (f (w-1)) f^T
-                    }
-                }
+                tile.update_staged(ae - t0 < CH ? ae - t0 : CH, sc, bw);     // phase B
                 __builtin_amdgcn_wave_barrier();
             }
             bw += __shfl_xor(bw, 32, 64);
@@ -519,7 +464,7 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4
 #pragma unroll
             for (int v4 = 0; v4 < 4; ++v4) {
                 const int gi0 = 8 * v4 + 4 * hh;
-                float4 val = make_float4(acc[4 * v4], acc[4 * v4 + 1], acc[4 * v4 + 2], acc[4 * v4 + 3]);
+                float4 val = make_float4(tile.acc[4 * v4], tile.acc[4 * v4 + 1], tile.acc[4 * v4 + 2], tile.acc[4 * v4 + 3]);
                 if (l2 > 0.f && r < k) {
                     if (gi0 + 0 == r) val.x += l2;
                     if (gi0 + 1 == r) val.y += l2;
@@ -636,9 +581,9 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2
     int nonneg, int cd_maxit, int irls_max_iter, float irls_tol, const float* __restrict__ theta_row,
     const float* __restrict__ theta_col, int loss_type, float power, float robust,
     unsigned long long* __restrict__ stats) {
-    constexpr int KP = 64, CH = 32, FS = 68;          // FS: padded stride of a staged F row (64 features + bank spread)
-    constexpr int GW = KP * KP;                        // G_w slab; the staged rows (CH * FS = 2176 floats) alias its head
-    constexpr int WAVE_FLOATS = GW + 2 * CH + KP;      // G_w | (w-1, w a) pairs | x
+    constexpr int CH = GramTile32x2::CH, FS = GramTile32x2::FS;   // FS: padded stride of a staged F row (64 features + bank spread)
+    constexpr int GW = GramTile32x2::tile_elems;       // G_w slab; the staged rows (CH * FS = 2176 floats) alias its head
+    constexpr int WAVE_FLOATS = irls_wave_elems<GramTile32x2>;   // G_w | (w-1, w a) pairs | x
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float* Gl = reinterpret_cast<float*>(smem_raw) + (size_t)wave * WAVE_FLOATS;   // [c][r]
@@ -655,14 +600,8 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2
     int passes = 0, nsw = 0;      // IRLS passes; CD sweeps executed over all passes (work counters)
     for (int irls = 0; irls < irls_max_iter; ++irls) {
         ++passes;
-        // accumulator tiles <- base Gram (identity padding); C/D map of a tile: col = lane&31, row = (v&3) + 8(v>>2) + 4(lane>>5)
-        f32x16 a00, a01, a11;                           // rows 0-31 x cols 0-31 | rows 0-31 x cols 32-63 | rows 32-63 x cols 32-63
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int gi = (v & 3) + 8 * (v >> 2) + 4 * hh, gj = r;
-            auto base = [&](int i2, int j2) { return (i2 < k && j2 < k) ? Gbase[(int64_t)j2 * k + i2] : (i2 == j2 ? 1.f : 0.f); };
-            a00[v] = base(gi, gj); a01[v] = base(gi, gj + 32); a11[v] = base(gi + 32, gj + 32);
-        }
+        GramTile32x2 tile(Gl, lane);                    // accumulator tiles <- base Gram
+        tile.init(Gbase, k);
         xs[lane] = x;
         float bw0 = 0.f, bw1 = 0.f;                     // b_w of feature r and of feature 32 + r (this lane's K-slot share)
         __builtin_amdgcn_wave_barrier();
@@ -692,66 +631,24 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2
             for (int q = 0; q < 8; ++q) *reinterpret_cast<float4*>(Fst + r * FS + 32 * hh + 4 * q) = fv4[q];
             if (hh == 0) sc[r] = make_float2(ok ? w - 1.f : 0.f, ok ? w * a : 0.f);
             __builtin_amdgcn_wave_barrier();
-            // ---- phase B: nonzeros (2s, 2s+1) of the chunk per MFMA triple
-            const int cnt = ae - t0 < CH ? ae - t0 : CH;
-            const int nst = (cnt + 1) >> 1;
-#pragma unroll 2
-            for (int s2 = 0; s2 < nst; ++s2) {
-                const int t = 2 * s2 + hh;
-                const float f0 = Fst[t * FS + r], f1 = Fst[t * FS + 32 + r];
+            // ---- phase B
+            tile.update(ae - t0 < CH ? ae - t0 : CH, [&](int t, const float (&f)[2]) {
                 const float2 ws = sc[t];
-                bw0 = tfma(ws.y, f0, bw0);                                        // b_w += f * (w a)
-                bw1 = tfma(ws.y, f1, bw1);
-                const float s0 = ws.x * f0, s1 = ws.x * f1;
-                a00 = __builtin_amdgcn_mfma_f32_32x32x2f32(s0, f0, a00, 0, 0, 0);   // G_w += (f (w-1)) f^T, tile by tile
-                a01 = __builtin_amdgcn_mfma_f32_32x32x2f32(s0, f1, a01, 0, 0, 0);
-                a11 = __builtin_amdgcn_mfma_f32_32x32x2f32(s1, f1, a11, 0, 0, 0);
-            }
+                bw0 = tfma(ws.y, f[0], bw0);                                      // b_w += f * (w a)
+                bw1 = tfma(ws.y, f[1], bw1);
+                return ws.x;                                                      // G_w += (f (w-1)) f^T
+            });
             __builtin_amdgcn_wave_barrier();
         }
         bw0 += __shfl_xor(bw0, 32, 64);
         bw1 += __shfl_xor(bw1, 32, 64);
         const float bw = hh ? bw1 : bw0;                 // lane = feature from here on
-        // park G_w in LDS ([c][r]); the lower-left tile is the transpose of a01
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int gi = (v & 3) + 8 * (v >> 2) + 4 * hh;      // row inside the tile; column inside the tile = r
-            float d00 = a00[v], d11 = a11[v];
-            if (l2 > 0.f && gi == r) { if (gi < k) d00 += l2; if (gi + 32 < k) d11 += l2; }
-            Gl[gi * KP + r] = d00;                               // symmetric tile: stored as computed
-            Gl[(gi + 32) * KP + 32 + r] = d11;
-            Gl[(32 + r) * KP + gi] = a01[v];                     // G_w(row gi, col 32 + r) at [c = 32 + r][r' = gi]
-            Gl[gi * KP + 32 + r] = a01[v];                       // and its mirror G_w(row 32 + r, col gi) at [c = gi][r' = 32 + r]
-        }
+        tile.park(Gl, l2, k);
         __builtin_amdgcn_wave_barrier();
         // residual b_c = b_w - G_w x_old; the lane keeps its column of G_w in registers for the sweep
         const float x_old = x;
         float b = bw;
-        // (two 32-element vectors: hipcc indexes a 32-element vector with s_set_gpr_idx, a 64-element one through scratch)
-        typedef float f32x32 __attribute__((ext_vector_type(32)));
-        f32x32 gcol0, gcol1;
-#pragma unroll
-        for (int c = 0; c < 32; ++c) {
-            const float xc = __shfl(x_old, c, 64);
-            const float gv = Gl[c * KP + lane];
-            gcol0[c] = gv;
-            b = tfma(-gv, xc, b);
-        }
-#pragma unroll
-        for (int c = 0; c < 32; ++c) {
-            const float xc = __shfl(x_old, 32 + c, 64);
-            const float gv = Gl[(32 + c) * KP + lane];
-            gcol1[c] = gv;
-            b = tfma(-gv, xc, b);
-        }
-        const float gd = Gl[lane * KP + lane];
-        // cd_nnls_col_fixed(G_w, b_c, x, L1 inside, L2 = 0, nonneg, cd_maxit, ub = 0, tol = 0): all sweeps, static form (kernels.hip.h)
-        {
-            float gg[KP];
-#pragma unroll
-            for (int c = 0; c < 32; ++c) { gg[c] = gcol0[c]; gg[32 + c] = gcol1[c]; }
-            nsw += cd_static_sweeps_scaled_f32<KP>(b, x, gd, fok, l1, nonneg, cd_maxit, gg);
-        }
+        nsw += tile.solve_cd<true>(Gl, b, x, fok, l1, nonneg, cd_maxit);
         float rel = fok ? tabs(x - x_old) / (tabs(x_old) + 1e-12f) : 0.f;
         rel = wave_max(rel);
         __builtin_amdgcn_wave_barrier();
@@ -774,8 +671,8 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8
     int nonneg, int cd_maxit, int irls_max_iter, double irls_tol, const double* __restrict__ theta_row,
     const double* __restrict__ theta_col, int loss_type, double power, double robust,
     unsigned long long* __restrict__ stats) {
-    constexpr int KP = 32, CH = 32, FS = 34;          // FS: padded row stride (doubles) of the staged F rows
-    constexpr int WAVE_DOUBLES = CH * FS + 2 * CH + KP;
+    constexpr int KP = GramTile64::KP, CH = GramTile64::CH, FS = GramTile64::FS;   // FS: padded row stride (doubles) of the staged F rows
+    constexpr int WAVE_DOUBLES = irls_wave_elems<GramTile64>;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     double* Fst = reinterpret_cast<double*>(smem_raw) + (size_t)wave * WAVE_DOUBLES;
@@ -785,26 +682,16 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8
     const int64_t j = (int64_t)blockIdx.x * 4 + wave;
     if (j >= ncols) return;
     const int r = lane & 31, hh = lane >> 5;            // phase A: nonzero r, feature half hh
-    const int r16 = lane & 15, kk = lane >> 4;          // phase B: feature slot r16, K-slot kk
     const bool fok = lane < k;
     const bool lin = lane < KP;
-    const int ll = lin ? lane : 0;
     const int as = colptr[j], ae = colptr[j + 1];
     const double th_col = theta_col ? theta_col[j] : 0.0;
     double x = 0.0;
     int passes = 0, nsw = 0;      // IRLS passes; CD sweeps executed over all passes (work counters)
     for (int irls = 0; irls < irls_max_iter; ++irls) {
         ++passes;
-        f64x4 acc[2][2];
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int gi = 16 * ti + kk + 4 * v, gj = 16 * tj + r16;
-                    acc[ti][tj][v] = (gi < k && gj < k) ? Gbase[(int64_t)gj * k + gi] : (gi == gj ? 1.0 : 0.0);
-                }
+        GramTile64 tile(Fst, lane);
+        tile.init(Gbase, k);
         if (lin) xs[lane] = x;
         double bw[2] = {0.0, 0.0};
         for (int t0 = as; t0 < ae; t0 += CH) {
@@ -831,22 +718,13 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8
             for (int q = 0; q < 8; ++q) *reinterpret_cast<double2*>(Fst + r * FS + 16 * hh + 2 * q) = fv2[q];
             if (hh == 0) sc[r] = make_double2(ok ? w - 1.0 : 0.0, ok ? w * a : 0.0);
             __builtin_amdgcn_wave_barrier();
-            // ---- phase B: nonzeros 4s .. 4s+3 of the chunk per MFMA step
-            const int cnt = ae - t0 < CH ? ae - t0 : CH;
-            const int nst = (cnt + 3) >> 2;
-#pragma unroll 2
-            for (int s4 = 0; s4 < nst; ++s4) {
-                const int t = 4 * s4 + kk;
-                const double f0 = Fst[t * FS + r16], f1 = Fst[t * FS + 16 + r16];
+            // ---- phase B
+            tile.update(ae - t0 < CH ? ae - t0 : CH, [&](int t, const double (&f)[2]) {
                 const double2 ws = sc[t];
-                bw[0] = tfma(ws.y, f0, bw[0]);
-                bw[1] = tfma(ws.y, f1, bw[1]);
-                const double a0 = ws.x * f0, a1 = ws.x * f1;
-                acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, f0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, f1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, f0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, f1, acc[1][1], 0, 0, 0);
-            }
+                bw[0] = tfma(ws.y, f[0], bw[0]);
+                bw[1] = tfma(ws.y, f[1], bw[1]);
+                return ws.x;
+            });
             __builtin_amdgcn_wave_barrier();
         }
         // b_w[16 ti + r16]: sum over the four K-slot groups, then gather both halves into lane = feature order
@@ -856,28 +734,11 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8
             bw[ti] += __shfl_xor(bw[ti], 32, 64);
         }
         const double bwt = (lane & 16) ? bw[1] : bw[0];     // own registers: lane l < 32 has r16 = l & 15 and wants feature l
-        // park G_w in LDS ([c][r]; symmetric)
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int gi = 16 * ti + kk + 4 * v, gj = 16 * tj + r16;
-                    double val = acc[ti][tj][v];
-                    if (l2 > 0.0 && gi == gj && gi < k) val += l2;
-                    Gl[gi * KP + gj] = val;
-                }
+        tile.park(Gl, l2, k);
         __builtin_amdgcn_wave_barrier();
         const double x_old = x;
         double b = bwt;
-#pragma unroll 8
-        for (int c = 0; c < KP; ++c) {
-            const double xc = __shfl(x_old, c, 64);
-            b = tfma(-Gl[c * KP + ll], xc, b);
-        }
-        const double gd = Gl[ll * KP + ll];
-        nsw += cd_static_sweeps<double, KP>(b, x, gd, fok, l1, nonneg, cd_maxit, [&](auto IC) { return Gl[decltype(IC)::value * KP + ll]; });
+        nsw += tile.solve_cd<true>(Gl, b, x, fok, l1, nonneg, cd_maxit);
         double rel = fok ? tabs(x - x_old) / (tabs(x_old) + 1e-12) : 0.0;
         rel = wave_max(rel);
         __builtin_amdgcn_wave_barrier();

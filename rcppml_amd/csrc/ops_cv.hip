@@ -50,14 +50,14 @@ void cv_solve_impl(rcppml_hip_ctx* c, const int* cp, const int* ri, const T* val
     const bool use_mfma = cv_use_mfma();
     if constexpr (std::is_same<T, float>::value) if (!mp) {
         if (use_mfma && k <= 32 && k % 4 == 0 && reinterpret_cast<uintptr_t>(F) % 16 == 0) {
-            const size_t smem = (size_t)4 * CvTile32::wave_elems * sizeof(float);
+            const size_t smem = (size_t)4 * cv_wave_elems<GramTile32> * sizeof(float);
             hipLaunchKernelGGL(cv_solve_mfma32_kernel, dim3((unsigned)nblk), dim3(256), smem, c->stream, cp, ri, vals, ncols, nrows, F, G,
                                X, k, seed, thr, mask_zeros, transposed, l1, nonneg, maxit, solver_mode);
             HIPCHK(hipGetLastError());
             return;
         }
         if (use_mfma && k <= 64 && k % 4 == 0 && reinterpret_cast<uintptr_t>(F) % 16 == 0) {      // 32 < k <= 64: 2 x 2 tiles
-            const size_t smem = (size_t)4 * CvTile32x2::wave_elems * sizeof(float);
+            const size_t smem = (size_t)4 * cv_wave_elems<GramTile32x2> * sizeof(float);
             static DynSmemOnce once;
             once.ensure(reinterpret_cast<const void*>(&cv_solve_mfma32x2_kernel), smem, c->device);
             hipLaunchKernelGGL(cv_solve_mfma32x2_kernel, dim3((unsigned)nblk), dim3(256), smem, c->stream, cp, ri, vals, ncols, nrows, F, G,
@@ -68,7 +68,7 @@ void cv_solve_impl(rcppml_hip_ctx* c, const int* cp, const int* ri, const T* val
     }
     if constexpr (std::is_same<T, double>::value) if (!mp) {
         if (use_mfma && k <= 32 && k % 2 == 0 && reinterpret_cast<uintptr_t>(F) % 16 == 0) {
-            const size_t smem = (size_t)4 * CvTile64::wave_elems * sizeof(double);
+            const size_t smem = (size_t)4 * cv_wave_elems<GramTile64> * sizeof(double);
             hipLaunchKernelGGL(cv_solve_mfma64_kernel, dim3((unsigned)nblk), dim3(256), smem, c->stream, cp, ri, vals, ncols, nrows, F, G,
                                X, k, seed, thr, mask_zeros, transposed, l1, nonneg, maxit, solver_mode);
             HIPCHK(hipGetLastError());

@@ -7,6 +7,10 @@
 
 using namespace rk;
 
+// A kernel as a TYPE: launch_mfma below is a generic lambda, and only a parameter type of its own gives each kernel its own
+// instantiation of the call operator -- and with it its own `static DynSmemOnce` (kernels of equal signature share a pointer type).
+template <auto Kern> struct KernelTag { constexpr auto operator()() const { return Kern; } };
+
 template <class T>
 static void irls_impl(rcppml_hip_ctx* c, const int* cp, const int* ri, const T* vals, int64_t ncols, const T* F,
                       const T* Gbase, T* X, int k, T l1, T l2, int nonneg, int cd_maxit, int irls_max_iter, T irls_tol,
@@ -26,58 +30,40 @@ static void irls_impl(rcppml_hip_ctx* c, const int* cp, const int* ri, const T* 
         HIPCHK(hipGetLastError());
         return;
     }
+    // one launch of a matrix-core kernel (four waves per block): its LDS is sized from the element count that stands next to the
+    // kernel, the same constant the kernel lays its LDS out with
+    auto launch_mfma = [&](auto kern, int64_t blocks, int wave_elems) {
+        const size_t smem = (size_t)4 * wave_elems * sizeof(T);
+        if (smem > 48 * 1024) {                   // (the 2 x 2 kernel only; the others fit the default limit)
+            static DynSmemOnce once;              // one per kernel: `kern` is a type of its own
+            once.ensure(reinterpret_cast<const void*>(kern()), smem, c->device);
+        }
+        hipLaunchKernelGGL(kern(), dim3((unsigned)blocks), dim3(256), smem, c->stream, cp, ri, vals, ncols, F, Gbase, X, k, l1, l2, nonneg,
+                           cd_maxit, irls_max_iter, irls_tol, theta_row, theta_col, loss_type, power, robust, st);
+        HIPCHK(hipGetLastError());
+    };
+    static int use_mfma = -1;                     // RCPPML_GPU_IRLS_VARIANT=valu keeps the register form
+    if (use_mfma < 0) use_mfma = exp_flag("RCPPML_GPU_IRLS_VARIANT", "valu") ? 0 : 1;
     if constexpr (std::is_same<T, float>::value) {
-        // fp32, k <= 32: weighted Gram on the matrix cores (RCPPML_GPU_IRLS_VARIANT=valu keeps the register form)
-        static int use_mfma = -1;
-        if (use_mfma < 0) use_mfma = exp_flag("RCPPML_GPU_IRLS_VARIANT", "valu") ? 0 : 1;
+        // fp32, k <= 32: weighted Gram on the matrix cores
         if (use_mfma && k <= 32 && k % 4 == 0 && reinterpret_cast<uintptr_t>(F) % 16 == 0 && reinterpret_cast<uintptr_t>(Gbase) % 16 == 0) {   // (16-byte loads of F rows and of the base Gram; unaligned views take the register kernel)
             // many short columns: four columns per wavefront in the CD solve (irls_nb_mfma32q_kernel); RCPPML_OPT_IRLS_COLUMNS_PER_WAVE forces
             const bool quad = c->opt_irls_cpw > 0 ? c->opt_irls_cpw == 4 : ncols >= (int64_t)64 * c->num_cu;
-            if (quad) {
-                const size_t qsmem = (size_t)4 * (64 * 36 + 2 * 64 + 2 * 32) * sizeof(float);
-                const int64_t qblk = (ncols + 15) / 16;
-                if (loss_type == 5 && !(robust > 0)) {
-                    static DynSmemOnce once;
-                    once.ensure(reinterpret_cast<const void*>(&irls_nb_mfma32q_kernel<5>), qsmem, c->device);
-                    hipLaunchKernelGGL(irls_nb_mfma32q_kernel<5>, dim3((unsigned)qblk), dim3(256), qsmem, c->stream, cp, ri, vals, ncols, F,
-                                       Gbase, X, k, l1, l2, nonneg, cd_maxit, irls_max_iter, irls_tol, theta_row, theta_col, loss_type, power, robust, st);
-                } else {
-                    static DynSmemOnce once;
-                    once.ensure(reinterpret_cast<const void*>(&irls_nb_mfma32q_kernel<-1>), qsmem, c->device);
-                    hipLaunchKernelGGL(irls_nb_mfma32q_kernel<-1>, dim3((unsigned)qblk), dim3(256), qsmem, c->stream, cp, ri, vals, ncols, F,
-                                       Gbase, X, k, l1, l2, nonneg, cd_maxit, irls_max_iter, irls_tol, theta_row, theta_col, loss_type, power, robust, st);
-                }
-                HIPCHK(hipGetLastError());
-                return;
-            }
-            const size_t smem = (size_t)4 * (32 * 36 + 2 * 32 + 32) * sizeof(float);
-            if (loss_type == 5 && !(robust > 0))          // negative binomial without the robust modifier: specialised weights
-                hipLaunchKernelGGL(irls_nb_mfma32_kernel<5>, dim3((unsigned)nblk), dim3(256), smem, c->stream, cp, ri, vals, ncols, F,
-                                   Gbase, X, k, l1, l2, nonneg, cd_maxit, irls_max_iter, irls_tol, theta_row, theta_col, loss_type, power, robust, st);
-            else
-                hipLaunchKernelGGL(irls_nb_mfma32_kernel<-1>, dim3((unsigned)nblk), dim3(256), smem, c->stream, cp, ri, vals, ncols, F,
-                                   Gbase, X, k, l1, l2, nonneg, cd_maxit, irls_max_iter, irls_tol, theta_row, theta_col, loss_type, power, robust, st);
-            HIPCHK(hipGetLastError());
+            const bool nb = loss_type == 5 && !(robust > 0);      // negative binomial without the robust modifier: specialised weights
+            if (quad && nb) launch_mfma(KernelTag<&irls_nb_mfma32q_kernel<5>>{}, (ncols + 15) / 16, IRLS_QUAD_WAVE_ELEMS);
+            else if (quad) launch_mfma(KernelTag<&irls_nb_mfma32q_kernel<-1>>{}, (ncols + 15) / 16, IRLS_QUAD_WAVE_ELEMS);
+            else if (nb) launch_mfma(KernelTag<&irls_nb_mfma32_kernel<5>>{}, nblk, irls_wave_elems<GramTile32>);
+            else launch_mfma(KernelTag<&irls_nb_mfma32_kernel<-1>>{}, nblk, irls_wave_elems<GramTile32>);
             return;
         }
         if (use_mfma && k <= 64 && k % 4 == 0 && reinterpret_cast<uintptr_t>(F) % 16 == 0) {      // 32 < k <= 64: 2 x 2 tiles
-            const size_t smem = (size_t)4 * (64 * 64 + 2 * 32 + 64) * sizeof(float);
-            static DynSmemOnce once;
-            once.ensure(reinterpret_cast<const void*>(&irls_nb_mfma32x2_kernel), smem, c->device);
-            hipLaunchKernelGGL(irls_nb_mfma32x2_kernel, dim3((unsigned)nblk), dim3(256), smem, c->stream, cp, ri, vals, ncols, F,
-                               Gbase, X, k, l1, l2, nonneg, cd_maxit, irls_max_iter, irls_tol, theta_row, theta_col, loss_type, power, robust, st);
-            HIPCHK(hipGetLastError());
+            launch_mfma(KernelTag<&irls_nb_mfma32x2_kernel>{}, nblk, irls_wave_elems<GramTile32x2>);
             return;
         }
     }
     if constexpr (std::is_same<T, double>::value) {
-        static int use_mfma64 = -1;
-        if (use_mfma64 < 0) use_mfma64 = exp_flag("RCPPML_GPU_IRLS_VARIANT", "valu") ? 0 : 1;
-        if (use_mfma64 && k <= 32 && k % 2 == 0 && reinterpret_cast<uintptr_t>(F) % 16 == 0) {
-            const size_t smem = (size_t)4 * (32 * 34 + 2 * 32 + 32) * sizeof(double);
-            hipLaunchKernelGGL(irls_nb_mfma64_kernel, dim3((unsigned)nblk), dim3(256), smem, c->stream, cp, ri, vals, ncols, F,
-                               Gbase, X, k, l1, l2, nonneg, cd_maxit, irls_max_iter, irls_tol, theta_row, theta_col, loss_type, power, robust, st);
-            HIPCHK(hipGetLastError());
+        if (use_mfma && k <= 32 && k % 2 == 0 && reinterpret_cast<uintptr_t>(F) % 16 == 0) {
+            launch_mfma(KernelTag<&irls_nb_mfma64_kernel>{}, nblk, irls_wave_elems<GramTile64>);
             return;
         }
     }
