@@ -803,7 +803,14 @@ enum { RCPPML_OPT_CD_COUNT_NOOP = 1 /* LMF kernel counts all-zero coordinate ste
                                    map) when there are 2 to 5 32-column tiles, or between 1 and 2 16-column tiles, per SIMD; 1 = explicitly
                                    placed whenever those kernels run; 2 = never (one workgroup per four tiles); 3 / 4 = as 0 for the 32- /
                                    16-column tiles only (A/B runs).  Same results bit for bit */,
-       RCPPML_OPT_CD_ASSUME_CUS = 8 /* test switch: the explicitly placed launch assumes this many CUs (> 0) instead of the device's */ };
+       RCPPML_OPT_CD_ASSUME_CUS = 8 /* test switch: the explicitly placed launch assumes this many CUs (> 0) instead of the device's */,
+       RCPPML_OPT_CD_PRIO = 9 /* wave priorities (s_setprio) in the fp32 k <= 64 MFMA solves with the plain non-negative step: value = mode of
+                                 the 32-column tiles (the H side of a wide fit) + 8 x mode of the 16-column tiles (the W side).  Modes: 0 none;
+                                 1 / 2 static by round of the explicitly placed launch, younger / older rounds boosted (the tile-per-wave
+                                 launch ignores them); 3 / 4 dynamic, priority 1 during the scalar step / around the MFMAs of every
+                                 coordinate pair or quad.  Any other value is refused.  A context starts at RCPPML_CD_PRIO_DEFAULT; unlike
+                                 the other switches, 0 here means "no priorities", not "default".  Same results bit for bit */ };
+#define RCPPML_CD_PRIO_DEFAULT 3 /* H side: priority 1 during the scalar step (mode 3); W side: none.  profiles/cd_prio_ab.txt */
 RCPPML_GPU_API int rcppml_hip_ctx_set_option(rcppml_hip_ctx* ctx, int option, int value);
 
 /* One-time setup of a fit, on the device.

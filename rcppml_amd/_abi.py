@@ -17,6 +17,20 @@ CD_AUTO, CD_LANE, CD_WAVE, CD_GROUP, CD_MFMA, CD_MFMA16, CD_LMF = 0, 1, 2, 5, 6,
 # rcppml_hip_ctx_set_option
 OPT_CD_COUNT_NOOP, OPT_CD_LMF_LANE_GROUPS, OPT_CD_LMF_WAVES_PER_SIMD, OPT_CD_NO_LMF, OPT_IRLS_COLUMNS_PER_WAVE, OPT_SMALL_GIVE_UP = 1, 2, 3, 4, 5, 6
 OPT_CD_PLACED, OPT_CD_ASSUME_CUS = 7, 8          # launch form of the 32-column MFMA solve (0 auto, 1 always placed, 2 never); test switch
+OPT_CD_PRIO = 9                                  # wave priority modes of the fp32 MFMA solves: 32-column mode + 8 x 16-column mode
+CD_PRIO_MODES = (0, 1, 2, 3, 4)                  # none; static younger / older round boosted; dynamic scalar step / MFMAs boosted
+CD_PRIO_DEFAULT = 3                              # RCPPML_CD_PRIO_DEFAULT: what a new context runs
+
+
+def cd_prio_value(h_mode, w_mode):
+    """The RCPPML_OPT_CD_PRIO value of a pair of modes; anything but CD_PRIO_MODES is refused (as the library refuses it)."""
+    if h_mode not in CD_PRIO_MODES or w_mode not in CD_PRIO_MODES:
+        raise ValueError("CD priority modes are 0..4, got %r / %r" % (h_mode, w_mode))
+    return h_mode + 8 * w_mode
+
+
+def cd_prio_valid(value):
+    return isinstance(value, int) and value >= 0 and (value & 7) in CD_PRIO_MODES and (value >> 3) in CD_PRIO_MODES
 
 # Every symbol include/rcppml_gpu.h declares (tests check the library exports all of them).
 EXPORTED_SYMBOLS = [
@@ -437,6 +451,8 @@ class Context:
         _chk(lib().rcppml_hip_ctx_sync(self._h), "ctx_sync")
 
     def set_option(self, option, value):
+        if option == OPT_CD_PRIO and not cd_prio_valid(value):
+            raise BackendError("ctx_set_option: RCPPML_OPT_CD_PRIO value %r is out of range" % (value,))
         _chk(lib().rcppml_hip_ctx_set_option(self._h, C.c_int(option), C.c_int(value)), "ctx_set_option")
 
     def stats(self, reset=False):

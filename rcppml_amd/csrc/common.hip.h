@@ -48,6 +48,9 @@ inline bool exp_flag(const char*, const char*) { return false; }
 inline const char* exp_env(const char*) { return nullptr; }
 #endif
 
+// RCPPML_OPT_CD_PRIO: wave priority mode of the 32-column solve (0..4) + 8 x that of the 16-column solve (0..4)
+inline bool rcppml_cd_prio_valid(int v) { return v >= 0 && (v & 7) <= 4 && (v >> 3) <= 4; }
+
 struct rcppml_hip_ctx;
 enum { WS_GRAM = 0, WS_GPAD, WS_CHOL, WS_RED, WS_RED2, WS_ORDER, WS_IRLS, WS_MFMA, WS_FEAT, WS_GRAPH, WS_COUNT };
 
@@ -89,7 +92,7 @@ struct rcppml_hip_ctx {
     unsigned long long* stats = nullptr;
     // rcppml_hip_ctx_set_option
     int opt_cd_count = 0, opt_lmf_lg = 0, opt_lmf_wps = 0, opt_cd_no_lmf = 0, opt_irls_cpw = 0, opt_small_give_up = 0;
-    int opt_cd_placed = 0, opt_cd_assume_cus = 0;
+    int opt_cd_placed = 0, opt_cd_assume_cus = 0, opt_cd_prio = RCPPML_CD_PRIO_DEFAULT;
     // Per-fit arena (plugin entries): ONE hipMalloc / hipFree for everything a fit allocates instead of ~60 pairs -- hipMalloc
     // costs tens of microseconds and every hipFree synchronises the device; together they were 5-6 ms of a 20 ms one-iteration
     // call.  Pure bump allocation, nothing is handed back before the fit ends.  arena_take() returns nullptr when there is no

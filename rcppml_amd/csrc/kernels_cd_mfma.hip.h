@@ -131,10 +131,33 @@ __device__ __forceinline__ void cd_mfma_fill_lds(const float* __restrict__ G /* 
     }
 }
 
+// Wave priority modes of the fp32 tile bodies (PRIO; RCPPML_OPT_CD_PRIO picks one per side).  s_setprio only changes which
+// READY wave of a SIMD issues next: every column's arithmetic and sweep count stay bit for bit what mode 0 computes.
+//   0  none
+//   1  static, by round of the placed launch, younger boosted: wave w = round r = w >> 2 runs at priority min(r, 3)
+//   2  static, older boosted: priority min(rounds - 1 - r, 3)
+//   3  dynamic, chain high: priority 1 from the top of a pair's (quad's) scalar step until just before its MFMAs
+//   4  dynamic, MFMA high: priority 1 around the pair's (quad's) MFMAs
+// The static modes are set once by the placed kernels, before their tile loop (cd_static_prio); the tile body knows the dynamic
+// ones.  The tile-per-wave kernels have no rounds and take the dynamic modes only.
+enum { CD_PRIO_NONE = 0, CD_PRIO_YOUNG = 1, CD_PRIO_OLD = 2, CD_PRIO_CHAIN = 3, CD_PRIO_MFMA = 4 };
+
+// s_setprio takes an immediate and ignores EXEC: `r` and `rounds` must be wave-uniform SCALARS (a readfirstlane and a kernel
+// argument), so that the compares below become s_cmp / s_cbranch around one s_setprio each, never an EXEC mask
+template <int PRIO>
+__device__ __forceinline__ void cd_static_prio(int r, int rounds) {
+    if constexpr (PRIO == CD_PRIO_YOUNG || PRIO == CD_PRIO_OLD) {
+        const int pr = PRIO == CD_PRIO_YOUNG ? r : rounds - 1 - r;
+        if (pr == 1) __builtin_amdgcn_s_setprio(1);
+        else if (pr == 2) __builtin_amdgcn_s_setprio(2);
+        else if (pr >= 3) __builtin_amdgcn_s_setprio(3);
+    }
+}
+
 // One tile: the 32*CT work-order slots from `base` on, solved by the calling wave against the operand image in LDS -- load B
 // and X, warm pass, sweeps, store, sweep counts, work counters.  Both launch forms below run their tiles through this body; a
 // column's arithmetic depends neither on its tile-mates nor on which wave runs the tile.
-template <int RT, int CT, bool SIMPLE>   // KP = 32*RT rows (k <= KP), 32*CT columns per wave
+template <int RT, int CT, bool SIMPLE, int PRIO = CD_PRIO_NONE>   // KP = 32*RT rows (k <= KP), 32*CT columns per wave
 __device__ __forceinline__ void cd_mfma_tile(const int64_t base, const float* __restrict__ B, float* __restrict__ X, int k, int64_t ncols,
                                              float l1_pre, int warm, int zero_init, float l1_cd, float l2_cd, int nonneg, int maxit,
                                              float tol, float ub_cd, float ub_post, int* __restrict__ sweeps,
@@ -240,6 +263,7 @@ __device__ __forceinline__ void cd_mfma_tile(const int64_t base, const float* __
                 const PairOps nxt = load_pair(inext >> 1);
                 const float g_oe = cur.coup;
                 float aval[CT];
+                if constexpr (PRIO == CD_PRIO_CHAIN) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) {
                     const float b = acc[rt][ct][q];
@@ -279,6 +303,8 @@ __device__ __forceinline__ void cd_mfma_tile(const int64_t base, const float* __
                         tsum[ct] = __builtin_fmaf(tabs(o.a), __builtin_amdgcn_rcpf(tabs(o.nx) + 1e-15f), tsum[ct]);
                     }
                 }
+                if constexpr (PRIO == CD_PRIO_CHAIN) __builtin_amdgcn_s_setprio(0);
+                if constexpr (PRIO == CD_PRIO_MFMA) __builtin_amdgcn_s_setprio(1);
                 // the row tile that holds the NEXT pair's residuals goes first, so its results are back first
 #pragma unroll
                 for (int s2 = 0; s2 < RT; ++s2) {
@@ -287,6 +313,7 @@ __device__ __forceinline__ void cd_mfma_tile(const int64_t base, const float* __
                     for (int ct = 0; ct < CT; ++ct)
                         acc[rt2][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.av[rt2], aval[ct], acc[rt2][ct], 0, 0, 0);
                 }
+                if constexpr (PRIO == CD_PRIO_MFMA) __builtin_amdgcn_s_setprio(0);
                 cur = nxt;
                 // one scheduling region per coordinate pair: without it hipcc hoists the LDS reads of many pairs and
                 // spends > 380 registers on this fully unrolled sweep
@@ -340,7 +367,7 @@ __device__ __forceinline__ void cd_mfma_tile(const int64_t base, const float* __
 }
 
 // Launch form 1: one tile per wave, 4 waves per workgroup share the operand image; the dispatcher decides where tiles run.
-template <int RT, int CT, bool SIMPLE>
+template <int RT, int CT, bool SIMPLE, int PRIO = CD_PRIO_NONE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CT == 1 && RT <= 2) ? 4 : 2, 8))) void cd_mfma_kernel(const float* __restrict__ G /* k x k, as rcppml_hip_gram wrote it */,
                                                        const float* __restrict__ B,
                                                        float* __restrict__ X, int k, int64_t ncols, float l1_pre,
@@ -352,7 +379,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CT == 1 &&
     __syncthreads();
     const int wave = threadIdx.x >> 6;
     const int64_t base = ((int64_t)blockIdx.x * (blockDim.x >> 6) + wave) * (32 * CT);
-    cd_mfma_tile<RT, CT, SIMPLE>(base, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps,
+    cd_mfma_tile<RT, CT, SIMPLE, PRIO>(base, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps,
                                  order, stats);
 }
 
@@ -365,7 +392,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CT == 1 &&
 // computes the same numbers.)  With `unserp` the work order is the serpentine layout of rcppml_hip_order_columns and the
 // map's longest-first positions are translated.  Register budget as form 1 (<= 128 VGPRs: four waves per SIMD), whatever R
 // the launch picks.
-template <int RT, bool SIMPLE>
+template <int RT, bool SIMPLE, int PRIO = CD_PRIO_NONE>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 8))) void cd_mfma_placed_kernel(
     const float* __restrict__ G, const float* __restrict__ B, float* __restrict__ X, int k, int64_t ncols, float l1_pre, int warm,
     int zero_init, float l1_cd, float l2_cd, int nonneg, int maxit, float tol, float ub_cd, float ub_post, int* __restrict__ sweeps,
@@ -378,9 +405,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 8))) vo
     const int64_t mapped = (int64_t)pl.rounds * pl.simds;
     int64_t p = cd_place_pos(pl, g, r);
     int64_t e = r == pl.rounds - 1 ? cd_place_extra(pl, g) : ntiles;      // left-over tiles: the last-round wave only
+    cd_static_prio<PRIO>(r, pl.rounds);
     while (p < ntiles) {
         const int64_t t = unserp ? cd_place_unserp(p, 4, ncols) : p;
-        cd_mfma_tile<RT, 1, SIMPLE>(t * 32, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post,
+        cd_mfma_tile<RT, 1, SIMPLE, PRIO>(t * 32, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post,
                                     sweeps, order, stats);
         p = mapped + e;
         e += pl.simds;

@@ -140,7 +140,8 @@ __device__ __forceinline__ void cd_mfma64_fill_lds(const T* __restrict__ G /* k 
 
 // One tile: the 16 work-order slots from `base` on, solved by the calling wave against the operand image in LDS -- load B and
 // X, warm pass, sweeps, store, sweep counts, work counters.  Both launch forms below run their tiles through this body.
-template <class T, int NT, bool SIMPLE>   // KP = 16*NT rows (k <= KP), 16 columns per wave
+// PRIO: the wave priority modes of kernels_cd_mfma.hip.h (fp32 only; the dynamic ones act here, per quad).
+template <class T, int NT, bool SIMPLE, int PRIO = CD_PRIO_NONE>   // KP = 16*NT rows (k <= KP), 16 columns per wave
 __device__ __forceinline__ void cd_mfma64_tile(const int64_t base, const T* __restrict__ B, T* __restrict__ X, int k, int64_t ncols, T l1_pre,
                                                int warm, int zero_init, T l1_cd, T l2_cd, int nonneg, int maxit, T tol, T ub_cd, T ub_post,
                                                int* __restrict__ sweeps, const int* __restrict__ order,
@@ -221,6 +222,7 @@ __device__ __forceinline__ void cd_mfma64_tile(const int64_t base, const T* __re
                 const T b0 = acc[t][v];
                 const T xo = xr[t][v];
                 const T ginv = SIMPLE ? (active ? tb_c.x : T(0)) : tb_c.x;
+                if constexpr (PRIO == CD_PRIO_CHAIN) __builtin_amdgcn_s_setprio(1);
                 // phase p: group p's step is final; the groups behind it take the lazy correction, the others keep b
                 const CdStepOut64<T> s0 = cd_step64<SIMPLE, T>(b0, xo, gd_c, ginv, active, l1_cd, l2_cd, lo, hi);
                 const T b1 = tfma(-tb_c.y, bcast_row<0>(s0.a), b0);
@@ -232,12 +234,15 @@ __device__ __forceinline__ void cd_mfma64_tile(const int64_t base, const T* __re
                 xr[t][v] = s3.nx;
                 // |a| / (|x_new| + 1e-15)  (nnls_batch.hpp:117-120): v_rcp_f64 + one Newton step
                 tsum = tfma(tabs(s3.a), fast_recip(tabs(s3.nx) + T(1e-15)), tsum);
+                if constexpr (PRIO == CD_PRIO_CHAIN) __builtin_amdgcn_s_setprio(0);
+                if constexpr (PRIO == CD_PRIO_MFMA) __builtin_amdgcn_s_setprio(1);
                 // the row tile that holds the NEXT quad's residuals goes first
 #pragma unroll
                 for (int s = 0; s < NT; ++s) {
                     const int t2 = (tn + s) % NT;
                     acc[t2] = mfma16(av_c[t2], s3.a, acc[t2]);
                 }
+                if constexpr (PRIO == CD_PRIO_MFMA) __builtin_amdgcn_s_setprio(0);
                 tb_c = tb_n;
                 gd_c = gd_n;
 #pragma unroll
@@ -268,7 +273,7 @@ __device__ __forceinline__ void cd_mfma64_tile(const int64_t base, const T* __re
 }
 
 // Launch form 1: one tile per wave, 4 waves per workgroup share the operand image; the dispatcher decides where tiles run.
-template <class T, int NT, bool SIMPLE>
+template <class T, int NT, bool SIMPLE, int PRIO = CD_PRIO_NONE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= 2 ? 4 : (NT <= 4 ? 2 : 1), 8)))
 void cd_mfma64_kernel(const T* __restrict__ G /* k x k, as rcppml_hip_gram wrote it */, const T* __restrict__ B,
                       T* __restrict__ X, int k, int64_t ncols, T l1_pre, int warm, int zero_init, T l1_cd,
@@ -278,7 +283,7 @@ void cd_mfma64_kernel(const T* __restrict__ G /* k x k, as rcppml_hip_gram wrote
     __syncthreads();
     const int wave = threadIdx.x >> 6;
     const int64_t base = ((int64_t)blockIdx.x * (blockDim.x >> 6) + wave) * 16;
-    cd_mfma64_tile<T, NT, SIMPLE>(base, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order,
+    cd_mfma64_tile<T, NT, SIMPLE, PRIO>(base, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order,
                                   stats);
 }
 
@@ -287,7 +292,7 @@ void cd_mfma64_kernel(const T* __restrict__ G /* k x k, as rcppml_hip_gram wrote
 // round dealt in descending SIMD order, the first `SIMDs` tiles of the longest-first order get a SIMD each and the surplus
 // (shortest) tiles become second waves on the SIMDs that hold the shortest first-round tiles, never beside the longest: this
 // kernel lasts as long as its longest lone chain, and a second wave on that chain's SIMD takes issue slots from it.
-template <int NT, bool SIMPLE>
+template <int NT, bool SIMPLE, int PRIO = CD_PRIO_NONE>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NT <= 2 ? 4 : 2, 8)))
 void cd_mfma64_placed_kernel(const float* __restrict__ G, const float* __restrict__ B, float* __restrict__ X, int k, int64_t ncols,
                              float l1_pre, int warm, int zero_init, float l1_cd, float l2_cd, int nonneg, int maxit, float tol, float ub_cd,
@@ -301,9 +306,10 @@ void cd_mfma64_placed_kernel(const float* __restrict__ G, const float* __restric
     const int64_t mapped = (int64_t)pl.rounds * pl.simds;
     int64_t p = cd_place_pos(pl, gs, r);
     int64_t e = r == pl.rounds - 1 ? cd_place_extra(pl, gs) : ntiles;      // left-over tiles: the last-round wave only
+    cd_static_prio<PRIO>(r, pl.rounds);
     while (p < ntiles) {
         const int64_t t = unserp ? cd_place_unserp(p, 8, ncols) : p;
-        cd_mfma64_tile<float, NT, SIMPLE>(t * 16, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post,
+        cd_mfma64_tile<float, NT, SIMPLE, PRIO>(t * 16, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post,
                                           sweeps, order, stats);
         p = mapped + e;
         e += pl.simds;

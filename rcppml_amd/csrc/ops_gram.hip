@@ -49,6 +49,10 @@ extern "C" int rcppml_hip_ctx_set_option(rcppml_hip_ctx* c, int option, int valu
         case RCPPML_OPT_SMALL_GIVE_UP: c->opt_small_give_up = value; return 0;
         case RCPPML_OPT_CD_PLACED: c->opt_cd_placed = value; return 0;
         case RCPPML_OPT_CD_ASSUME_CUS: c->opt_cd_assume_cus = value; return 0;
+        case RCPPML_OPT_CD_PRIO:
+            if (!rcppml_cd_prio_valid(value)) { rcppml_err() = "RCPPML_OPT_CD_PRIO: each side's mode is 0..4 (value = H mode + 8 x W mode)"; return 1; }
+            c->opt_cd_prio = value;
+            return 0;
         default: rcppml_err() = "unknown option"; return 1;
     }
 }

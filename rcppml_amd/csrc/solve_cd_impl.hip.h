@@ -57,6 +57,28 @@ static void cd_group_launch(rcppml_hip_ctx* c, const T* Gp, const T* invd, const
     HIPCHK(hipGetLastError());
 }
 
+// One launch of kernel instantiation KERN, with its per-device dynamic-LDS attribute (one DynSmemOnce per instantiation).
+template <auto KERN, class... A>
+static void cd_launch(rcppml_hip_ctx* c, dim3 grid, dim3 block, size_t smem, A... a) {
+    static DynSmemOnce once;
+    once.ensure(reinterpret_cast<const void*>(KERN), smem, c->device);
+    hipLaunchKernelGGL(KERN, grid, block, smem, c->stream, a...);
+}
+
+// Wave priority mode of one side (kernels_cd_mfma.hip.h: CD_PRIO_*): RCPPML_OPT_CD_PRIO holds the 32-column form's mode + 8 x the
+// 16-column form's (the H and the W side of the headline fit); RCPPML_GPU_CD_PRIO overrides in experiment builds.  The priority
+// kernels exist for the plain non-negative step only: the general step keeps mode 0.  `placed` = the launch form has rounds;
+// the tile-per-wave forms take the dynamic modes only.
+static int cd_prio_mode(const rcppml_hip_ctx* c, bool wide16, bool simple, bool placed) {
+    int v = c->opt_cd_prio;
+    if (const char* e = exp_env("RCPPML_GPU_CD_PRIO")) v = atoi(e);
+    if (!rcppml_cd_prio_valid(v)) throw std::runtime_error("solve_cd: RCPPML_GPU_CD_PRIO out of range");
+    const int m = wide16 ? (v >> 3) : (v & 7);
+    if (!simple) return rk::CD_PRIO_NONE;
+    if (!placed && (m == rk::CD_PRIO_YOUNG || m == rk::CD_PRIO_OLD)) return rk::CD_PRIO_NONE;
+    return m;
+}
+
 // MFMA variant, explicitly placed launch (fp32, k <= 64, 32-column tiles): one workgroup of 4 R waves per CU, the tiles dealt to
 // SIMDs by the static map of cd_placement.hip.h.  R = tiles per SIMD (rounded down, 1..4); the workgroup asks for more than half
 // of a CU's LDS so that no two share a CU.  `order` is taken to be the layout rcppml_hip_order_columns writes.
@@ -75,16 +97,21 @@ static void cd_mfma_placed_launch(rcppml_hip_ctx* c, int cus, const float* G, co
     const size_t alone = (size_t)160 * 1024 / 2 + 1024;
     if (smem < alone) smem = alone;
     const bool simple = nonneg && ub_cd <= 0.f && l1_cd == 0.f && l2_cd == 0.f;
-    static DynSmemOnce once_simple, once_general;
-    if (simple) once_simple.ensure(reinterpret_cast<const void*>(&cd_mfma_placed_kernel<RT, true>), smem, c->device);
-    else once_general.ensure(reinterpret_cast<const void*>(&cd_mfma_placed_kernel<RT, false>), smem, c->device);
     const dim3 grid((unsigned)cus), block(256u * (unsigned)pl.rounds);
-    if (simple)
-        hipLaunchKernelGGL((cd_mfma_placed_kernel<RT, true>), grid, block, smem, c->stream, G, B, X, k, ncols, l1_pre, warm, zero_init,
-                           l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats, pl, order ? 1 : 0);
-    else
-        hipLaunchKernelGGL((cd_mfma_placed_kernel<RT, false>), grid, block, smem, c->stream, G, B, X, k, ncols, l1_pre, warm, zero_init,
-                           l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats, pl, order ? 1 : 0);
+#define CD_PLACED_GO(SIMPLE_, PRIO_)                                                                                                  \
+    cd_launch<&cd_mfma_placed_kernel<RT, SIMPLE_, PRIO_>>(c, grid, block, smem, G, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, \
+                                                          nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats, pl, order ? 1 : 0)
+    switch (cd_prio_mode(c, false, simple, true)) {
+        case CD_PRIO_YOUNG: CD_PLACED_GO(true, CD_PRIO_YOUNG); break;
+        case CD_PRIO_OLD: CD_PLACED_GO(true, CD_PRIO_OLD); break;
+        case CD_PRIO_CHAIN: CD_PLACED_GO(true, CD_PRIO_CHAIN); break;
+        case CD_PRIO_MFMA: CD_PLACED_GO(true, CD_PRIO_MFMA); break;
+        default:
+            if (simple) CD_PLACED_GO(true, CD_PRIO_NONE);
+            else CD_PLACED_GO(false, CD_PRIO_NONE);
+            break;
+    }
+#undef CD_PLACED_GO
     HIPCHK(hipGetLastError());
 }
 
@@ -126,15 +153,22 @@ static void cd_mfma_launch(rcppml_hip_ctx* c, const float* G, const float* /*unu
             if (want > smem && want <= lds_cu / (size_t)cap) smem = want;
         }
     }
-    static DynSmemOnce once_simple, once_general;
-    if (simple) once_simple.ensure(reinterpret_cast<const void*>(&cd_mfma_kernel<RT, CT, true>), smem, c->device);
-    else once_general.ensure(reinterpret_cast<const void*>(&cd_mfma_kernel<RT, CT, false>), smem, c->device);
-    if (simple)
-        hipLaunchKernelGGL((cd_mfma_kernel<RT, CT, true>), dim3((unsigned)nblk), dim3(256), smem, c->stream, G, B, X,
-                           k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats);
-    else
-        hipLaunchKernelGGL((cd_mfma_kernel<RT, CT, false>), dim3((unsigned)nblk), dim3(256), smem, c->stream, G, B, X,
-                           k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats);
+    const dim3 grid((unsigned)nblk), block(256);
+#define CD_TILE_GO(SIMPLE_, PRIO_)                                                                                                     \
+    cd_launch<&cd_mfma_kernel<RT, CT, SIMPLE_, PRIO_>>(c, grid, block, smem, G, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, \
+                                                       nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats)
+    // the k <= 64 tile body has the dynamic priority modes (the placed form's static ones need rounds)
+    int prio = CD_PRIO_NONE;
+    if constexpr (RT <= 2 && CT == 1) prio = cd_prio_mode(c, false, simple, false);
+    if constexpr (RT <= 2 && CT == 1) {
+        if (prio == CD_PRIO_CHAIN) CD_TILE_GO(true, CD_PRIO_CHAIN);
+        else if (prio == CD_PRIO_MFMA) CD_TILE_GO(true, CD_PRIO_MFMA);
+    }
+    if (prio == CD_PRIO_NONE) {
+        if (simple) CD_TILE_GO(true, CD_PRIO_NONE);
+        else CD_TILE_GO(false, CD_PRIO_NONE);
+    }
+#undef CD_TILE_GO
     HIPCHK(hipGetLastError());
 }
 
@@ -166,31 +200,44 @@ static void cd_mfma64_launch(rcppml_hip_ctx* c, const T* G, const T* /*unused*/,
             size_t smem = ((size_t)KP * KP + 4 * KP) * sizeof(float);
             const size_t alone = (size_t)160 * 1024 / 2 + 1024;      // more than half of a CU's LDS: no two workgroups share a CU
             if (smem < alone) smem = alone;
-            static DynSmemOnce once_simple, once_general;
-            if (simple) once_simple.ensure(reinterpret_cast<const void*>(&cd_mfma64_placed_kernel<NT, true>), smem, c->device);
-            else once_general.ensure(reinterpret_cast<const void*>(&cd_mfma64_placed_kernel<NT, false>), smem, c->device);
             const dim3 grid((unsigned)cus), block(256u * (unsigned)pl.rounds);
-            if (simple)
-                hipLaunchKernelGGL((cd_mfma64_placed_kernel<NT, true>), grid, block, smem, c->stream, G, B, X, k, ncols, l1_pre, warm, zero_init,
-                                   l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats, pl, order ? 1 : 0);
-            else
-                hipLaunchKernelGGL((cd_mfma64_placed_kernel<NT, false>), grid, block, smem, c->stream, G, B, X, k, ncols, l1_pre, warm, zero_init,
-                                   l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats, pl, order ? 1 : 0);
+#define CD_PLACED_GO(SIMPLE_, PRIO_)                                                                                                     \
+    cd_launch<&cd_mfma64_placed_kernel<NT, SIMPLE_, PRIO_>>(c, grid, block, smem, G, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, \
+                                                            nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats, pl, order ? 1 : 0)
+            switch (cd_prio_mode(c, true, simple, true)) {
+                case CD_PRIO_YOUNG: CD_PLACED_GO(true, CD_PRIO_YOUNG); break;
+                case CD_PRIO_OLD: CD_PLACED_GO(true, CD_PRIO_OLD); break;
+                case CD_PRIO_CHAIN: CD_PLACED_GO(true, CD_PRIO_CHAIN); break;
+                case CD_PRIO_MFMA: CD_PLACED_GO(true, CD_PRIO_MFMA); break;
+                default:
+                    if (simple) CD_PLACED_GO(true, CD_PRIO_NONE);
+                    else CD_PLACED_GO(false, CD_PRIO_NONE);
+                    break;
+            }
+#undef CD_PLACED_GO
             HIPCHK(hipGetLastError());
             return;
         }
     }
+    // fp64 above k = 64: the LDS copy of G passes 64 KiB (128 KiB at KP = 128)
     const size_t smem = ((size_t)KP * KP + 4 * KP + (sizeof(T) == 8 ? KP : 0)) * sizeof(T);      // fp64: + the diagonal itself
     const int64_t nblk = (ncols + 63) / 64;          // 4 waves x 16 columns per block
-    static DynSmemOnce once_simple, once_general;    // fp64 above k = 64: the LDS copy of G passes 64 KiB (128 KiB at KP = 128)
-    if (simple) once_simple.ensure(reinterpret_cast<const void*>(&cd_mfma64_kernel<T, NT, true>), smem, c->device);
-    else once_general.ensure(reinterpret_cast<const void*>(&cd_mfma64_kernel<T, NT, false>), smem, c->device);
-    if (simple)
-        hipLaunchKernelGGL((cd_mfma64_kernel<T, NT, true>), dim3((unsigned)nblk), dim3(256), smem, c->stream, G, B, X, k,
-                           ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats);
-    else
-        hipLaunchKernelGGL((cd_mfma64_kernel<T, NT, false>), dim3((unsigned)nblk), dim3(256), smem, c->stream, G, B, X, k,
-                           ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats);
+    const dim3 grid((unsigned)nblk), block(256);
+#define CD_TILE_GO(SIMPLE_, PRIO_)                                                                                                      \
+    cd_launch<&cd_mfma64_kernel<T, NT, SIMPLE_, PRIO_>>(c, grid, block, smem, G, B, X, k, ncols, l1_pre, warm, zero_init, l1_cd, l2_cd, \
+                                                        nonneg, maxit, tol, ub_cd, ub_post, sweeps, order, c->stats)
+    // the fp32 k <= 64 tile body has the dynamic priority modes (the placed form's static ones need rounds)
+    int prio = CD_PRIO_NONE;
+    if constexpr (std::is_same<T, float>::value && NT <= 4) {
+        prio = cd_prio_mode(c, true, simple, false);
+        if (prio == CD_PRIO_CHAIN) CD_TILE_GO(true, CD_PRIO_CHAIN);
+        else if (prio == CD_PRIO_MFMA) CD_TILE_GO(true, CD_PRIO_MFMA);
+    }
+    if (prio == CD_PRIO_NONE) {
+        if (simple) CD_TILE_GO(true, CD_PRIO_NONE);
+        else CD_TILE_GO(false, CD_PRIO_NONE);
+    }
+#undef CD_TILE_GO
     HIPCHK(hipGetLastError());
 }
 
