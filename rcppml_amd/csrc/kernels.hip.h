@@ -1777,7 +1777,11 @@ __global__ __launch_bounds__(256) void masked_solve_kernel(
 
 // Per-element loss term of the distribution losses (math/loss.hpp:512-536 compute_loss): GP (4) :382-398, NB (5) :415-426,
 // Gamma (6) / inverse Gaussian (7) / Tweedie (8) deviance terms :439-505.  y, mu (>= 1e-10 already) and theta in double; the
-// caller casts the term to Scalar as the reference does.
+// caller casts the term to Scalar as the reference does.  These two functions are the only statement of the terms.
+// The NB term takes lgamma(r) of its size r (>= 1e-10 already) from the caller: a row kernel evaluates it once per row.
+__device__ __forceinline__ double nb_loss_term(double y, double mu, double r, double lgamma_r) {
+    return -lgamma(y + r) + lgamma_r - r * log(r / (r + mu)) - y * log(mu / (r + mu));
+}
 __device__ __forceinline__ double dist_loss_term(int loss_type, double y, double mu, double th, double power) {
     if (loss_type == 4) {
         const double opt = 1.0 + th;
@@ -1802,7 +1806,7 @@ __device__ __forceinline__ double dist_loss_term(int loss_type, double y, double
         return 2.0 * (pow(yy, tmp) / (omp * tmp) - yy * pow(mu, omp) / omp + pow(mu, tmp) / tmp);
     }
     const double r = th > 1e-10 ? th : 1e-10;
-    return -lgamma(y + r) + lgamma(r) - r * log(r / (r + mu)) - y * log(mu / (r + mu));
+    return nb_loss_term(y, mu, r, lgamma(r));
 }
 
 // The per-nonzero gather p = sum_f d_f W_T(f,row) H(f,j) of one wavefront (lanes stride the factors, butterfly sum: every lane

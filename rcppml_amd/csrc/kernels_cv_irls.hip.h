@@ -3,7 +3,7 @@
 // Tweedie; robust MSE): reference nmf/cv_detail.hpp:101-292 (irls_solve_col_cv / irls_solve_row_cv), nmf/fit_cv.hpp:446-456,
 // :670-689 (callers), :866-961 (GP theta over the training entries), :1377-1443 (per-element losses).
 //
-// What differs from the non-CV IRLS kernels (kernels_irls.hip.h) -- all of it the reference's behaviour, restated:
+// What differs from the non-CV IRLS kernels (kernels_irls.hip.h, kernels_dispersion.hip.h) -- all of it the reference's behaviour, restated:
 //   * the weighted Gram is built FROM ZERO over the column's TRAINING entries, G_w = sum_train w f f^T (no base Gram, no w - 1),
 //     plus the additive CV features (L2, graph, L21: `G_add`) and 1e-15 on the diagonal;
 //   * training entries: the nonzeros that are not held out (mask_zeros) or EVERY row that is not held out, zeros included --
@@ -19,7 +19,7 @@
 // ============================================================================
 #pragma once
 #include "kernels_cv.hip.h"
-#include "kernels_irls.hip.h"
+#include "kernels_dispersion.hip.h"
 
 namespace rk {
 
@@ -53,51 +53,16 @@ template <class T> __device__ __forceinline__ T cv_irls_weight_dev(int loss_type
     if (loss_type == 0) w_dist = T(1);
     else if (loss_type == 4) w_dist = irls_weight_gp_dev<T>(T(0), predicted, T(0), T(1));
     else w_dist = irls_weight_dev<T>(loss_type, predicted, T(0), power);
-    if (robust > T(0)) {
-        const T wd = w_dist > T(1e-15) ? w_dist : T(1e-15);
-        const T abs_r = tabs(residual * sqrt(wd));
-        return abs_r <= robust ? w_dist : w_dist * (robust / (abs_r + T(1e-15)));
-    }
-    return w_dist;
+    return huber_weight_dev<T>(w_dist, residual, robust);
 }
 
-// compute_loss(observed, predicted, loss, theta), math/loss.hpp:511-535 with the per-distribution terms of :382-505, each in fp64
-// and cast to Scalar as the reference's Scalar-typed functions return them (loss_type 0: squared error)
+// compute_loss(observed, predicted, loss, theta), math/loss.hpp:511-535: the per-distribution terms (dist_loss_term, kernels.hip.h) in
+// fp64 and cast to Scalar as the reference's Scalar-typed functions return them (loss_type 0: squared error)
 template <class T> __device__ __forceinline__ T cv_loss_term_dev(int loss_type, T observed, T predicted, T theta, double power) {
     if (loss_type == 0) { const T df = observed - predicted; return df * df; }
-    const double y = static_cast<double>(observed);
     double mu = static_cast<double>(predicted);
     mu = mu > 1e-10 ? mu : 1e-10;
-    const double th = static_cast<double>(theta);
-    double nll;
-    if (loss_type == 4) {                  // loss_contribution_gp
-        const double opt = 1.0 + th;
-        nll = -log(mu / opt);
-        if (y >= 1.0) {
-            double inner = (mu + th * y) / opt;
-            inner = inner > 1e-10 ? inner : 1e-10;
-            nll -= (y - 1.0) * log(inner);
-        }
-        nll += (mu + th * y) / opt;
-    } else if (loss_type >= 6) {           // Gamma / inverse Gaussian / Tweedie deviance terms
-        const double yy = y > 1e-10 ? y : 1e-10;
-        const double pp = loss_type == 6 ? 2.0 : (loss_type == 7 ? 3.0 : power);
-        if (loss_type == 7) {
-            const double df = yy - mu;
-            nll = df * df / (mu * mu * yy);
-        } else if (fabs(pp - 1.0) < 1e-6) {
-            nll = 2.0 * (yy * log(yy / mu) - (yy - mu));
-        } else if (fabs(pp - 2.0) < 1e-6) {
-            nll = 2.0 * (-log(yy / mu) + (yy - mu) / mu);
-        } else {
-            const double omp = 1.0 - pp, tmp = 2.0 - pp;
-            nll = 2.0 * (pow(yy, tmp) / (omp * tmp) - yy * pow(mu, omp) / omp + pow(mu, tmp) / tmp);
-        }
-    } else {                               // loss_contribution_nb
-        const double r = th > 1e-10 ? th : 1e-10;
-        nll = -lgamma(y + r) + lgamma(r) - r * log(r / (r + mu)) - y * log(mu / (r + mu));
-    }
-    return static_cast<T>(nll);
+    return static_cast<T>(dist_loss_term(loss_type, static_cast<double>(observed), mu, static_cast<double>(theta), power));
 }
 
 template <class T, int KP>   // KP in {32, 64}
@@ -199,19 +164,15 @@ __global__ __launch_bounds__(256) void cv_irls_loss_kernel(
     __shared__ T dsh[128];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t j = (int64_t)blockIdx.x * 4 + wave;
-    if (threadIdx.x < 128) dsh[threadIdx.x] = (int)threadIdx.x < k ? d[threadIdx.x] : T(0);
-    hs[wave][lane] = (j < ncols && lane < k) ? H[j * (int64_t)k + lane] : T(0);
-    hs[wave][lane + 64] = (j < ncols && lane + 64 < k) ? H[j * (int64_t)k + lane + 64] : T(0);
-    __syncthreads();
+    stage_column(dsh, hs, d, H, j, ncols, k);
     double tr = 0.0, te = 0.0;
     unsigned long long ntr = 0, nte = 0;
     if (j < ncols) {
+        const bool vec_ok = gather_vec_ok(W_T, k);
         const int as = colptr[j], ae = colptr[j + 1];
         auto term = [&](int row, T a) {
             if (cv_user_masked(mp, mi, j, row)) return;              // fit_cv.hpp:1391, :1407: user-masked entries are in neither sum
-            const T* wr = W_T + (int64_t)row * k;
-            T pred = T(0);
-            for (int c = 0; c < k; ++c) pred = tfma(wr[c] * dsh[c], hs[wave][c], pred);
+            const T pred = column_pred(W_T + (int64_t)row * k, dsh, hs[wave], k, vec_ok);
             const T th = (loss_type == 4 && theta_row) ? theta_row[row] : T(0);
             const double lv = static_cast<double>(cv_loss_term_dev<T>(loss_type, a, pred, th, power));
             if (cv_held(seed, 0, (unsigned)j, (unsigned)row, threshold)) { te += lv; ++nte; } else { tr += lv; ++ntr; }
@@ -266,25 +227,20 @@ __global__ __launch_bounds__(256) void cv_gp_theta_rows_kernel(
     const int* __restrict__ tp, const int* __restrict__ ti, const T* __restrict__ tx, int64_t m, int64_t n,
     const T* __restrict__ W_T, const T* __restrict__ d, const T* __restrict__ H, const T* __restrict__ h_rs, int k,
     unsigned long long seed, unsigned long long threshold, double hi, T* __restrict__ s_cache, T* __restrict__ theta) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __shared__ T wds[4][128];
+    // (the wave index as a SCALAR: the row's bounds and pointers then sit in SGPRs, which leaves the VGPRs for the 16-byte gathers)
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + wave;
     if (i >= m) return;
-    const bool fok = lane < k, fok2 = lane + 64 < k;                     // lane holds features lane and lane + 64 (k <= 128)
-    const T wd = fok ? W_T[i * (int64_t)k + lane] * d[lane] : T(0);
-    const T wd2 = fok2 ? W_T[i * (int64_t)k + lane + 64] * d[lane + 64] : T(0);
-    __shared__ T wds[4][128];
-    wds[wave][lane] = wd;
-    wds[wave][lane + 64] = wd2;
-    __builtin_amdgcn_wave_barrier();
+    const ScaledRow<T> row(wds[wave], W_T, d, i, k, lane);
+    const bool vec_ok = gather_vec_ok(H, k);
     const int ts = tp[i], te = tp[i + 1];
     double sum_y = 0.0, n_nz = 0.0;
     for (int t = ts + lane; t < te; t += 64) {
         const int col = ti[t];
         if (cv_held(seed, 1, (unsigned)i, (unsigned)col, threshold)) { s_cache[t] = T(-1); continue; }     // held out: not a training entry
-        const T* hr = H + (int64_t)col * k;
-        T dot = T(0);
-        for (int c = 0; c < k; ++c) dot = tfma(wds[wave][c], hr[c], dot);
-        dot = dot > T(0) ? dot : T(0);            // (s_cache < 0 marks held-out entries; predictions are floored at 1e-10 below anyway)
+        T dot = row.dot(H + (int64_t)col * k, k, vec_ok);
+        dot = dot > T(0) ? dot : T(0);            // (s_cache < 0 marks held-out entries; predictions are floored at 1e-10 in the update anyway)
         const double y = static_cast<double>(tx[t]);
         s_cache[t] = dot;
         sum_y += y;
@@ -292,47 +248,14 @@ __global__ __launch_bounds__(256) void cv_gp_theta_rows_kernel(
     }
     sum_y = wave_sum(sum_y);
     n_nz = wave_sum(n_nz);
-    double sum_s = static_cast<double>(wave_sum((fok ? wd * h_rs[lane] : T(0)) + (fok2 ? wd2 * h_rs[lane + 64] : T(0))));
+    double sum_s = static_cast<double>(row.dot_k(h_rs));
     double held_s = 0.0;
     for (int64_t j0 = 0; j0 < n; j0 += 64) {
         const int64_t jj = j0 + lane;
-        if (jj < n && cv_held(seed, 1, (unsigned)i, (unsigned)jj, threshold)) {
-            const T* hr = H + jj * k;
-            T dot = T(0);
-            for (int c = 0; c < k; ++c) dot = tfma(wds[wave][c], hr[c], dot);
-            held_s += static_cast<double>(dot);
-        }
+        if (jj < n && cv_held(seed, 1, (unsigned)i, (unsigned)jj, threshold)) held_s += static_cast<double>(row.dot(H + jj * k, k, vec_ok));
     }
     sum_s -= wave_sum(held_s);
-    T th_s = theta[i];
-    for (int mm = 0; mm < 5; ++mm) {
-        const double th = static_cast<double>(th_s);
-        double alpha = 0.0, gamma = 0.0;
-        for (int t = ts + lane; t < te; t += 64) {
-            const double y = static_cast<double>(tx[t]);
-            const T sc = s_cache[t];
-            if (y >= 1.0 && !(sc < T(0))) {
-                double sv = static_cast<double>(sc);
-                sv = sv > 1e-10 ? sv : 1e-10;
-                double denom = sv + th * y;
-                denom = denom > 1e-10 ? denom : 1e-10;
-                const double eta1 = sv / denom;
-                alpha += (y - 1.0) * eta1;
-                gamma += (y - 1.0) * (1.0 - eta1);
-            }
-        }
-        alpha = wave_sum(alpha);
-        gamma = wave_sum(gamma);
-        const double a = alpha + n_nz;
-        const double b = (sum_y - sum_s) - gamma + a;
-        if (a > 1e-15) {
-            const double disc = b * b + 4.0 * a * gamma;
-            if (disc > 0.0 && isfinite(disc)) {
-                const double nt = (-b + sqrt(disc)) / (2.0 * a);
-                if (isfinite(nt) && nt >= 0.0) th_s = static_cast<T>(nt < hi ? nt : hi);
-            }
-        }
-    }
+    const T th_s = gp_theta_mm<T, true>(tx, s_cache, ts, te, lane, sum_y, n_nz, sum_s, hi, theta[i]);
     if (lane == 0) theta[i] = th_s;
 }
 

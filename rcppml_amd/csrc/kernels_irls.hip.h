@@ -1,10 +1,10 @@
 // ============================================================================
-// kernels_irls.hip.h -- NB (negative-binomial) IRLS path of the ALS-NNLS NMF update for gfx950
-// (BASELINE config 5).
+// kernels_irls.hip.h -- IRLS weights and half-update (solve) kernels of the ALS-NNLS NMF update for gfx950
+// (BASELINE config 5).  The dispersion estimators and likelihoods: kernels_dispersion.hip.h.
 //
-//   irls_nb_solve_kernel  primitives/cpu/nnls_batch_irls.hpp:202-329,465-520 + math/loss.hpp:248-256
-//   nb_size_rows_kernel   nmf/fit_cpu.hpp:1094-1265 (PER_ROW / GLOBAL, sparse branch)
-//   nb_loss_kernel        nmf/explicit_loss.hpp:53-77 + math/loss.hpp:415-426
+//   irls_weight_*_dev     math/loss.hpp:176-303, nnls_batch_irls.hpp:57-120
+//   irls_nb_solve_kernel  primitives/cpu/nnls_batch_irls.hpp:202-329,465-520 (any k <= 64, row-in-registers weighted Gram)
+//   irls_nb_mfma*_kernel  the same half-update with the weighted Gram on the matrix cores
 //
 // One wavefront per column, lane r = feature r (k <= 64).  Per IRLS pass the wave walks the column's nonzeros once:
 // the reconstruction f_i . x is a wave reduction, the NB weight is evaluated in fp64 as the reference does, and the
@@ -119,17 +119,20 @@ template <class T> __device__ __forceinline__ T irls_weight_dev(int loss_type, T
     return irls_weight_nb_dev<T>(predicted, theta);
 }
 
-// nnls_batch_irls.hpp:95-120  compute_irls_weight: distribution weight (1 for loss_type 0 = MSE) x Huber modifier of
-// the Pearson residual when robust_delta > 0 (math/loss.hpp:294-303)
-template <class T> __device__ __forceinline__ T irls_weight_full_dev(int loss_type, T residual, T predicted, T theta, T power,
-                                                                     T robust) {
-    const T w_dist = loss_type == 0 ? T(1) : irls_weight_dev<T>(loss_type, predicted, theta, power);
+// math/loss.hpp:294-303  the distribution weight times the Huber modifier of the Pearson residual when robust_delta > 0
+template <class T> __device__ __forceinline__ T huber_weight_dev(T w_dist, T residual, T robust) {
     if (robust > T(0)) {
         const T wd = w_dist > T(1e-15) ? w_dist : T(1e-15);
         const T abs_r = tabs(residual * sqrt(wd));
         return abs_r <= robust ? w_dist : w_dist * (robust / (abs_r + T(1e-15)));
     }
     return w_dist;
+}
+
+// nnls_batch_irls.hpp:95-120  compute_irls_weight: distribution weight (1 for loss_type 0 = MSE) x Huber modifier
+template <class T> __device__ __forceinline__ T irls_weight_full_dev(int loss_type, T residual, T predicted, T theta, T power,
+                                                                     T robust) {
+    return huber_weight_dev<T>(loss_type == 0 ? T(1) : irls_weight_dev<T>(loss_type, predicted, theta, power), residual, robust);
 }
 
 template <class T, int KP>   // KP in {32, 64}: features padded to KP (k <= KP), lane r = feature r
@@ -747,459 +750,6 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8
     if (fok) X[j * (int64_t)k + lane] = x;
     // work counters (RCPPML_OPT_CD_COUNT_NOOP only): IRLS passes and nonzero-passes = weighted-Gram rank-1 updates
     if (stats && lane == 0) { atomicAdd(stats, (unsigned long long)passes); atomicAdd(stats + 1, (unsigned long long)passes * (unsigned long long)(ae - as)); atomicAdd(stats + 4, (unsigned long long)nsw); }
-}
-
-// NB size (r) method-of-moments update, one wavefront per ROW i of A (= column i of A^T):
-//   nonzero sums of mu^2 and (y-mu)^2 in fp64, totals via  Wd_i . h_rs  and  Wd_i^T G_H Wd_i.
-template <class T>
-__global__ __launch_bounds__(256) void nb_size_rows_kernel(
-    const int* __restrict__ tp, const int* __restrict__ ti, const T* __restrict__ tx, int64_t m,
-    const T* __restrict__ W_T, const T* __restrict__ d, const T* __restrict__ H, const T* __restrict__ h_rs,
-    const T* __restrict__ G_H, int k, double r_min, double r_max, T* __restrict__ nb_size) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * 4 + wave;
-    if (i >= m) return;
-    const bool fok = lane < k, fok2 = lane + 64 < k;                     // lane holds features lane and lane + 64 (k <= 128)
-    const T wd = fok ? W_T[i * (int64_t)k + lane] * d[lane] : T(0);     // apply_scaling(W_Td, d)
-    const T wd2 = fok2 ? W_T[i * (int64_t)k + lane + 64] * d[lane + 64] : T(0);
-    // one lane per nonzero: the row of H is gathered with 16-byte loads and dotted in-lane against Wd_i (LDS broadcast)
-    __shared__ T wds[4][128];
-    wds[wave][lane] = wd;
-    wds[wave][lane + 64] = wd2;
-    __builtin_amdgcn_wave_barrier();
-    constexpr int VEC = 16 / sizeof(T);
-    typedef typename VecT<T, VEC>::type V;
-    const bool vec_ok = (k % VEC == 0) && (reinterpret_cast<uintptr_t>(H) % 16 == 0);
-    double s_mu2 = 0.0, s_res2 = 0.0;
-    for (int t = tp[i] + lane; t < tp[i + 1]; t += 64) {
-        const int col = ti[t];
-        const T* hr = H + (int64_t)col * k;
-        T dot = T(0);
-        if (vec_ok) {
-            for (int c = 0; c < k; c += VEC) {
-                const V v = *reinterpret_cast<const V*>(hr + c);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) dot = tfma(wds[wave][c + e], v[e], dot);
-            }
-        } else {
-            for (int c = 0; c < k; ++c) dot = tfma(wds[wave][c], hr[c], dot);
-        }
-        const double y = static_cast<double>(tx[t]);
-        double mu = static_cast<double>(dot);
-        mu = mu > 1e-10 ? mu : 1e-10;
-        const double resid = y - mu;
-        s_mu2 += mu * mu;
-        s_res2 += resid * resid;
-    }
-    s_mu2 = wave_sum(s_mu2);
-    s_res2 = wave_sum(s_res2);
-    const T tm = wave_sum((fok ? wd * h_rs[lane] : T(0)) + (fok2 ? wd2 * h_rs[lane + 64] : T(0)));
-    const double total_mu = static_cast<double>(tm);
-    // total_mu_sq = sum_ab Wd_a G_H(a,b) Wd_b  (fp64 accumulation as the reference)
-    double acc = 0.0;
-    for (int b2 = 0; b2 < k; ++b2) {
-        const double wb = static_cast<double>(wds[wave][b2]);
-        if (fok) acc += static_cast<double>(wd) * static_cast<double>(G_H[(int64_t)b2 * k + lane]) * wb;
-        if (fok2) acc += static_cast<double>(wd2) * static_cast<double>(G_H[(int64_t)b2 * k + lane + 64]) * wb;
-    }
-    const double total_mu_sq = wave_sum(acc);
-    if (lane == 0) {
-        const double total_resid_sq = s_res2 + (total_mu_sq - s_mu2);
-        const double excess = total_resid_sq - total_mu;
-        if (excess > 1e-10 && total_mu_sq > 1e-10) {
-            double r_new = total_mu_sq / excess;
-            r_new = r_new < r_max ? r_new : r_max;
-            r_new = r_new > r_min ? r_new : r_min;
-            if (isfinite(r_new)) nb_size[i] = static_cast<T>(r_new);
-        } else {
-            nb_size[i] = static_cast<T>(r_max);
-        }
-    }
-}
-
-// NB size update AND the NB negative log-likelihood in one kernel (PER_ROW dispersion, no robust modifier): fit_cpu.hpp:1094-1265
-// followed by explicit_loss.hpp:53-77 + math/loss.hpp:415-426 with the UPDATED sizes, as the fit loop orders them.  One wavefront
-// per row i of A: the first pass over the row's nonzeros is nb_size_rows_kernel's (prediction = Wd_i . H_col, in-lane) and parks
-// every prediction in mu_cache (each lane re-reads only what it wrote); the row's new size r_i is then known to the whole wave,
-// and the second pass evaluates the likelihood terms from the parked predictions -- no second gather of factor rows (the
-// separate loss kernel re-gathers 128 B per nonzero), and lgamma(r_i) once per row instead of once per nonzero.  The terms are
-// those of nb_loss_lane_kernel (same prediction arithmetic: (W d) . H in feature order, same fp64 formula, each term cast to
-// Scalar); only the order of the fp64 sum differs (by row instead of by column).
-template <class T>
-__global__ __launch_bounds__(256) void nb_size_loss_rows_kernel(
-    const int* __restrict__ tp, const int* __restrict__ ti, const T* __restrict__ tx, int64_t m,
-    const T* __restrict__ W_T, const T* __restrict__ d, const T* __restrict__ H, const T* __restrict__ h_rs,
-    const T* __restrict__ G_H, int k, double r_min, double r_max, T* __restrict__ nb_size, T* __restrict__ mu_cache,
-    double* __restrict__ partial) {
-    __shared__ T wds[4][128];
-    __shared__ double sh[4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * 4 + wave;
-    double nll_sum = 0.0;
-    if (i < m) {
-        const bool fok = lane < k, fok2 = lane + 64 < k;                     // lane holds features lane and lane + 64 (k <= 128)
-        const T wd = fok ? W_T[i * (int64_t)k + lane] * d[lane] : T(0);     // apply_scaling(W_Td, d)
-        const T wd2 = fok2 ? W_T[i * (int64_t)k + lane + 64] * d[lane + 64] : T(0);
-        wds[wave][lane] = wd;
-        wds[wave][lane + 64] = wd2;
-        __builtin_amdgcn_wave_barrier();
-        constexpr int VEC = 16 / sizeof(T);
-        typedef typename VecT<T, VEC>::type V;
-        const bool vec_ok = (k % VEC == 0) && (reinterpret_cast<uintptr_t>(H) % 16 == 0);
-        const int ts = tp[i], te = tp[i + 1];
-        double s_mu2 = 0.0, s_res2 = 0.0;
-        for (int t = ts + lane; t < te; t += 64) {
-            const int col = ti[t];
-            const T* hr = H + (int64_t)col * k;
-            T dot = T(0);
-            if (vec_ok) {
-                for (int c = 0; c < k; c += VEC) {
-                    const V v = *reinterpret_cast<const V*>(hr + c);
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) dot = tfma(wds[wave][c + e], v[e], dot);
-                }
-            } else {
-                for (int c = 0; c < k; ++c) dot = tfma(wds[wave][c], hr[c], dot);
-            }
-            mu_cache[t] = dot;
-            const double y = static_cast<double>(tx[t]);
-            double mu = static_cast<double>(dot);
-            mu = mu > 1e-10 ? mu : 1e-10;
-            const double resid = y - mu;
-            s_mu2 += mu * mu;
-            s_res2 += resid * resid;
-        }
-        s_mu2 = wave_sum(s_mu2);
-        s_res2 = wave_sum(s_res2);
-        const T tm = wave_sum((fok ? wd * h_rs[lane] : T(0)) + (fok2 ? wd2 * h_rs[lane + 64] : T(0)));
-        const double total_mu = static_cast<double>(tm);
-        double acc = 0.0;                                                    // total_mu_sq = Wd^T G_H Wd, fp64 as the reference
-        for (int b2 = 0; b2 < k; ++b2) {
-            const double wb = static_cast<double>(wds[wave][b2]);
-            if (fok) acc += static_cast<double>(wd) * static_cast<double>(G_H[(int64_t)b2 * k + lane]) * wb;
-            if (fok2) acc += static_cast<double>(wd2) * static_cast<double>(G_H[(int64_t)b2 * k + lane + 64]) * wb;
-        }
-        const double total_mu_sq = wave_sum(acc);
-        // every lane takes the decision lane 0 takes in nb_size_rows_kernel (wave_sum leaves the same value in all lanes)
-        T size_new = nb_size[i];
-        {
-            const double total_resid_sq = s_res2 + (total_mu_sq - s_mu2);
-            const double excess = total_resid_sq - total_mu;
-            if (excess > 1e-10 && total_mu_sq > 1e-10) {
-                double r_new = total_mu_sq / excess;
-                r_new = r_new < r_max ? r_new : r_max;
-                r_new = r_new > r_min ? r_new : r_min;
-                if (isfinite(r_new)) size_new = static_cast<T>(r_new);
-            } else {
-                size_new = static_cast<T>(r_max);
-            }
-        }
-        if (lane == 0) nb_size[i] = size_new;
-        // ---- likelihood terms of the row with the updated size (math/loss.hpp:415-426)
-        const double th = static_cast<double>(size_new);
-        const double r = th > 1e-10 ? th : 1e-10;
-        const double lg_r = lgamma(r);
-        for (int t = ts + lane; t < te; t += 64) {
-            const double y = static_cast<double>(tx[t]);
-            double mu = static_cast<double>(mu_cache[t]);
-            mu = mu > 1e-10 ? mu : 1e-10;
-            const double nll = -lgamma(y + r) + lg_r - r * log(r / (r + mu)) - y * log(mu / (r + mu));
-            nll_sum += static_cast<double>(static_cast<T>(nll));             // the reference casts each term to Scalar
-        }
-    }
-    nll_sum = wave_sum(nll_sum);
-    if (lane == 0) sh[wave] = nll_sum;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// Dispersion estimators of the other IRLS losses, one wavefront per ROW i of A (= column i of A^T), one lane per nonzero
-// (the gather / in-lane dot of nb_size_rows_kernel):
-//   loss_type 4      GP theta, auxiliary-function (MM) update, nmf/fit_cpu.hpp:914-1001: the Scalar predictions s of the
-//                    row's nonzeros are parked in s_cache (each lane re-reads what it wrote), then five inner passes
-//                    accumulate alpha / gamma in fp64 with theta rounded through Scalar between passes, as the reference;
-//   loss_type 6/7/8  Pearson phi over the positive nonzeros, nmf/fit_cpu.hpp:1561-1661, clamped to [lo, hi].
-template <class T>
-__global__ __launch_bounds__(256) void dispersion_rows_kernel(
-    const int* __restrict__ tp, const int* __restrict__ ti, const T* __restrict__ tx, int64_t m,
-    const T* __restrict__ W_T, const T* __restrict__ d, const T* __restrict__ H, const T* __restrict__ h_rs, int k,
-    int loss_type, double power, double lo, double hi, T* __restrict__ s_cache, T* __restrict__ theta) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * 4 + wave;
-    if (i >= m) return;
-    const bool fok = lane < k, fok2 = lane + 64 < k;                     // lane holds features lane and lane + 64 (k <= 128)
-    const T wd = fok ? W_T[i * (int64_t)k + lane] * d[lane] : T(0);     // apply_scaling(W_Td, d)
-    const T wd2 = fok2 ? W_T[i * (int64_t)k + lane + 64] * d[lane + 64] : T(0);
-    __shared__ T wds[4][128];
-    wds[wave][lane] = wd;
-    wds[wave][lane + 64] = wd2;
-    __builtin_amdgcn_wave_barrier();
-    constexpr int VEC = 16 / sizeof(T);
-    typedef typename VecT<T, VEC>::type V;
-    const bool vec_ok = (k % VEC == 0) && (reinterpret_cast<uintptr_t>(H) % 16 == 0);
-    const int ts = tp[i], te = tp[i + 1];
-    const bool is_gp = loss_type == 4;
-    const double var_power = loss_type == 8 ? power : (loss_type == 6 ? 2.0 : 3.0);
-    double acc0 = 0.0, acc1 = 0.0;      // GP: sum_y, n_nz      phi: sum of Pearson terms, count
-    for (int t = ts + lane; t < te; t += 64) {
-        const int col = ti[t];
-        const T* hr = H + (int64_t)col * k;
-        T dot = T(0);
-        if (vec_ok) {
-            for (int c = 0; c < k; c += VEC) {
-                const V v = *reinterpret_cast<const V*>(hr + c);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) dot = tfma(wds[wave][c + e], v[e], dot);
-            }
-        } else {
-            for (int c = 0; c < k; ++c) dot = tfma(wds[wave][c], hr[c], dot);
-        }
-        const double y = static_cast<double>(tx[t]);
-        if (is_gp) {
-            s_cache[t] = dot;
-            acc0 += y;
-            if (y >= 1.0) acc1 += 1.0;
-        } else if (y > 0.0) {
-            double mu = static_cast<double>(dot);
-            mu = mu > 1e-10 ? mu : 1e-10;
-            const double resid = y - mu;
-            double v_mu = pow(mu, var_power);
-            v_mu = v_mu > 1e-20 ? v_mu : 1e-20;
-            acc0 += (resid * resid) / v_mu;
-            acc1 += 1.0;
-        }
-    }
-    acc0 = wave_sum(acc0);
-    acc1 = wave_sum(acc1);
-    if (!is_gp) {
-        if (lane == 0 && acc1 > 0.0) {
-            double pn = acc0 / acc1;
-            pn = pn < hi ? pn : hi;
-            pn = pn > lo ? pn : lo;
-            if (isfinite(pn)) theta[i] = static_cast<T>(pn);
-        }
-        return;
-    }
-    const double sum_s = static_cast<double>(wave_sum((fok ? wd * h_rs[lane] : T(0)) + (fok2 ? wd2 * h_rs[lane + 64] : T(0))));   // Gram trick, :935-938
-    T th_s = theta[i];
-    for (int mm = 0; mm < 5; ++mm) {                                                          // THETA_INNER_ITERS
-        const double th = static_cast<double>(th_s);
-        double alpha = 0.0, gamma = 0.0;
-        for (int t = ts + lane; t < te; t += 64) {
-            const double y = static_cast<double>(tx[t]);
-            if (y >= 1.0) {
-                double sv = static_cast<double>(s_cache[t]);
-                sv = sv > 1e-10 ? sv : 1e-10;
-                double denom = sv + th * y;
-                denom = denom > 1e-10 ? denom : 1e-10;
-                const double eta1 = sv / denom;
-                alpha += (y - 1.0) * eta1;
-                gamma += (y - 1.0) * (1.0 - eta1);
-            }
-        }
-        alpha = wave_sum(alpha);
-        gamma = wave_sum(gamma);
-        const double a = alpha + acc1;
-        const double b = (acc0 - sum_s) - gamma + a;
-        if (a > 1e-15) {
-            const double disc = b * b + 4.0 * a * gamma;
-            if (disc > 0.0 && isfinite(disc)) {
-                const double nt = (-b + sqrt(disc)) / (2.0 * a);
-                if (isfinite(nt) && nt >= 0.0) th_s = static_cast<T>(nt < hi ? nt : hi);
-            }
-        }
-    }
-    if (lane == 0) theta[i] = th_s;
-}
-
-// GLOBAL dispersion: every entry <- the mean (stat 0; GP, fit_cpu.hpp:1005-1008) or <- src[m/2] of the SORTED copy
-// (stat 1: nth_element at m/2; NB :1257-1262, phi :1664-1669).  Single block.
-// The median is found by an 8-bit radix SELECT on order-preserving integer keys (no sort: the reference only needs the element
-// nth_element would put at m / 2): per digit, a 256-bin histogram of the candidates that share the prefix found so far.
-template <class T> struct OrdKey;
-template <> struct OrdKey<float> {
-    typedef unsigned int U;
-    static __device__ __forceinline__ U enc(float v) { const U b = __float_as_uint(v); return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); }
-    static __device__ __forceinline__ float dec(U k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
-};
-template <> struct OrdKey<double> {
-    typedef unsigned long long U;
-    static __device__ __forceinline__ U enc(double v) { const U b = (U)__double_as_longlong(v); return b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull); }
-    static __device__ __forceinline__ double dec(U k) { return __longlong_as_double((long long)(k ^ ((k >> 63) ? 0x8000000000000000ull : ~0ull))); }
-};
-template <class T>
-__global__ __launch_bounds__(256) void vec_global_fill_kernel(T* __restrict__ x, int64_t m, int stat) {
-    __shared__ double red[256];
-    __shared__ unsigned int hist[256];
-    __shared__ unsigned long long sel[2];              // [0] = digit chosen, [1] = rank left inside it
-    T val;
-    if (stat == 1) {
-        typedef typename OrdKey<T>::U U;
-        U prefix = 0, mask = 0;
-        unsigned long long kth = (unsigned long long)(m / 2);      // 0-based rank of the wanted element
-        for (int shift = (int)sizeof(U) * 8 - 8; shift >= 0; shift -= 8) {
-            hist[threadIdx.x] = 0;
-            __syncthreads();
-            for (int64_t i = threadIdx.x; i < m; i += 256) {
-                const U key = OrdKey<T>::enc(x[i]);
-                if ((key & mask) == prefix) atomicAdd(&hist[(unsigned)((key >> shift) & 0xff)], 1u);
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                unsigned long long run = 0;
-                int dgt = 0;
-                for (; dgt < 255; ++dgt) {
-                    if (run + hist[dgt] > kth) break;
-                    run += hist[dgt];
-                }
-                sel[0] = (unsigned long long)dgt;
-                sel[1] = kth - run;
-            }
-            __syncthreads();
-            prefix |= (U)sel[0] << shift;
-            mask |= (U)0xff << shift;
-            kth = sel[1];
-            __syncthreads();
-        }
-        val = OrdKey<T>::dec(prefix);
-    } else {
-        double acc = 0.0;
-        for (int64_t i = threadIdx.x; i < m; i += 256) acc += static_cast<double>(x[i]);
-        red[threadIdx.x] = acc;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
-        val = static_cast<T>(red[0] / static_cast<double>(m));
-    }
-    __syncthreads();
-    for (int64_t i = threadIdx.x; i < m; i += 256) x[i] = val;
-}
-
-// NB negative log-likelihood over the NONZEROS of A (explicit_loss.hpp:53-77), per-row theta, fp64 partials.
-// One wavefront per column, ONE LANE PER NONZERO: each lane gathers its row of W_T with 16-byte loads, forms the
-// prediction as k in-lane fmas against the column of H (broadcast from LDS) and evaluates the two lgamma / two log terms
-// of its own nonzero -- 64 likelihood terms per wave instruction stream instead of one.
-template <class T>
-__global__ __launch_bounds__(256) void nb_loss_lane_kernel(
-    const int* __restrict__ colptr, const int* __restrict__ rowidx, const T* __restrict__ vals, int64_t ncols,
-    const T* __restrict__ W_T, const T* __restrict__ d, const T* __restrict__ H, const T* __restrict__ theta_row, int k,
-    int vec_ok, int loss_type, double power, double robust, double* __restrict__ partial) {
-    constexpr int VEC = 16 / sizeof(T);
-    typedef typename VecT<T, VEC>::type V;
-    __shared__ double sh[4];
-    __shared__ T hs[4][128];
-    __shared__ T dsh[128];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t j = (int64_t)blockIdx.x * 4 + wave;
-    if (threadIdx.x < 128) dsh[threadIdx.x] = (int)threadIdx.x < k ? d[threadIdx.x] : T(0);
-    hs[wave][lane] = (j < ncols && lane < k) ? H[j * (int64_t)k + lane] : T(0);
-    hs[wave][lane + 64] = (j < ncols && lane + 64 < k) ? H[j * (int64_t)k + lane + 64] : T(0);
-    __syncthreads();
-    double acc = 0.0;
-    if (j < ncols) {
-        const int as = colptr[j], ae = colptr[j + 1];
-        for (int t = as + lane; t < ae; t += 64) {
-            const int row = rowidx[t];
-            const T* wr = W_T + (int64_t)row * k;
-            T pred = T(0);
-            if (vec_ok) {
-                for (int c = 0; c < k; c += VEC) {
-                    const V v = *reinterpret_cast<const V*>(wr + c);
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) pred = tfma(v[e] * dsh[c + e], hs[wave][c + e], pred);
-                }
-            } else {
-                for (int c = 0; c < k; ++c) pred = tfma(wr[c] * dsh[c], hs[wave][c], pred);
-            }
-            const double y = static_cast<double>(vals[t]);
-            double mu = static_cast<double>(pred);
-            mu = mu > 1e-10 ? mu : 1e-10;
-            const double th = static_cast<double>(theta_row ? theta_row[row] : T(0));
-            double nll;
-            if (robust > 0.0) {                    // math/loss.hpp:549-607  compute_robust_loss, in Scalar arithmetic
-                const T muS = pred > T(1e-10) ? pred : T(1e-10);
-                const T resid = vals[t] - muS;
-                const T thS = theta_row ? theta_row[row] : T(0);
-                T var_mu;
-                if (loss_type == 4 || loss_type == 3) var_mu = muS;
-                else if (loss_type == 5) { const T r = thS > T(1e-10) ? thS : T(1e-10); var_mu = muS + muS * muS / r; }
-                else if (loss_type == 6) var_mu = muS * muS;
-                else if (loss_type == 7) var_mu = muS * muS * muS;
-                else if (loss_type == 8) var_mu = static_cast<T>(pow(static_cast<double>(muS), power));
-                else var_mu = T(1);
-                const T sd = sqrt(var_mu > T(1e-20) ? var_mu : T(1e-20));
-                const T pr = resid / sd;
-                const T apr = tabs(pr);
-                const T dl = static_cast<T>(robust);
-                const T rho = apr <= dl ? T(0.5) * pr * pr : dl * apr - T(0.5) * dl * dl;
-                nll = static_cast<double>(rho);
-            } else if (loss_type == 4) {           // math/loss.hpp:382-398  loss_contribution_gp
-                const double opt = 1.0 + th;
-                nll = -log(mu / opt);
-                if (y >= 1.0) {
-                    double inner = (mu + th * y) / opt;
-                    inner = inner > 1e-10 ? inner : 1e-10;
-                    nll -= (y - 1.0) * log(inner);
-                }
-                nll += (mu + th * y) / opt;
-            } else if (loss_type >= 6) {           // math/loss.hpp:439-505  Gamma / inverse Gaussian / Tweedie deviance terms
-                const double yy = y > 1e-10 ? y : 1e-10;
-                const double pp = loss_type == 6 ? 2.0 : (loss_type == 7 ? 3.0 : power);
-                if (loss_type == 7) {
-                    const double df = yy - mu;
-                    nll = df * df / (mu * mu * yy);
-                } else if (fabs(pp - 1.0) < 1e-6) {
-                    nll = 2.0 * (yy * log(yy / mu) - (yy - mu));
-                } else if (fabs(pp - 2.0) < 1e-6) {
-                    nll = 2.0 * (-log(yy / mu) + (yy - mu) / mu);
-                } else {
-                    const double omp = 1.0 - pp, tmp = 2.0 - pp;
-                    nll = 2.0 * (pow(yy, tmp) / (omp * tmp) - yy * pow(mu, omp) / omp + pow(mu, tmp) / tmp);
-                }
-            } else {                               // math/loss.hpp:415-426  loss_contribution_nb
-                const double r = th > 1e-10 ? th : 1e-10;
-                nll = -lgamma(y + r) + lgamma(r) - r * log(r / (r + mu)) - y * log(mu / (r + mu));
-            }
-            acc += static_cast<double>(static_cast<T>(nll));      // the reference casts each term to Scalar
-        }
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) sh[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// Wave-per-nonzero form (any k <= 64 layout; kept for reference and as the fallback).
-template <class T>
-__global__ __launch_bounds__(256) void nb_loss_kernel(
-    const int* __restrict__ colptr, const int* __restrict__ rowidx, const T* __restrict__ vals, int64_t ncols,
-    const T* __restrict__ W_T, const T* __restrict__ d, const T* __restrict__ H, const T* __restrict__ theta_row, int k,
-    double* __restrict__ partial) {
-    __shared__ double sh[4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t j = (int64_t)blockIdx.x * 4 + wave;
-    double acc = 0.0;
-    if (j < ncols) {
-        const bool fok = lane < k;
-        const bool fok2 = lane + 64 < k;
-        const T hv = fok ? H[j * (int64_t)k + lane] : T(0);
-        const T hv2 = fok2 ? H[j * (int64_t)k + lane + 64] : T(0);
-        for (int t = colptr[j]; t < colptr[j + 1]; ++t) {
-            const int row = rowidx[t];
-            const T wd = fok ? W_T[(int64_t)row * k + lane] * d[lane] : T(0);
-            const T wd2 = fok2 ? W_T[(int64_t)row * k + lane + 64] * d[lane + 64] : T(0);
-            const T pred = wave_sum(wd * hv + wd2 * hv2);
-            const double y = static_cast<double>(vals[t]);
-            double mu = static_cast<double>(pred);
-            mu = mu > 1e-10 ? mu : 1e-10;
-            double r = static_cast<double>(theta_row ? theta_row[row] : T(0));
-            r = r > 1e-10 ? r : 1e-10;
-            const double nll = -lgamma(y + r) + lgamma(r) - r * log(r / (r + mu)) - y * log(mu / (r + mu));
-            acc += static_cast<double>(static_cast<T>(nll));      // the reference casts each term to Scalar
-        }
-    }
-    if (lane == 0) sh[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
 }  // namespace rk

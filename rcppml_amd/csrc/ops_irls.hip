@@ -2,7 +2,7 @@
 #include <type_traits>
 #include <cstring>
 #include "common.hip.h"
-#include "kernels_irls.hip.h"
+#include "kernels_dispersion.hip.h"
 #include "kernels_wide.hip.h"
 
 using namespace rk;
@@ -118,8 +118,8 @@ static void nb_size_impl(rcppml_hip_ctx* c, int dtype, const int* tp, const int*
     if (rcppml_hip_gram(c, dtype, H, k, n, 1e-15, 0.0, G_H) != 0) throw std::runtime_error(rcppml_err());
     if (rcppml_hip_row_norms(c, dtype, H, k, n, 3, h_rs) != 0) throw std::runtime_error(rcppml_err());
     const int64_t nblk = (m + 3) / 4;
-    hipLaunchKernelGGL(nb_size_rows_kernel<T>, dim3((unsigned)nblk), dim3(256), 0, c->stream, tp, ti, tx, m, W_T, d, H, h_rs,
-                       G_H, k, r_min, r_max, nb_size);
+    hipLaunchKernelGGL((nb_size_rows_kernel<T, false>), dim3((unsigned)nblk), dim3(256), 0, c->stream, tp, ti, tx, m, W_T, d, H, h_rs,
+                       G_H, k, r_min, r_max, nb_size, static_cast<T*>(nullptr), static_cast<double*>(nullptr));
     HIPCHK(hipGetLastError());
 }
 extern "C" int rcppml_hip_nb_size_update(rcppml_hip_ctx* c, int dtype, const int* t_col_ptr, const int* t_row_idx,
@@ -152,7 +152,7 @@ static void nb_size_loss_impl(rcppml_hip_ctx* c, int dtype, const int* tp, const
     if (rcppml_hip_row_norms(c, dtype, H, k, n, 3, h_rs) != 0) throw std::runtime_error(rcppml_err());
     const int64_t nblk = m > 0 ? (m + 3) / 4 : 1;
     double* partial = static_cast<double*>(c->scratch(WS_RED2, (size_t)nblk * sizeof(double)));
-    hipLaunchKernelGGL(nb_size_loss_rows_kernel<T>, dim3((unsigned)nblk), dim3(256), 0, c->stream, tp, ti, tx, m, W_T, d, H, h_rs,
+    hipLaunchKernelGGL((nb_size_rows_kernel<T, true>), dim3((unsigned)nblk), dim3(256), 0, c->stream, tp, ti, tx, m, W_T, d, H, h_rs,
                        G_H, k, r_min, r_max, nb_size, mu_cache, partial);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(sum_partials, dim3(1), dim3(256), 0, c->stream, partial, (int)nblk, out);
@@ -232,10 +232,8 @@ static void nb_loss_impl(rcppml_hip_ctx* c, const int* cp, const int* ri, const 
                          const T* d, const T* H, const T* theta_row, int k, double* out, int loss_type, double power, double robust) {
     const int64_t nblk = ncols > 0 ? (ncols + 3) / 4 : 1;
     double* partial = static_cast<double*>(c->scratch(WS_RED2, (size_t)nblk * sizeof(double)));
-    constexpr int VEC = 16 / (int)sizeof(T);
-    const int vec_ok = (k % VEC == 0 && reinterpret_cast<uintptr_t>(W_T) % 16 == 0) ? 1 : 0;
     hipLaunchKernelGGL(nb_loss_lane_kernel<T>, dim3((unsigned)nblk), dim3(256), 0, c->stream, cp, ri, vals, ncols, W_T, d, H,
-                       theta_row, k, vec_ok, loss_type, power, robust, partial);
+                       theta_row, k, loss_type, power, robust, partial);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(sum_partials, dim3(1), dim3(256), 0, c->stream, partial, (int)nblk, out);
     HIPCHK(hipGetLastError());

@@ -281,18 +281,19 @@ def test_cv_irls_losses(env, dtype, tol, loss_type, mask_zeros):
 
 @pytest.mark.parametrize("dtype,tol", [(np.float64, 1e-9), (np.float32, 5e-4)])
 @pytest.mark.parametrize("mode", [2, 1])
-@pytest.mark.parametrize("frac", [0.2, 0.0])
-def test_cv_gp_theta_over_training_entries(env, dtype, tol, mode, frac):
+# k = 5: the element-wise gather loop; 8, 68: 16-byte loads (68 with a second feature per lane)
+@pytest.mark.parametrize("frac,k", [pytest.param(0.2, 5, id="0.2"), pytest.param(0.0, 5, id="0.0"), pytest.param(0.2, 8, id="0.2-k8"),
+                                    pytest.param(0.0, 8, id="0.0-k8"), pytest.param(0.2, 68, id="0.2-k68"), pytest.param(0.0, 68, id="0.0-k68")])
+def test_cv_gp_theta_over_training_entries(env, dtype, tol, mode, frac, k):
     """GP theta (MM update) over the training entries only (reference nmf/fit_cv.hpp:866-961); frac = 0 = the non-CV update."""
     torch, _abi, ctx = env
-    k = 5
     A = _counts_csc(60, 150, 0.3, seed=8)
     At = A.transpose()
     dt = _abi.F32 if dtype == np.float32 else _abi.F64
     rng = np.random.default_rng(mode)
     W = rng.uniform(0.1, 1.0, size=(A.rows, k)).astype(dtype)
     H = rng.uniform(0.1, 1.0, size=(A.cols, k)).astype(dtype)
-    d = rng.uniform(0.5, 2.0, size=k).astype(dtype)
+    d = (rng.uniform(0.5, 2.0, size=k) * (5.0 / k)).astype(dtype)     # 5 / k: predictions of one size at every rank (theta off its cap)
     th0 = np.full(A.rows, 0.1, dtype)
     ref = O.cv_gp_theta_update(A, W, d, H, th0, frac, 13, mode=mode, theta_max=5.0, dtype=dtype)
     dth = _dev(torch, th0.copy())

@@ -90,7 +90,7 @@ def test_irls_static_sweep_options(env, k, opts):
 
 
 @pytest.mark.parametrize("dtype,tol", [(np.float64, 1e-9), (np.float32, 2e-3)])
-@pytest.mark.parametrize("k", [8, 96])
+@pytest.mark.parametrize("k", [8, 96, 7, 67])        # 7, 67: the element-wise gather loop (67 with a second feature per lane)
 def test_nb_size_and_loss(env, dtype, tol, k):
     torch, _abi, ctx = env
     A = _nb_problem(120, 180, 3, seed=5)
@@ -98,7 +98,7 @@ def test_nb_size_and_loss(env, dtype, tol, k):
     rng = np.random.default_rng(1)
     W_T = rng.uniform(size=(A.rows, k)).astype(dtype); W_T /= W_T.sum(axis=0, keepdims=True)
     H = rng.uniform(size=(A.cols, k)).astype(dtype); H /= H.sum(axis=0, keepdims=True)
-    d = rng.uniform(50, 500, size=k).astype(dtype)
+    d = (rng.uniform(50, 500, size=k) * (12.0 if k == 7 else 1.0)).astype(dtype)      # k = 7: sizes off the r_min clamp, as at k = 96
     th0 = np.full(A.rows, 10.0, dtype)
     ref_r = O.nb_size_update(A, W_T, H, d, th0, dtype=dtype)
     dt = _abi.F32 if dtype == np.float32 else _abi.F64
@@ -115,7 +115,7 @@ def test_nb_size_and_loss(env, dtype, tol, k):
 
 
 @pytest.mark.parametrize("dtype,tol", [(np.float64, 1e-12), (np.float32, 1e-9)])
-@pytest.mark.parametrize("k", [8, 32, 96])
+@pytest.mark.parametrize("k", [8, 32, 96, 7, 67])    # 7, 67: the element-wise gather loop (67 with a second feature per lane)
 def test_nb_size_update_loss_fused(env, dtype, tol, k):
     """rcppml_hip_nb_size_update_loss (what the fit loop runs for per-row sizes) against the two separate calls: the sizes
     bit for bit, the likelihood to the order of its fp64 sum (by row instead of by column; the terms themselves are identical),
@@ -135,7 +135,7 @@ def test_nb_size_update_loss_fused(env, dtype, tol, k):
     rng = np.random.default_rng(1)
     W_T = rng.uniform(size=(A.rows, k)).astype(dtype); W_T /= W_T.sum(axis=0, keepdims=True)
     H = rng.uniform(size=(A.cols, k)).astype(dtype); H /= H.sum(axis=0, keepdims=True)
-    d = rng.uniform(50, 500, size=k).astype(dtype)
+    d = (rng.uniform(50, 500, size=k) * (12.0 if k == 7 else 1.0)).astype(dtype)      # k = 7: sizes off the r_min clamp, as at k = 96
     th0 = np.full(A.rows, 10.0, dtype)
     dt = _abi.F32 if dtype == np.float32 else _abi.F64
     dev = lambda a: _dev(torch, a)
@@ -385,19 +385,21 @@ def test_robust_fit_through_plugin(loss_type):
 
 @pytest.mark.parametrize("dtype,tol", [(np.float64, 1e-10), (np.float32, 2e-4)])
 @pytest.mark.parametrize("loss_type,power", [(4, 0.0), (6, 0.0), (7, 0.0), (8, 1.4)])
-@pytest.mark.parametrize("mode", [2, 1])
-def test_dispersion_update(env, dtype, tol, loss_type, power, mode):
+# k = 7: the element-wise gather loop in both dtypes; 68: 16-byte loads with a second feature per lane (per-row mode only)
+@pytest.mark.parametrize("mode,k", [pytest.param(2, 8, id="2"), pytest.param(1, 8, id="1"), pytest.param(2, 7, id="2-k7"),
+                                    pytest.param(2, 68, id="2-k68")])
+def test_dispersion_update(env, dtype, tol, loss_type, power, mode, k):
     """rcppml_hip_dispersion_update: GP theta by five MM passes (fit_cpu.hpp:914-1008) and Gamma / inverse-Gaussian /
     Tweedie phi by Pearson moments (:1561-1670), PER_ROW and GLOBAL (mean / median), vs the oracle restatement.  The
     per-row sums are fp64 on both sides; the GPU's wave-tree order differs from the oracle's sequential one."""
     torch, _abi, ctx = env
     A = _nb_problem(130, 190, 3, seed=5 + loss_type)
     At = A.transpose()
-    k = 8
     rng = np.random.default_rng(loss_type)
     W_T = rng.uniform(size=(A.rows, k)).astype(dtype); W_T /= W_T.sum(axis=0, keepdims=True)
     H = rng.uniform(size=(A.cols, k)).astype(dtype); H /= H.sum(axis=0, keepdims=True)
-    d = (rng.uniform(50, 500, size=k) * (1 if loss_type == 4 else 40)).astype(dtype)     # phi: predictions of the size of the data
+    # phi: predictions of the size of the data; 8 / k keeps them there at every rank (GP theta would sit at its cap at k = 68 otherwise)
+    d = (rng.uniform(50, 500, size=k) * (1 if loss_type == 4 else 40) * (8.0 / k)).astype(dtype)
     th0 = np.full(A.rows, 0.1 if loss_type == 4 else 1.0, dtype)
     lo, hi = (0.0, 5.0) if loss_type == 4 else (1e-6, 1e4)
     ref = O.dispersion_update(loss_type, A, W_T, H, d, th0, dispersion_mode=mode, power=power, lo=lo, hi=hi, dtype=dtype)
