@@ -107,15 +107,23 @@ __global__ __launch_bounds__(WG) void spmv_csr(const int* __restrict__ tp, const
     acc = wave_sum(acc);
     if (l == 0) y[i] = acc;
 }
+// A thread adds the n terms of its row one after the other.  In float that serial sum drifts by about sqrt(n) eps, where the
+// other three products split a sum over 64 lanes first: at n = 6145 the fp32 dense fit sat 15 times further from the float64
+// restatement than the restatement's own float32 run (4 times is the suite's bound), the CSC fit of the same shape 1.5 times.  So
+// the float row is summed in double (the products are exact there) and rounded once; the double row is summed as before.  The
+// kernel is bound by its one read of A, not by these adds.
+template <class T> struct RowSum { using type = T; };
+template <> struct RowSum<float> { using type = double; };
 template <class T>
 __global__ __launch_bounds__(WG) void spmv_dense(const T* __restrict__ A, int m, int n, const T* __restrict__ v, T* __restrict__ y,
                                                  const int* st, int it, int brk) {
     if (idle(st, it) || (brk && st[brk])) return;
     const int i = blockIdx.x * WG + threadIdx.x;
     if (i >= m) return;
-    T acc = 0;
-    for (int j = 0; j < n; ++j) acc += A[(long)j * m + i] * v[j];
-    y[i] = acc;
+    using S = typename RowSum<T>::type;
+    S acc = 0;
+    for (int j = 0; j < n; ++j) acc += (S)A[(long)j * m + i] * (S)v[j];
+    y[i] = (T)acc;
 }
 
 // ------------------------------------------------------------------------------------------------------------ partials

@@ -76,7 +76,11 @@ def test_start_against_lapack(key, k, dense, precision):
 @pytest.mark.parametrize("key", list(MATS))
 def test_start_is_bitwise_the_ritz_path_transformed(key, k, dense, precision):
     """The same basis, the same sums in the same order: a condition, not a tolerance."""
-    A = MATS[key]
+    assert_start_is_the_ritz_path_transformed(MATS[key], k, dense, precision)
+
+
+def assert_start_is_the_ritz_path_transformed(A, k, dense, precision):
+    """Also what tests/test_gpu_svd_geometry.py asserts of its matrices, whose rows fill more than two blocks of nmf_start_kernel."""
     r = start(A, k, dense, precision, seed=5)
     s = _abi.svd_pca(A if dense else parts(A), k, dense=dense, precision=precision, algorithm=2, tol=1e-10, max_iter=0, seed=5)
     assert s["status"] == 0, s["error"]
