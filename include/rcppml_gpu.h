@@ -1269,6 +1269,49 @@ RCPPML_GPU_API void rcppml_gpu_cosine_dense_ex(const double* W, const double* R,
 RCPPML_GPU_API void rcppml_gpu_bipartite_match_ex(const double* cost, int* nr, int* nc, int* batch, int* out_assignment,
         double* out_cost, int* out_status);
 
+/* Panel-streamed NMF (rcppml_amd/csrc/ops_stream.hip, kernels_stream.hip.h).  Build-defined.  It replaces the
+ * reference's out-of-core fit -- nmf/fit_chunked.hpp, nmf/fit_streaming_spz.hpp and the `streaming` / `panel_cols` arguments of
+ * R/nmf_thin.R:442-610 -- with the plain ALS regrouped: the H half-update runs one column panel at a time against a fixed Gram of
+ * W, and the two sums of the W half-update, B_W = H A^T and G_H = H H^T, are accumulated over the panels.  Neither the matrix nor its
+ * transpose is resident on the device.
+ *
+ * rcppml_hip_stream_geometry (host arithmetic): out[0] = R, the rows of a row tile of rcppml_hip_stream_rhs_w (a k_pad x R
+ *   accumulator tile of 32 KiB per workgroup; a function of dtype and k only), out[1] = wavefronts per workgroup, out[2] = rows each
+ *   wavefront owns, out[3] = k_pad (8, 16, 32 or 64).  k in [1, 64].
+ * rcppml_hip_stream_rhs_w: B_W[:, r] (+)= sum over the panel's columns j of a_rj H_p[:, j], from the panel in COLUMN form (CSC of
+ *   nrows x ncols, row indices strictly increasing within a column; all device memory).  H_p: k x ncols, B_W: k x nrows, leading
+ *   dimension k.  accumulate 0: B_W is overwritten (first panel of a pass); 1: added to.  One workgroup owns a row tile and one
+ *   wavefront a fixed slice of its rows, which it accumulates in LDS walking the columns in ascending order: no atomics, and the
+ *   result does not depend on `groups` (workgroups of the launch; 0 = one per row tile), bit for bit.  k in [1, 64].
+ * rcppml_hip_stream_gram_accum: G_acc (k x k) (+)= H_p H_p^T by the MFMA partial-tile kernels of rcppml_hip_gram, the tiles added in
+ *   tile order.  rcppml_hip_stream_gram_finish: G = diag(1/d) G_acc diag(1/d) (d NULL: G_acc) + eps on the diagonal, then + l2 --
+ *   what rcppml_hip_gram(eps, l2) gives for the factor whose rows were divided by d. */
+RCPPML_GPU_API int rcppml_hip_stream_geometry(int dtype, int k, int64_t* out4);
+RCPPML_GPU_API int rcppml_hip_stream_rhs_w(rcppml_hip_ctx* ctx, int dtype, const int* col_ptr, const int* row_idx, const void* values,
+                                           int64_t ncols, int64_t nrows, const void* H_p, int k, int accumulate, int groups,
+                                           void* B_W);
+RCPPML_GPU_API int rcppml_hip_stream_gram_accum(rcppml_hip_ctx* ctx, int dtype, const void* H_p, int k, int64_t ncols, int accumulate,
+                                                void* G_acc);
+RCPPML_GPU_API int rcppml_hip_stream_gram_finish(rcppml_hip_ctx* ctx, int dtype, const void* G_acc, const void* d, int k, double eps,
+                                                 double l2, void* G);
+/* rcppml_gpu_nmf_streaming_ex: the streamed fit.  Data: a host CSC (*m x *n, rows strictly increasing within a column) with
+ * spz_path NULL, or the path of a StreamPress v2 file of that shape with col_ptr NULL: the file is parsed on the host and per panel
+ * the bytes of its chunks' streams are uploaded and decoded on the device (the whole-file decoder's kernels); row-sorted files are
+ * refused.  *panel_cols: columns per panel (.spz: rounded up to whole chunks), 0 = panels of about 64 MiB of CSC at the matrix's
+ * mean column size in whole multiples of 256 columns, no wider than a 2 GiB range table allows; capped at *n.  W (k x m), H (k x n) in / out and
+ * d (k) out as in the plain entries; L1, L2, upper_bound, nonneg: {W side, H side}; *norm_type 0 L1, 1 L2, 2 none; *solver_mode 0 CD,
+ * 1 Cholesky + clip; *precision 0 fp32, 1 fp64; *devices (may be NULL) must be <= 1.  MSE loss only; the convergence rule, the
+ * scaling and sort_model are the plain fit's.  loss_history: *max_iter doubles, may be NULL.  out_info (5): {panels, columns of
+ * the widest panel, panel_bytes_peak = the bytes of the panel buffer, device-op calls per iteration (not kernel launches: an op
+ * launches one to four), bytes of the range table of rcppml_hip_stream_rhs_w}.
+ * Refused (*out_status = -1, reason in rcppml_gpu_last_error, no output written): a null pointer, k > 64, a panel width whose range table would pass 2 GiB, an
+ * unreadable, malformed or row-sorted .spz file, more than one device, a malformed CSC, a non-finite value, not enough free device memory, no HIP device. */
+RCPPML_GPU_API void rcppml_gpu_nmf_streaming_ex(const int* col_ptr, const int* row_idx, const double* values, int* nnz,
+        const char* spz_path, int* m, int* n, int* k, int* panel_cols, double* W, double* H, double* d, int* max_iter, double* tol,
+        const double* L1, const double* L2, const double* upper_bound, const int* nonneg, int* norm_type, int* solver_mode,
+        int* cd_maxit, double* cd_tol, int* patience, int* sort_model, int* precision, int* devices, double* loss_history,
+        int* out_iter, int* out_converged, double* out_loss, double* out_tol, int64_t* out_info, int* out_status);
+
 #ifdef __cplusplus
 }
 #endif

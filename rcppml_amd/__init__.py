@@ -24,6 +24,8 @@ Layout (only what the path needs):
   factor_net.py factor_input() / nmf_layer() / svd_layer() / factor_shared() / factor_concat() / factor_add() / factor_condition() /
              factor_net() / fit() / predict(): mirror of the R factor-graph surface; multi-layer graphs run the reference's deep fit
              resident on the device (csrc/ops_graph.hip)
+  streaming.py nmf_streaming(): the plain MSE fit with the matrix streamed through the device one column panel at a time
+             (csrc/ops_stream.hip); neither the matrix nor its transpose is resident
   als.py     one-process-per-GPU column-sharded ALS loop over torch.distributed (RCCL): Comm, ShardedALS, HipOps
   data.py    synthetic inputs (restatement of R/simulateNMF.R) and CSC helpers
 """
@@ -33,3 +35,4 @@ __version__ = "0.1.0"
 from .refine import compute_target, refine  # noqa: E402,F401
 from .classify import classify_cv, classify_embedding, classify_logistic  # noqa: E402,F401
 from .similarity import align, bipartiteMatch, cosine  # noqa: E402,F401
+from .streaming import nmf_streaming  # noqa: E402,F401

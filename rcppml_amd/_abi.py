@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_classify_metrics_ex", "rcppml_gpu_classify_knn_ex", "rcppml_gpu_classify_logistic_ex",
     "rcppml_hip_graph_assemble", "rcppml_hip_graph_layer_loss", "rcppml_gpu_factor_net_fit_ex",
     "rcppml_gpu_cosine_sparse_ex", "rcppml_gpu_cosine_geometry", "rcppml_gpu_cosine_dense_ex", "rcppml_gpu_bipartite_match_ex",
+    "rcppml_hip_stream_geometry", "rcppml_hip_stream_rhs_w", "rcppml_hip_stream_gram_accum", "rcppml_hip_stream_gram_finish",
+    "rcppml_gpu_nmf_streaming_ex",
 ]
 
 
@@ -731,6 +733,23 @@ class Context:
                                                   C.c_int64(m), C.c_int64(nnz), _dptr(W_T), _dptr(d), _dptr(H), C.c_int64(n),
                                                   C.c_int(k), C.c_double(r_min), C.c_double(r_max), _dptr(nb_size), _dptr(out)),
              "nb_size_update_loss")
+
+    # ---- panel-streamed fit (ops_stream.hip): the W-side sums of one column panel
+    def stream_rhs_w(self, dt, col_ptr, row_idx, values, ncols, nrows, H_p, k, accumulate, B_W, groups=0):
+        f = lib().rcppml_hip_stream_rhs_w
+        f.restype = C.c_int
+        _chk(f(self._h, C.c_int(dt), _dptr(col_ptr), _dptr(row_idx), _dptr(values), C.c_int64(ncols), C.c_int64(nrows), _dptr(H_p),
+               C.c_int(k), C.c_int(int(accumulate)), C.c_int(groups), _dptr(B_W)), "stream_rhs_w")
+
+    def stream_gram_accum(self, dt, H_p, k, ncols, accumulate, G_acc):
+        f = lib().rcppml_hip_stream_gram_accum
+        f.restype = C.c_int
+        _chk(f(self._h, C.c_int(dt), _dptr(H_p), C.c_int(k), C.c_int64(ncols), C.c_int(int(accumulate)), _dptr(G_acc)), "stream_gram_accum")
+
+    def stream_gram_finish(self, dt, G_acc, d, k, eps, l2, G):
+        f = lib().rcppml_hip_stream_gram_finish
+        f.restype = C.c_int
+        _chk(f(self._h, C.c_int(dt), _dptr(G_acc), _dptr(d), C.c_int(k), C.c_double(eps), C.c_double(l2), _dptr(G)), "stream_gram_finish")
 
     def nb_loss(self, dt, col_ptr, row_idx, values, ncols, W_T, d, H, theta_row, k, out):
         _chk(lib().rcppml_hip_nb_loss(self._h, C.c_int(dt), _dptr(col_ptr), _dptr(row_idx), _dptr(values), C.c_int64(ncols),
@@ -1756,4 +1775,43 @@ def bipartite_match(cost, *, nr=None, nc=None, batch=None, init=-7):
     r = dict(status=st.value, error=last_error() if st.value else "", buffers=(asg, tot))
     if st.value == 0:
         r.update(assignment=asg[0] if single else asg, cost=float(tot[0]) if single else tot)
+    return r
+
+
+# ----------------------------------------------------------------------------- panel-streamed NMF (ops_stream.hip)
+def stream_geometry(dt, k):
+    """rcppml_hip_stream_geometry: dict(tile_rows, waves, wave_rows, k_pad) of stream_rhs_w for this precision and rank."""
+    out = (C.c_int64 * 4)()
+    f = lib().rcppml_hip_stream_geometry
+    f.restype = C.c_int
+    _chk(f(C.c_int(dt), C.c_int(k), out), "stream_geometry")
+    return dict(zip(("tile_rows", "waves", "wave_rows", "k_pad"), (int(v) for v in out)))
+
+
+def nmf_streaming(csc, spz_path, m, n, k, W_T, H, *, panel_cols=0, max_iter=100, tol=1e-4, L1=(0.0, 0.0), L2=(0.0, 0.0),
+                  upper_bound=(0.0, 0.0), nonneg=(1, 1), norm_type=0, solver_mode=0, cd_maxit=100, cd_tol=1e-8, patience=5,
+                  sort_model=1, precision=F64, devices=1):
+    """rcppml_gpu_nmf_streaming_ex.  csc: (p, i, x) host arrays or None; spz_path: a path or None.  W_T (m, k) and H (n, k) float64
+    C-contiguous, updated in place on success only; the pairs are (W side, H side).  Returns dict(status, error, d, iter, converged,
+    loss, tol, loss_history, panels, panel_cols, panel_bytes_peak, ops_per_iter, range_table_bytes)."""
+    keep = _csc_args(*csc) if csc is not None else ()
+    head = [_np_ptr(keep[0]), _np_ptr(keep[1]), _np_ptr(keep[2]), _ci(keep[2].shape[0])] if csc is not None else [None, None, None, _ci(0)]
+    pairs = [np.asarray(v, np.float64) for v in (L1, L2, upper_bound)]
+    nn = np.asarray(nonneg, np.int32)
+    d = np.ones(max(int(k), 1))
+    hist = np.full(max(int(max_iter), 1), np.nan)
+    info = (C.c_int64 * 5)()
+    it, conv, st = C.c_int(0), C.c_int(0), C.c_int(-99)
+    loss, otol = C.c_double(0), C.c_double(0)
+    lib().rcppml_gpu_nmf_streaming_ex(*head, C.c_char_p(os.fsencode(spz_path)) if spz_path is not None else None, _ci(m), _ci(n), _ci(k),
+                                      _ci(panel_cols), _np_ptr(W_T), _np_ptr(H), _np_ptr(d), _ci(max_iter), _cd(tol), _np_ptr(pairs[0]),
+                                      _np_ptr(pairs[1]), _np_ptr(pairs[2]), _np_ptr(nn), _ci(norm_type), _ci(solver_mode), _ci(cd_maxit),
+                                      _cd(cd_tol), _ci(patience), _ci(sort_model), _ci(precision), _ci(devices), _np_ptr(hist),
+                                      C.byref(it), C.byref(conv), C.byref(loss), C.byref(otol), info, C.byref(st))
+    del keep
+    r = dict(status=st.value, error=last_error() if st.value else "")
+    if st.value == 0:
+        r.update(d=d, iter=it.value, converged=bool(conv.value), loss=loss.value, tol=otol.value, loss_history=hist[:it.value].copy(),
+                 panels=int(info[0]), panel_cols=int(info[1]), panel_bytes_peak=int(info[2]), ops_per_iter=int(info[3]),
+                 range_table_bytes=int(info[4]))
     return r

@@ -261,6 +261,52 @@ void decode_to_device(rcppml_hip_ctx* c, const uint8_t* data, uint64_t size, con
 
 }  // namespace
 
+// Columns [col0, col1) of a parsed file -- whole chunks: both are chunk boundaries -- into caller-allocated device arrays, the column
+// pointers rebased to the range's first nonzero (the panel decode of the streamed fit, ops_stream.hip).  Only the bytes that hold the
+// range's streams are uploaded.  check_rows_below > 0: throws unless every decoded row index lies in [0, check_rows_below).
+// Files with a stored row permutation are the caller's to refuse (P.row_perm is not applied here).
+void rcppml_spz_decode_columns(rcppml_hip_ctx* c, const uint8_t* data, const SpzParsed& P, int64_t col0, int64_t col1, int* d_col_ptr,
+                               int* d_row_idx, double* d_values, int check_rows_below) {
+    const uint64_t o0 = (uint32_t)P.col_ptr[col0], o1 = (uint32_t)P.col_ptr[col1];
+    SpzParsed Q;
+    Q.h = P.h;
+    Q.h.n = (uint32_t)(col1 - col0);
+    Q.h.nnz = o1 - o0;
+    Q.bpv = P.bpv;
+    Q.col_ptr.resize((size_t)Q.h.n + 1);
+    Q.seg_ptr.resize((size_t)Q.h.n + 1);
+    for (int64_t j = col0; j <= col1; ++j) {
+        Q.col_ptr[(size_t)(j - col0)] = (int)((uint32_t)P.col_ptr[j] - o0);
+        Q.seg_ptr[(size_t)(j - col0)] = (int)(std::min<uint64_t>(std::max<uint64_t>((uint32_t)P.seg_ptr[j], o0), o1) - o0);
+    }
+    uint64_t lo = UINT64_MAX, hi = 0;
+    for (const SpzJob& j : P.jobs) {
+        if (j.out_off < o0 || j.out_off >= o1) continue;
+        if (j.out_off + j.count > o1) throw std::runtime_error("spz: a stream crosses the panel boundary (not a chunk boundary)");
+        Q.jobs.push_back(j);
+        lo = std::min(lo, j.table_off);
+        hi = std::max(hi, j.enc_off + j.enc_size);
+        if (j.ov_size > 0) hi = std::max(hi, j.ov_off + j.ov_size);
+    }
+    if (Q.jobs.empty()) lo = hi = 0;
+    for (SpzJob& j : Q.jobs) {
+        j.out_off -= o0; j.table_off -= lo; j.enc_off -= lo;
+        if (j.ov_size > 0) j.ov_off -= lo;
+    }
+    decode_to_device(c, data + lo, hi - lo, Q, d_col_ptr, d_row_idx, d_values);
+    if (check_rows_below > 0 && Q.h.nnz > 0) {
+        int* dbad = static_cast<int*>(c->scratch(WS_RED, sizeof(int)));
+        HIPCHK(hipMemsetAsync(dbad, 0, sizeof(int), c->stream));
+        hipLaunchKernelGGL(spz_check_rows_kernel, dim3((unsigned)((Q.h.nnz + 255) / 256)), dim3(256), 0, c->stream, (const int*)d_row_idx,
+                           (int64_t)Q.h.nnz, check_rows_below, dbad);
+        HIPCHK(hipGetLastError());
+        int bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, dbad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (bad) throw std::runtime_error("spz: a decoded row index lies outside the matrix");
+    }
+}
+
 extern "C" int rcppml_hip_spz_info(const void* file_bytes, uint64_t size, int* m, int* n, int64_t* nnz, int* value_type) {
     try {
         SpzHeader h;
