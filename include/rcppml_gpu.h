@@ -1244,6 +1244,16 @@ RCPPML_GPU_API void rcppml_gpu_factor_net_fit_ex(const int* col_ptr, const int* 
  * own excluded.  out_ms (2 doubles, may be NULL): device time from the end of the upload to the last kernel, and the time of the
  * download of C, in milliseconds.  Device memory: 8 nx ny for C, three times the CSC of X, the CSC of Y, 4 m (ceil(nx / T) + 1).
  *
+ * rcppml_gpu_cosine_knn_sparse_ex: the *k best columns of X for every column of Y, without C.  The matrix arguments, *groups,
+ * out_launches and out_status are those of rcppml_gpu_cosine_sparse_ex, and every value ranked is, bit for bit, the C[i, j] that
+ * entry stores.  out_idx (int) and out_val (double) are *k x *ny with the rank running fastest: out_idx[r + *k * j] is the 0-based
+ * column of X of rank r for column j of Y, out_val its cosine.  The order is total: larger value first, equal values (+0 and -0
+ * are equal) by smaller column index, so the result depends on the data alone.  Zeros are neighbours like any other value: a column
+ * with fewer than *k non-zero cosines is filled up with zero-valued columns in ascending index order.  *include_self is read only
+ * when y_col_ptr is NULL: 0 keeps column j of X out of the list of column j.  Refused as well: *k < 1, *k > 64, *k above the
+ * eligible columns (*nx, or *nx - 1 when self is excluded).  out_ms[1] is the download of the two result arrays.  Device memory:
+ * three times the CSC of X, the CSC of Y, 4 m (ceil(nx / T) + 1), the norms and 12 k ny for the result -- no term in nx ny.
+ *
  * rcppml_gpu_cosine_geometry: out[0] = T, the columns of X one wavefront keeps in LDS at a time; out[1] = the wavefronts of a
  * workgroup; out[2] = the workgroups of the default launch before it is capped by the work (one per CU; 0 without a device).
  * Returns 0 (-1 for a null pointer); needs no device for out[0] and out[1].
@@ -1263,6 +1273,9 @@ RCPPML_GPU_API void rcppml_gpu_factor_net_fit_ex(const int* col_ptr, const int* 
 RCPPML_GPU_API void rcppml_gpu_cosine_sparse_ex(const int* x_col_ptr, const int* x_row_idx, const double* x_values, int* x_nnz,
         const int* y_col_ptr, const int* y_row_idx, const double* y_values, int* y_nnz, int* m, int* nx, int* ny, int* groups,
         double* out_C, int* out_launches, double* out_ms, int* out_status);
+RCPPML_GPU_API void rcppml_gpu_cosine_knn_sparse_ex(const int* x_col_ptr, const int* x_row_idx, const double* x_values, int* x_nnz,
+        const int* y_col_ptr, const int* y_row_idx, const double* y_values, int* y_nnz, int* m, int* nx, int* ny, int* k,
+        int* include_self, int* groups, int* out_idx, double* out_val, int* out_launches, double* out_ms, int* out_status);
 RCPPML_GPU_API int rcppml_gpu_cosine_geometry(int64_t* out);
 RCPPML_GPU_API void rcppml_gpu_cosine_dense_ex(const double* W, const double* R, int* m, int* kx, int* ky, int* reps, int* method,
         double* out, int* out_launches, int* out_status);

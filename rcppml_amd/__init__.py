@@ -20,7 +20,8 @@ Layout (only what the path needs):
              sparse column cosines (rcppml_gpu_cosine_sparse_ex, tile geometry from rcppml_gpu_cosine_geometry), batched dense
              cosines / correlations (rcppml_gpu_cosine_dense_ex) and the host assignment solver (rcppml_gpu_bipartite_match_ex).  A
              zero-norm column has similarity 0 to every column; two deviations from R (cosine(vector, matrix) returns the cosine,
-             align() applies the inverse of the matching), see the module docstring
+             align() applies the inverse of the matching), see the module docstring; and, build-defined, cosine_knn() (the k best
+             columns without the full matrix, rcppml_gpu_cosine_knn_sparse_ex) and knn_graph() (the graph Laplacian nmf(graph_H=) takes)
   factor_net.py factor_input() / nmf_layer() / svd_layer() / factor_shared() / factor_concat() / factor_add() / factor_condition() /
              factor_net() / fit() / predict(): mirror of the R factor-graph surface; multi-layer graphs run the reference's deep fit
              resident on the device (csrc/ops_graph.hip)
@@ -34,5 +35,5 @@ __version__ = "0.1.0"
 # the package attribute `refine` is the function from here on; the module's other names come with `from rcppml_amd.refine import ...`
 from .refine import compute_target, refine  # noqa: E402,F401
 from .classify import classify_cv, classify_embedding, classify_logistic  # noqa: E402,F401
-from .similarity import align, bipartiteMatch, cosine  # noqa: E402,F401
+from .similarity import align, bipartiteMatch, cosine, cosine_knn, knn_graph  # noqa: E402,F401
 from .streaming import nmf_streaming  # noqa: E402,F401

@@ -59,7 +59,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_nmf_zi_double", "rcppml_gpu_zi_em_double",
     "rcppml_gpu_classify_metrics_ex", "rcppml_gpu_classify_knn_ex", "rcppml_gpu_classify_logistic_ex",
     "rcppml_hip_graph_assemble", "rcppml_hip_graph_layer_loss", "rcppml_gpu_factor_net_fit_ex",
-    "rcppml_gpu_cosine_sparse_ex", "rcppml_gpu_cosine_geometry", "rcppml_gpu_cosine_dense_ex", "rcppml_gpu_bipartite_match_ex",
+    "rcppml_gpu_cosine_sparse_ex", "rcppml_gpu_cosine_knn_sparse_ex", "rcppml_gpu_cosine_geometry", "rcppml_gpu_cosine_dense_ex", "rcppml_gpu_bipartite_match_ex",
     "rcppml_hip_stream_geometry", "rcppml_hip_stream_rhs_w", "rcppml_hip_stream_gram_accum", "rcppml_hip_stream_gram_finish",
     "rcppml_gpu_nmf_streaming_ex",
 ]
@@ -1734,6 +1734,28 @@ def cosine_sparse(x, y=None, *, m=None, nx=None, ny=None, groups=0, init=-7.0, o
     r = dict(status=st.value, error=last_error() if st.value else "", buffers=(out,))
     if st.value == 0:
         r.update(C=out, launches=launches.value, device_ms=ms[0], download_ms=ms[1])
+    return r
+
+
+def cosine_knn_sparse(x, y=None, k=10, include_self=False, *, m=None, nx=None, ny=None, groups=0, init=-7):
+    """rcppml_gpu_cosine_knn_sparse_ex.  x, y, m, nx, ny, groups as cosine_sparse; k None passes a null pointer (a test of the
+    refusals).  Returns dict(status, error, idx (ny, k) int32 and val (ny, k), best first, launches, device_ms, download_ms, buffers
+    (the two output arrays, filled with `init` before the call)); a refused call leaves them as they were."""
+    m = x.shape[0] if m is None else m
+    nx = x.shape[1] if nx is None else nx
+    ny = (nx if y is None else y.shape[1]) if ny is None else ny
+    hx, keep_x = _csc_ptrs(x)
+    hy, keep_y = _csc_ptrs(y) if y is not None else ([None, None, None, None], ())
+    shape = (max(int(ny), 1), min(max(int(k or 1), 1), 64))          # rank fastest
+    idx, val = np.full(shape, int(init), np.int32), np.full(shape, float(init))
+    launches, st = C.c_int(0), C.c_int(-99)
+    ms = (C.c_double * 2)(0.0, 0.0)
+    lib().rcppml_gpu_cosine_knn_sparse_ex(*hx, *hy, _ci(m), _ci(nx), _ci(ny), None if k is None else _ci(k), _ci(bool(include_self)),
+                                          _ci(groups), _np_ptr(idx), _np_ptr(val), C.byref(launches), ms, C.byref(st))
+    del keep_x, keep_y
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=(idx, val))
+    if st.value == 0:
+        r.update(idx=idx, val=val, launches=launches.value, device_ms=ms[0], download_ms=ms[1])
     return r
 
 

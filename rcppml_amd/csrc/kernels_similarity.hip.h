@@ -13,6 +13,9 @@
 //                        Every C[i, j] belongs to one item, items are dealt to wavefronts round-robin, and the order inside an item
 //                        is fixed, so the result does not depend on the number of workgroups.
 // With Y = X, C[i, j] and C[j, i] are the same chain: the same rows in the same order, products and the norm product commuted.
+//   cosine_knn_kernel    the k <= 64 best columns of X for every column of Y without C: one wavefront owns a column j and walks the
+//                        tiles in order, each built by the same tile_dots / tile_cosine as above (the same bits), and keeps a
+//                        sorted list of (value, index) pairs across its lanes, ordered by larger value, then smaller index
 //
 // Dense: reps matrices W_q (m x kx) against one R (m x ky), all column-major, kx, ky <= DK.
 //   dense_stats_kernel   one wavefront per column: lane l adds rows l, l + 64, ..., then a butterfly over the 64 partials; the mean
@@ -71,6 +74,42 @@ __global__ __launch_bounds__(256) void tile_offsets_kernel(const int* __restrict
     ts[idx] = lo;
 }
 
+// One (column j of Y, tile of tw columns of X from column i0) of the sparse product, shared by the full and the kNN kernel: a[c] =
+// <x_(i0 + c), y_j> for c in [0, tw), summed in the storage order of y_j.  ts0 / ts1: the offset rows of this tile and the next.
+__device__ __forceinline__ void tile_dots(double* a, int lane, int tw, int i0, const int* __restrict__ ts0,
+                                          const int* __restrict__ ts1, const int* __restrict__ yi, const double* __restrict__ yx,
+                                          int e0, int e1, const int* __restrict__ ti, const double* __restrict__ tx) {
+    for (int q = lane; q < tw; q += 64) a[q] = 0.0;
+    wave_sync();
+    for (int eb = e0; eb < e1; eb += 64) {
+        // 64 stored entries of y_j and their row segments, one per lane; then row after row, in storage order
+        const int cnt = e1 - eb < 64 ? e1 - eb : 64;
+        int s = 0, en = 0;
+        double v = 0.0;
+        if (lane < cnt) {
+            const int r = yi[eb + lane];
+            v = yx[eb + lane];
+            s = ts0[r];
+            en = ts1[r];
+        }
+        for (int k = 0; k < cnt; ++k) {
+            const int sk = __shfl(s, k), ek = __shfl(en, k);
+            const double vk = __shfl(v, k);
+            for (int q = sk + lane; q < ek; q += 64) {
+                const int c = ti[q] - i0;          // in [0, tw) by the construction of ts
+                a[c] = add_rn(a[c], mul_rn(vk, tx[q]));
+            }
+            wave_sync();
+        }
+    }
+}
+
+// dot / (|x_i| * |y_j|), 0 where a norm is 0
+__device__ __forceinline__ double tile_cosine(double dot, double norm_xi, double norm_yj) {
+    const double den = mul_rn(norm_xi, norm_yj);
+    return den > 0.0 ? dot / den : 0.0;
+}
+
 __global__ __launch_bounds__(NT) void cosine_tile_kernel(const int* __restrict__ yp, const int* __restrict__ yi,
                                                          const double* __restrict__ yx, const int* __restrict__ ts,
                                                          const int* __restrict__ ti, const double* __restrict__ tx,
@@ -86,39 +125,102 @@ __global__ __launch_bounds__(NT) void cosine_tile_kernel(const int* __restrict__
         const int64_t j = it - (int64_t)t * ny;
         const int64_t i0 = (int64_t)t * T;
         const int tw = (int)(nx - i0 < T ? nx - i0 : T);
-        for (int q = lane; q < tw; q += 64) a[q] = 0.0;
-        wave_sync();
         const int* ts0 = ts + (int64_t)t * m;
-        const int* ts1 = ts0 + m;
-        const int e1 = yp[j + 1];
-        for (int eb = yp[j]; eb < e1; eb += 64) {
-            // 64 stored entries of y_j and their row segments, one per lane; then row after row, in storage order
-            const int cnt = e1 - eb < 64 ? e1 - eb : 64;
-            int s = 0, en = 0;
-            double v = 0.0;
-            if (lane < cnt) {
-                const int r = yi[eb + lane];
-                v = yx[eb + lane];
-                s = ts0[r];
-                en = ts1[r];
-            }
-            for (int k = 0; k < cnt; ++k) {
-                const int sk = __shfl(s, k), ek = __shfl(en, k);
-                const double vk = __shfl(v, k);
-                for (int q = sk + lane; q < ek; q += 64) {
-                    const int c = ti[q] - (int)i0;          // in [0, tw) by the construction of ts
-                    a[c] = add_rn(a[c], mul_rn(vk, tx[q]));
-                }
-                wave_sync();
-            }
-        }
+        tile_dots(a, lane, tw, (int)i0, ts0, ts0 + m, yi, yx, yp[j], yp[j + 1], ti, tx);
         const double nj = norm_y[j];
         double* out = C + j * nx + i0;
-        for (int q = lane; q < tw; q += 64) {
-            const double den = mul_rn(norm_x[i0 + q], nj);
-            out[q] = den > 0.0 ? a[q] / den : 0.0;
-        }
+        for (int q = lane; q < tw; q += 64) out[q] = tile_cosine(a[q], norm_x[i0 + q], nj);
         wave_sync();
+    }
+}
+
+// ---- kNN form: the k best columns of X for every column of Y, selected from the tiles while they are still in LDS ----------------
+// The total order of a neighbour list: larger value first, then smaller column index.  NO_PAIR (value -inf) ranks after every pair
+// and a NaN (the mark of a slot that is taken or not eligible) before none, so neither is ever a candidate.
+constexpr int KNN_MAX = 64;
+constexpr int NO_PAIR = 0x7fffffff;
+__device__ __forceinline__ bool ranks_before(double va, int ia, double vb, int ib) { return va > vb || (va == vb && ia < ib); }
+
+// the best of this lane's slots (lane, lane + 64, ...: conflict-free) that ranks before the k-th pair (tv, tidx), or NO_PAIR
+__device__ __forceinline__ void lane_best(const double* a, int lane, int tw, int i0, double tv, int tidx, double& cv, int& ci) {
+    cv = -__builtin_inf();
+    ci = NO_PAIR;
+    for (int q = lane; q < tw; q += 64) {
+        const double v = a[q];
+        if (ranks_before(v, i0 + q, tv, tidx) && v > cv) { cv = v; ci = i0 + q; }          // ascending q: ties keep the lower index
+    }
+}
+
+// One wavefront owns column j of Y and walks the tiles of X in ascending order; consecutive j go to the wavefronts of a workgroup,
+// so the wavefronts in flight read the same tile of X^T.  Lane r keeps the pair of rank r in registers (all 64 ranks are kept,
+// the first k are the result).  Per tile: tile_dots, then the cosines in place -- tile_cosine on every slot that received a
+// product; a slot that received none holds +0 and tile_cosine(+0, ., .) is +0 whatever the norms, so its norm is not read -- then
+// rounds of { butterfly for the best candidate of the 64 lanes, insertion by one compare per lane and a shift by one lane, the
+// winner's slot marked, its lane rescans } until no lane holds a candidate.  Every round's winner ranks before the k-th pair, so a
+// tile takes at most k rounds.  The result is a function of the data alone: the values are those of cosine_tile_kernel bit for
+// bit, and the order is total.
+__global__ __launch_bounds__(NT) void cosine_knn_kernel(const int* __restrict__ yp, const int* __restrict__ yi,
+                                                        const double* __restrict__ yx, const int* __restrict__ ts,
+                                                        const int* __restrict__ ti, const double* __restrict__ tx,
+                                                        const double* __restrict__ norm_x, const double* __restrict__ norm_y,
+                                                        int64_t m, int64_t nx, int64_t ny, int ntiles, int k, int skip_self,
+                                                        int* __restrict__ out_idx, double* __restrict__ out_val) {
+    __shared__ double acc[WAVES][T];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    double* a = acc[w];
+    const double taken = __builtin_nan("");
+    for (int64_t j = (int64_t)blockIdx.x * WAVES + w; j < ny; j += (int64_t)gridDim.x * WAVES) {
+        double lv = -__builtin_inf(), tv = lv;          // lane's pair of the list; the k-th pair
+        int li = NO_PAIR, tidx = NO_PAIR;
+        const double nj = norm_y[j];
+        const int e0 = yp[j], e1 = yp[j + 1];
+        for (int t = 0; t < ntiles; ++t) {
+            const int i0 = t * T;
+            const int tw = (int)(nx - i0 < T ? nx - i0 : T);
+            const int* ts0 = ts + (int64_t)t * m;
+            tile_dots(a, lane, tw, i0, ts0, ts0 + m, yi, yx, e0, e1, ti, tx);
+            for (int q = lane; q < tw; q += 64) {
+                const double d = a[q];
+                if (skip_self && i0 + q == j) a[q] = taken;
+                else if (d != 0.0) a[q] = tile_cosine(d, norm_x[i0 + q], nj);
+            }
+            double cv;
+            int ci;
+            lane_best(a, lane, tw, i0, tv, tidx, cv, ci);
+            for (;;) {
+                double wv = cv;
+                int wi = ci;
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) {
+                    const double ov = __shfl_xor(wv, off);
+                    const int oi = __shfl_xor(wi, off);
+                    if (ranks_before(ov, oi, wv, wi)) { wv = ov; wi = oi; }
+                }
+                if (wi == NO_PAIR) break;          // the same in every lane
+                const int after = ranks_before(wv, wi, lv, li);          // the winner goes in front of this lane's pair
+                const double uv = __shfl_up(lv, 1);
+                const int ui = __shfl_up(li, 1);
+                const int up_after = __shfl_up(after, 1) && lane > 0;
+                if (after) {
+                    lv = up_after ? uv : wv;
+                    li = up_after ? ui : wi;
+                }
+                tv = __shfl(lv, k - 1);
+                tidx = __shfl(li, k - 1);
+                if (ci == wi) {
+                    a[wi - i0] = taken;
+                    lane_best(a, lane, tw, i0, tv, tidx, cv, ci);
+                } else if (!ranks_before(cv, ci, tv, tidx)) {
+                    cv = -__builtin_inf();
+                    ci = NO_PAIR;
+                }
+            }
+            wave_sync();
+        }
+        if (lane < k) {
+            out_idx[j * k + lane] = li;
+            out_val[j * k + lane] = lv;
+        }
     }
 }
 

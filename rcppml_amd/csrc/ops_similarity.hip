@@ -112,69 +112,108 @@ extern "C" int rcppml_gpu_cosine_geometry(int64_t* out) {
     return 0;
 }
 
+namespace {
+
+// The two sparse entries (full matrix and kNN) up to their main kernel: the checked arguments, then on the device the uploads, X^T by
+// rows, the column norms and the tile offsets.
+struct SparsePair {
+    bool self = false;
+    int64_t M = 0, NX = 0, NY = 0, ntiles = 0;
+    Csc X{}, Y{};
+    DevCsc dX, dY;
+    DevBuf Tp, Ti, Tx, Ts, Nx, Ny;
+    int* ts = nullptr;
+    double *nrmx = nullptr, *nrmy = nullptr;
+    int launches = 0;
+
+    void read(const int* xp, const int* xi, const double* xv, const int* x_nnz, const int* yp, const int* yi, const double* yv,
+              const int* y_nnz, const int* m, const int* nx, const int* ny, const int* groups) {
+        if (!m || !nx) throw std::invalid_argument("null scalar argument");
+        self = yp == nullptr;
+        if (!self && !ny) throw std::invalid_argument("null scalar argument");
+        M = *m, NX = *nx, NY = self ? NX : *ny;
+        if (M < 1 || NX < 1 || NY < 1) throw std::invalid_argument("m, nx and ny must be >= 1");
+        if (groups && *groups < 0) throw std::invalid_argument("groups must be >= 0");
+        X = read_csc(xp, xi, xv, x_nnz, M, NX, "x");
+        Y = self ? X : read_csc(yp, yi, yv, y_nnz, M, NY, "y");
+        ntiles = (NX + T - 1) / T;
+    }
+    // the CSC of X and of X^T (and the transpose's scratch, about as much again), the CSC of Y, the offset table, the norms
+    size_t bytes() const {
+        return 3 * X.bytes() + ((size_t)M + 1) * 4 + (self ? 0 : Y.bytes()) + (size_t)(ntiles + 1) * (size_t)M * 4 +
+               (size_t)(NX + NY) * 8 + std::min<size_t>((size_t)256 << 20, (size_t)2048 * (size_t)M) + (1 << 20);
+    }
+    void upload_to(hipStream_t s) {
+        dX.upload_from(X, s);
+        if (!self) dY.upload_from(Y, s);
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    const DevCsc& y() const { return self ? dX : dY; }
+    // X with no stored entry has no transpose to build: every segment of the offset table is empty
+    void prepare(CtxGuard& g) {
+        const int64_t nts = (ntiles + 1) * M;
+        dalloc<int>(Tp, (size_t)M + 1);
+        dalloc<int>(Ti, (size_t)X.nnz);
+        dalloc<double>(Tx, (size_t)X.nnz);
+        ts = dalloc<int>(Ts, (size_t)nts);
+        if (X.nnz > 0)
+            OPCHK(rcppml_hip_transpose_csc(g.c, RCPPML_F64, (int)M, (int)NX, dX.p.as<int>(), dX.i.as<int>(), dX.x.p, Tp.as<int>(),
+                                           Ti.as<int>(), Tx.p));
+        nrmx = dalloc<double>(Nx, (size_t)NX);
+        nrmy = nrmx;
+        hipLaunchKernelGGL(col_norm_kernel, dim3((unsigned)((NX + 255) / 256)), dim3(256), 0, g.s, dX.p.as<int>(),
+                           dX.x.as<double>(), NX, nrmx);
+        ++launches;
+        if (!self) {
+            nrmy = dalloc<double>(Ny, (size_t)NY);
+            hipLaunchKernelGGL(col_norm_kernel, dim3((unsigned)((NY + 255) / 256)), dim3(256), 0, g.s, dY.p.as<int>(),
+                               dY.x.as<double>(), NY, nrmy);
+            ++launches;
+        }
+        if (X.nnz > 0) {
+            hipLaunchKernelGGL(tile_offsets_kernel, dim3((unsigned)((nts + 255) / 256)), dim3(256), 0, g.s, Tp.as<int>(), Ti.as<int>(), M,
+                               (int)ntiles, ts);
+            ++launches;
+        } else {
+            HIPCHK(hipMemsetAsync(ts, 0, (size_t)nts * 4, g.s));
+        }
+        HIPCHK(hipGetLastError());
+    }
+    // workgroups of the main kernel for `most` workgroups' worth of work
+    unsigned grid(const CtxGuard& g, const int* groups, int64_t most) const {
+        const int64_t want = (groups && *groups > 0) ? *groups : std::max(1, g.c->num_cu);
+        return (unsigned)std::max<int64_t>(1, std::min(want, most));
+    }
+};
+
+}  // namespace
+
 extern "C" void rcppml_gpu_cosine_sparse_ex(const int* x_col_ptr, const int* x_row_idx, const double* x_values, int* x_nnz,
                                             const int* y_col_ptr, const int* y_row_idx, const double* y_values, int* y_nnz, int* m,
                                             int* nx, int* ny, int* groups, double* out_C, int* out_launches, double* out_ms,
                                             int* out_status) {
     entry_guard(out_status, [&] {
-        if (!m || !nx) throw std::invalid_argument("null scalar argument");
-        const bool self = y_col_ptr == nullptr;
-        if (!self && !ny) throw std::invalid_argument("null scalar argument");
-        const int64_t M = *m, NX = *nx, NY = self ? NX : *ny;
-        if (M < 1 || NX < 1 || NY < 1) throw std::invalid_argument("m, nx and ny must be >= 1");
-        if (groups && *groups < 0) throw std::invalid_argument("groups must be >= 0");
+        SparsePair P;
         if (!out_C) throw std::invalid_argument("null out_C");
-        const Csc X = read_csc(x_col_ptr, x_row_idx, x_values, x_nnz, M, NX, "x");
-        const Csc Y = self ? X : read_csc(y_col_ptr, y_row_idx, y_values, y_nnz, M, NY, "y");
-        const int64_t ntiles = (NX + T - 1) / T;
-        const size_t nC = (size_t)NX * (size_t)NY;
-        if ((double)NX * (double)NY * 8.0 > 9.0e18) throw std::invalid_argument("the result does not fit in memory");
-        // C, the CSC of X and of X^T (and the transpose's scratch, about as much again), the CSC of Y, the offset table, the norms
-        const size_t need = 8 * nC + 3 * X.bytes() + ((size_t)M + 1) * 4 + (self ? 0 : Y.bytes()) +
-                            (size_t)(ntiles + 1) * (size_t)M * 4 + (size_t)(NX + NY) * 8 + std::min<size_t>((size_t)256 << 20, (size_t)2048 * (size_t)M) + (1 << 20);
-        device_ready(need, "the cosine matrix");
+        P.read(x_col_ptr, x_row_idx, x_values, x_nnz, y_col_ptr, y_row_idx, y_values, y_nnz, m, nx, ny, groups);
+        const size_t nC = (size_t)P.NX * (size_t)P.NY;
+        if ((double)P.NX * (double)P.NY * 8.0 > 9.0e18) throw std::invalid_argument("the result does not fit in memory");
+        device_ready(8 * nC + P.bytes(), "the cosine matrix");
         CtxGuard g(env_device());
         Events ev;
-        DevCsc dX, dY;
-        DevBuf Tp, Ti, Tx, Ts, Nx, Ny, dC;
-        dX.upload_from(X, g.s);
-        if (!self) dY.upload_from(Y, g.s);
-        HIPCHK(hipStreamSynchronize(g.s));
+        DevBuf dC;
+        P.upload_to(g.s);
         HIPCHK(hipEventRecord(ev.a, g.s));
         double* C = dalloc<double>(dC, nC);
-        int launches = 0;
-        if (X.nnz == 0 || Y.nnz == 0) {
+        if (P.X.nnz == 0 || P.Y.nnz == 0) {
             HIPCHK(hipMemsetAsync(C, 0, nC * 8, g.s));      // every column of one side has zero norm
         } else {
-            dalloc<int>(Tp, (size_t)M + 1);
-            dalloc<int>(Ti, (size_t)X.nnz);
-            dalloc<double>(Tx, (size_t)X.nnz);
-            OPCHK(rcppml_hip_transpose_csc(g.c, RCPPML_F64, (int)M, (int)NX, dX.p.as<int>(), dX.i.as<int>(), dX.x.p, Tp.as<int>(),
-                                           Ti.as<int>(), Tx.p));
-            double* nrmx = dalloc<double>(Nx, (size_t)NX);
-            double* nrmy = nrmx;
-            hipLaunchKernelGGL(col_norm_kernel, dim3((unsigned)((NX + 255) / 256)), dim3(256), 0, g.s, dX.p.as<int>(),
-                               dX.x.as<double>(), NX, nrmx);
-            ++launches;
-            if (!self) {
-                nrmy = dalloc<double>(Ny, (size_t)NY);
-                hipLaunchKernelGGL(col_norm_kernel, dim3((unsigned)((NY + 255) / 256)), dim3(256), 0, g.s, dY.p.as<int>(),
-                                   dY.x.as<double>(), NY, nrmy);
-                ++launches;
-            }
-            const int64_t nts = (ntiles + 1) * M;
-            int* ts = dalloc<int>(Ts, (size_t)nts);
-            hipLaunchKernelGGL(tile_offsets_kernel, dim3((unsigned)((nts + 255) / 256)), dim3(256), 0, g.s, Tp.as<int>(), Ti.as<int>(), M,
-                               (int)ntiles, ts);
-            ++launches;
-            HIPCHK(hipGetLastError());
-            const int64_t items = NY * ntiles, most = (items + WAVES - 1) / WAVES;
-            int64_t grid = (groups && *groups > 0) ? *groups : std::max(1, g.c->num_cu);
-            grid = std::max<int64_t>(1, std::min(grid, most));
-            const DevCsc& O = self ? dX : dY;
-            hipLaunchKernelGGL(cosine_tile_kernel, dim3((unsigned)grid), dim3(NT), 0, g.s, O.p.as<int>(), O.i.as<int>(),
-                               O.x.as<double>(), ts, Ti.as<int>(), Tx.as<double>(), nrmx, nrmy, M, NX, NY, (int)ntiles, C);
-            ++launches;
+            P.prepare(g);
+            const DevCsc& O = P.y();
+            hipLaunchKernelGGL(cosine_tile_kernel, dim3(P.grid(g, groups, (P.NY * P.ntiles + WAVES - 1) / WAVES)), dim3(NT), 0, g.s,
+                               O.p.as<int>(), O.i.as<int>(), O.x.as<double>(), P.ts, P.Ti.as<int>(), P.Tx.as<double>(), P.nrmx,
+                               P.nrmy, P.M, P.NX, P.NY, (int)P.ntiles, C);
+            ++P.launches;
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventRecord(ev.b, g.s));
@@ -184,7 +223,53 @@ extern "C" void rcppml_gpu_cosine_sparse_ex(const int* x_col_ptr, const int* x_r
         const auto t0 = std::chrono::steady_clock::now();
         HIPCHK(hipMemcpy(out_C, C, nC * 8, hipMemcpyDeviceToHost));
         const double down_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        if (out_launches) *out_launches = launches;
+        if (out_launches) *out_launches = P.launches;
+        if (out_ms) { out_ms[0] = dev_ms; out_ms[1] = down_ms; }
+    });
+}
+
+extern "C" void rcppml_gpu_cosine_knn_sparse_ex(const int* x_col_ptr, const int* x_row_idx, const double* x_values, int* x_nnz,
+                                                const int* y_col_ptr, const int* y_row_idx, const double* y_values, int* y_nnz,
+                                                int* m, int* nx, int* ny, int* k, int* include_self, int* groups, int* out_idx,
+                                                double* out_val, int* out_launches, double* out_ms, int* out_status) {
+    entry_guard(out_status, [&] {
+        SparsePair P;
+        if (!k || (!y_col_ptr && !include_self)) throw std::invalid_argument("null scalar argument");
+        if (!out_idx || !out_val) throw std::invalid_argument("null output");
+        P.read(x_col_ptr, x_row_idx, x_values, x_nnz, y_col_ptr, y_row_idx, y_values, y_nnz, m, nx, ny, groups);
+        const bool skip_self = P.self && *include_self == 0;
+        const int64_t K = *k, eligible = P.NX - (skip_self ? 1 : 0);
+        if (K < 1 || K > KNN_MAX) throw std::invalid_argument("k must be in [1, 64]");
+        if (K > eligible) throw std::invalid_argument("k exceeds the " + std::to_string(eligible) + " eligible columns of x");
+        const size_t nOut = (size_t)K * (size_t)P.NY;
+        device_ready(12 * nOut + P.bytes(), "the cosine kNN");          // no term in nx * ny
+        CtxGuard g(env_device());
+        Events ev;
+        DevBuf dI, dV;
+        P.upload_to(g.s);
+        HIPCHK(hipEventRecord(ev.a, g.s));
+        int* idx = dalloc<int>(dI, nOut);
+        double* val = dalloc<double>(dV, nOut);
+        P.prepare(g);
+        const DevCsc& O = P.y();
+        hipLaunchKernelGGL(cosine_knn_kernel, dim3(P.grid(g, groups, (P.NY + WAVES - 1) / WAVES)), dim3(NT), 0, g.s, O.p.as<int>(),
+                           O.i.as<int>(), O.x.as<double>(), P.ts, P.Ti.as<int>(), P.Tx.as<double>(), P.nrmx, P.nrmy, P.M, P.NX, P.NY,
+                           (int)P.ntiles, (int)K, skip_self ? 1 : 0, idx, val);
+        ++P.launches;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev.b, g.s));
+        HIPCHK(hipStreamSynchronize(g.s));
+        float dev_ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&dev_ms, ev.a, ev.b));
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<int> hi(nOut);
+        std::vector<double> hv(nOut);
+        HIPCHK(hipMemcpy(hi.data(), idx, nOut * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hv.data(), val, nOut * 8, hipMemcpyDeviceToHost));
+        std::copy(hi.begin(), hi.end(), out_idx);          // both downloads have succeeded: only now are the outputs written
+        std::copy(hv.begin(), hv.end(), out_val);
+        const double down_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (out_launches) *out_launches = P.launches;
         if (out_ms) { out_ms[0] = dev_ms; out_ms[1] = down_ms; }
     });
 }

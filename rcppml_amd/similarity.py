@@ -12,6 +12,9 @@ Rules and deviations from R, all documented in DESIGN.md 4.16:
     by that vector, which applies the permutation where its inverse is needed (right only when the permutation is its own inverse).
     This build does what the documentation promises: aligned factor j is the object factor matched to ref factor j, that is
     order = argsort(assignment).  misc["assignment"] keeps the raw assignment.
+
+Build-defined, not in R: cosine_knn() (the k best columns by cosine without the full matrix, rcppml_gpu_cosine_knn_sparse_ex) and
+knn_graph() (the kNN graph or its Laplacian, for nmf(graph_H=) / svd(graph_V=)); graph_from_knn() is the host assembly.
 """
 import warnings
 
@@ -67,6 +70,65 @@ def cosine(x, y=None):
     if xv or yv:
         return out.reshape(-1)
     return out
+
+
+KNN_MAX = 64
+GRAPH_WEIGHTS = ("binary", "cosine")
+GRAPH_SYMMETRIZE = ("union", "mutual")
+
+
+def cosine_knn(x, y=None, k=10, include_self=False):
+    """The k most similar columns of x for every column of y (y=None: of x itself, a column being its own neighbour only with
+    include_self=True): (idx, sim), each (ny, k), best first.  The cosines are those of cosine(), bit for bit, ranked by larger
+    value, then smaller column index; zeros count, so a column with fewer than k non-zero cosines is filled with zero-valued
+    columns in index order.  x, y: matrices as for cosine(), a dense one going to CSC with its zeros dropped.  The full nx x ny
+    matrix is never formed (rcppml_gpu_cosine_knn_sparse_ex), k <= 64.  Build-defined: R has no such function."""
+    xc, xd = as_matrix(x, what="x and y must be matrices")
+    yc, yd = as_matrix(y, what="x and y must be matrices") if y is not None else (None, None)
+    X = _to_csc(xc, xd)
+    Y = None if y is None else _to_csc(yc, yd)
+    if Y is not None and Y.shape[0] != X.shape[0]:
+        raise ValueError("x and y must have the same number of rows")
+    if int(k) != k or not 1 <= k <= KNN_MAX:
+        raise ValueError("k must be an integer in [1, %d]" % KNN_MAX)
+    eligible = X.shape[1] - (1 if Y is None and not include_self else 0)
+    if k > eligible:
+        raise ValueError("k must be at most the number of eligible columns of x (%d)" % eligible)
+    r = _abi._check(_abi.cosine_knn_sparse(X, Y, int(k), include_self), "cosine_knn")
+    return r["idx"].astype(np.int64), r["val"]
+
+
+def graph_from_knn(idx, sim, weights="binary", symmetrize="union", laplacian=True):
+    """The n x n graph of a kNN result with y = x (idx, sim: (n, k), row j the neighbours of column j), on the host.  Edge (i, j)
+    of A for every neighbour i of j with a positive cosine, weight 1 or the cosine; S = max(A, A^T) (union) or min(A, A^T)
+    (mutual); L = D - S with D the row sums of S, or S itself.  Returns a scipy CSC matrix, which nmf(graph_W= / graph_H=) and
+    svd(graph_U= / graph_V=) both take."""
+    import scipy.sparse as sp
+    if weights not in GRAPH_WEIGHTS:
+        raise ValueError("'arg' should be one of %s" % ", ".join('"%s"' % w for w in GRAPH_WEIGHTS))
+    if symmetrize not in GRAPH_SYMMETRIZE:
+        raise ValueError("'arg' should be one of %s" % ", ".join('"%s"' % s for s in GRAPH_SYMMETRIZE))
+    idx, sim = np.asarray(idx), np.asarray(sim, dtype=np.float64)
+    n, k = idx.shape
+    edge = sim > 0
+    cols = np.repeat(np.arange(n), k).reshape(n, k)[edge]
+    w = np.ones(cols.shape[0]) if weights == "binary" else sim[edge]
+    A = sp.csc_matrix((w, (idx[edge], cols)), shape=(n, n))
+    S = A.maximum(A.T) if symmetrize == "union" else A.minimum(A.T)
+    if laplacian:
+        S = sp.diags(np.asarray(S.sum(axis=1)).ravel()) - S
+    S = sp.csc_matrix(S)
+    S.eliminate_zeros()
+    S.sort_indices()
+    return S
+
+
+def knn_graph(x, k=10, weights="binary", symmetrize="union", laplacian=True):
+    """The cosine kNN graph of the columns of x, self excluded: its Laplacian L = D - S (laplacian=True; what nmf(graph_H=) and
+    svd(graph_V=) take for a matrix whose columns are the samples) or the symmetric adjacency S.  The neighbours come from
+    cosine_knn() on the device, the assembly is graph_from_knn()."""
+    idx, sim = cosine_knn(x, None, k, include_self=False)
+    return graph_from_knn(idx, sim, weights, symmetrize, laplacian)
 
 
 def bipartiteMatch(x, verbose=False):

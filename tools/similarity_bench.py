@@ -8,7 +8,12 @@
 Each leg comes with the numpy / scipy restatement of the same stage on the host (X.T @ X on scipy sparse and the norms; the dense
 restatement and the restated solver for align; at most 16 threads), the launch count, and for the sparse kernel the useful
 multiply-add pairs per second (work = sum over rows r of nnz_X(r) nnz_Y(r)) and the fraction of LDS tile slots touched (entries of C
-that received a product / slots of all tiles).  --skip-host-genes leaves the slowest host leg out (reported as null)."""
+that received a product / slots of all tiles).  --skip-host-genes leaves the slowest host leg out (reported as null).
+  knn        cosine kNN (rcppml_gpu_cosine_knn_sparse_ex, k = --knn-k (15), self excluded) of the cells and of the genes: entry,
+             device, download, launches; beside them what the same job costs through cosine(): the full leg of this run plus a host
+             argpartition of its result (so `knn` needs `cells` / `genes` in the same run)
+  knn_synth  the same kNN on a random matrix (--synth rows,columns,density; 2 000 x 200 000 at 0.5 %) whose full result (320 GB)
+             could not be allocated: the times and the bytes of device memory the entry asks for"""
 import argparse
 import json
 import os
@@ -64,11 +69,47 @@ def sparse_leg(name, X, repeat, host):
     leg = dict(columns=n, rows=X.shape[0], nnz=int(X.nnz), entry_s=t_total, device_s=dev_s, download_s=down_s,
                device_plus_download_s=dev_s + down_s, launches=r["launches"], mac_pairs=work, mac_pairs_per_s=work / dev_s,
                tile_slots_touched=touched / float(tiles * geo["tile"] * n), result_bytes=int(8 * n * n), host_s=None,
-               max_abs_diff_to_host=None)
+               max_abs_diff_to_host=None, _C=r["C"])          # _C: for the kNN leg, dropped before printing
     if host:
         ref, t_ref, _ = median_of(lambda: R.cosine_sparse_ref(X), 1)
         leg.update(host_s=t_ref, max_abs_diff_to_host=float(np.max(np.abs(ref - r["C"]))))
     return {name: leg}, geo
+
+
+def knn_leg(X, k, repeat, full_leg=None):
+    """cosine kNN of the columns of X (rcppml_gpu_cosine_knn_sparse_ex, y = x, self excluded).  With the full-matrix leg of the
+    same run (full_leg, and its result still in full_leg["_C"]): what the same job costs through cosine(), the full entry plus a
+    host argpartition of its result, and whether the two name the same neighbour values."""
+    geo = _abi.cosine_geometry()
+    csc = CSC.from_scipy(X)
+    n, m = X.shape[1], X.shape[0]
+    r, t_total, rs = median_of(lambda: _abi.cosine_knn_sparse(csc, None, k), repeat)
+    assert r["status"] == 0, r["error"]
+    tiles = -(-n // geo["tile"])
+    leg = dict(k=k, entry_s=t_total, device_s=statistics.median(q["device_ms"] for q in rs) / 1e3,
+               download_s=statistics.median(q["download_ms"] for q in rs) / 1e3, launches=r["launches"],
+               result_bytes=int(12 * k * n), full_result_bytes=int(8 * n * n),
+               device_bytes=int(3 * (4 * (n + 1) + 12 * X.nnz) + 4 * (m + 1) + 4 * m * (tiles + 1) + 8 * n + 12 * k * n))
+    if full_leg is not None:
+        C = full_leg.pop("_C")
+
+        def host_topk():
+            np.fill_diagonal(C, -np.inf)
+            part = np.argpartition(C, n - k, axis=0)[n - k:]
+            return np.sort(np.take_along_axis(C, part, axis=0), axis=0)[::-1].T
+
+        best, t_topk, _ = median_of(host_topk, 1)
+        leg.update(full_entry_s=full_leg["entry_s"], full_device_s=full_leg["device_s"],
+                   full_device_plus_download_s=full_leg["device_plus_download_s"], host_topk_s=t_topk,
+                   full_plus_host_topk_s=full_leg["entry_s"] + t_topk, values_equal_to_full=bool(np.array_equal(best, r["val"])))
+    return leg
+
+
+def synthetic_knn_leg(rows, cols, density, k, repeat, seed):
+    g = np.random.default_rng(seed)
+    X = sp.random(rows, cols, density=density, format="csc", random_state=g, data_rvs=lambda s: g.uniform(0.1, 1.0, s))
+    X.sort_indices()
+    return dict(knn_leg(X, k, repeat), columns=cols, rows=rows, nnz=int(X.nnz), density=density)
 
 
 def align_leg(A_cells, k, reps, maxit, repeat, seed):
@@ -102,7 +143,9 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--skip-host-genes", action="store_true")
-    ap.add_argument("--legs", default="cells,genes,align")
+    ap.add_argument("--legs", default="cells,genes,align,knn,knn_synth")
+    ap.add_argument("--knn-k", type=int, default=15)
+    ap.add_argument("--synth", default="2000,200000,0.005", help="rows,columns,density of the synthetic kNN leg")
     args = ap.parse_args()
     if not _abi.detect():
         raise SystemExit("similarity_bench needs a GPU")
@@ -110,14 +153,26 @@ def main():
     legs = args.legs.split(",")
     out = dict(workload="pbmc3k", restatement_label="numpy / scipy restatement (tests/similarity_ref.py), not the reference's code",
                host_threads=int(os.environ["OMP_NUM_THREADS"]))
+    knn = {}
     if "cells" in legs:
         leg, geo = sparse_leg("cells", A, args.repeat, True)
         out.update(leg, geometry=geo)
+        if "knn" in legs:
+            knn["cells"] = knn_leg(A, args.knn_k, args.repeat, out["cells"])
     if "genes" in legs:
         G = A.T.tocsc()
         G.sort_indices()
         leg, geo = sparse_leg("genes", G, args.repeat, not args.skip_host_genes)
         out.update(leg, geometry=geo)
+        if "knn" in legs:
+            knn["genes"] = knn_leg(G, args.knn_k, args.repeat, out["genes"])
+    for name in ("cells", "genes"):
+        out.get(name, {}).pop("_C", None)
+    if "knn_synth" in legs:
+        rows, cols, density = args.synth.split(",")
+        knn["synthetic"] = synthetic_knn_leg(int(rows), int(cols), float(density), args.knn_k, args.repeat, args.seed)
+    if knn:
+        out["knn"] = knn
     if "align" in legs:
         cells_rows = A.T.tocsc()
         out.update(align_leg(cells_rows, args.k, args.reps, args.maxit, args.repeat, args.seed))
