@@ -906,7 +906,11 @@ RCPPML_GPU_API int rcppml_hip_solve_cd(rcppml_hip_ctx* ctx, int dtype, const voi
 RCPPML_GPU_API int rcppml_hip_order_columns(rcppml_hip_ctx* ctx, const int* sweeps, int64_t ncols, int* order);
 
 /* Cholesky solve + clip -- reference primitives/cpu/fused_nnls.hpp:185-219:
- *   L = chol(G) once; x = L^-T L^-1 (B(:,j) - l1_pre); clip >= 0 (nonneg); clip <= ub_post. */
+ *   L = chol(G) once; x = L^-T L^-1 (B(:,j) - l1_pre); clip >= 0 (nonneg); clip <= ub_post.
+ * 1 <= k <= 256 in both dtypes.  k <= 64 (fp64) / k <= 128 (fp32): one lane per column, divisions as the reference's llt.solve.
+ * Above that: a blocked factorisation (panels of 16 / 32 columns, MFMA trailing update) and a blocked triangular solve on MFMA
+ * that multiplies by the inverses of the diagonal blocks in place of dividing (kernels_chol_wide.hip.h); a backward-stable
+ * solve, not the reference's order of operations. */
 RCPPML_GPU_API int rcppml_hip_solve_chol(rcppml_hip_ctx* ctx, int dtype, const void* G,
                                          const void* B, void* X, int k, int64_t ncols,
                                          double l1_pre, int nonneg, double ub_post);

@@ -27,6 +27,10 @@ extern "C" int rcppml_hip_solve_cd(rcppml_hip_ctx* c, int dtype, const void* G, 
 // ----------------------------------------------------------------------------
 // Cholesky solve + clip
 // ----------------------------------------------------------------------------
+void rcppml_solve_chol_wide_f32(rcppml_hip_ctx* c, const float* G, const float* B, float* X, int k, int64_t ncols, float l1_pre,
+                                int nonneg, float ub_post);
+void rcppml_solve_chol_wide_f64(rcppml_hip_ctx* c, const double* G, const double* B, double* X, int k, int64_t ncols,
+                                double l1_pre, int nonneg, double ub_post);
 template <class T, int KP>
 static void chol_launch(rcppml_hip_ctx* c, const T* Gp, const T* B, T* X, int k, int64_t ncols, T l1_pre,
                         int nonneg, T ub_post) {
@@ -44,6 +48,11 @@ static void solve_chol_impl(rcppml_hip_ctx* c, const T* G, const T* B, T* X, int
                             int nonneg, T ub_post) {
     if (ncols <= 0) return;
     const int lane_max = std::is_same<T, float>::value ? 128 : 64;
+    if (k > lane_max && k <= 256) {           // blocked MFMA factor + solve (kernels_chol_wide.hip.h)
+        if constexpr (std::is_same<T, float>::value) rcppml_solve_chol_wide_f32(c, G, B, X, k, ncols, l1_pre, nonneg, ub_post);
+        else rcppml_solve_chol_wide_f64(c, G, B, X, k, ncols, l1_pre, nonneg, ub_post);
+        return;
+    }
     if (k < 1 || k > lane_max) throw std::runtime_error("solve_chol: k out of supported range");
     const int KP = solve_kp(k);
     T *Gp, *invd;
