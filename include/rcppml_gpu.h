@@ -1329,6 +1329,38 @@ RCPPML_GPU_API void rcppml_gpu_nmf_streaming_ex(const int* col_ptr, const int* r
         int* cd_maxit, double* cd_tol, int* patience, int* sort_model, int* precision, int* devices, double* loss_history,
         int* out_iter, int* out_converged, double* out_loss, double* out_tol, int64_t* out_info, int* out_status);
 
+/* Panel-streamed randomized SVD / PCA (rcppml_amd/csrc/ops_stream_svd.hip, kernels_stream_svd.hip.h).
+ * Build-defined.  It stands for the reference's out-of-core SVD (svd/streaming.hpp:683-773, svd/streaming_matvec.hpp,
+ * svd_streaming_gateway) with the randomized block method of rcppml_gpu_svd_randomized_ex, step for step, its two block products
+ * taken one column panel at a time: neither the matrix nor its transpose is resident on the device.
+ *
+ * rcppml_hip_stream_block_geometry (host arithmetic): out[0] = rows of a workgroup's row tile of rcppml_hip_stream_block_prod,
+ *   out[1] = wavefronts (row slices) per workgroup, out[2] = rows of a wavefront's slice (8 per lane group), out[3] = lanes per
+ *   l-vector (8, 16, 32 or 64), out[4] = bytes of the range table per (tile, panel column); the table has 4 more bytes per panel
+ *   column.  A function of l only today; dtype is checked.  l in [1, 128].
+ * rcppml_hip_stream_block_prod: Y[:, r] (+)= sum over the panel's columns j of a_rj X[:, j], from the panel in COLUMN form (CSC of
+ *   nrows x ncols, row indices strictly increasing within a column; all device memory).  X: l x ncols, Y: l x nrows, leading
+ *   dimension l.  accumulate 0: Y is overwritten (first panel of a pass); 1: added to.  A wavefront owns a fixed slice of rows and
+ *   keeps its accumulators in registers, walking the columns in ascending order: no atomics, one order of additions per element,
+ *   and the result does not depend on `groups` (workgroups of the launch; 0 = one per row tile), bit for bit.  l in [1, 128].
+ * rcppml_gpu_svd_streaming_ex: the streamed fit.  Data as for rcppml_gpu_nmf_streaming_ex (a host CSC with spz_path NULL, or an
+ *   .spz path with col_ptr NULL; panels and *panel_cols = 0 as there, the range table being this kernel's).  *k in
+ *   [1, min(m, n)]; l = *k + max(10, *k / 5) must be at most 128 and at most min(m, n); *max_iter: the power iterations q (<= 0: 3,
+ *   at most 10); *seed as in rcppml_gpu_svd_randomized_ex (0: 42); *center: PCA, the row means computed in one more pass and
+ *   written to out_row_means (m; may be NULL without *center); *precision 0 fp32, 1 fp64; *devices (may be NULL) must be <= 1.
+ *   U (m x *k) and V (n x *k) column-major, d (*k).  out_info (8): {passes over the matrix (2 q + 2, + 1 centred), panels, columns
+ *   of the widest panel, bytes of the panel buffer, bytes of the range table, device-op calls, q, l}.
+ *   Refused (*out_status = -1, reason in rcppml_gpu_last_error, no output written): a null pointer, l above 128 or above min(m, n)
+ *   (the message names k), a panel width whose range table would pass 2 GiB, an unreadable, malformed or row-sorted .spz file, more
+ *   than one device, a malformed CSC, a non-finite value, not enough free device memory, no HIP device. */
+RCPPML_GPU_API int rcppml_hip_stream_block_geometry(int dtype, int l, int64_t* out5);
+RCPPML_GPU_API int rcppml_hip_stream_block_prod(rcppml_hip_ctx* ctx, int dtype, const int* col_ptr, const int* row_idx,
+                                                const void* values, int64_t nrows, int64_t ncols, int l, const void* X,
+                                                int accumulate, void* Y, int groups);
+RCPPML_GPU_API void rcppml_gpu_svd_streaming_ex(const int* col_ptr, const int* row_idx, const double* values, int* nnz,
+        const char* spz_path, int* m, int* n, int* k, int* center, int* seed, int* max_iter, int* precision, int* panel_cols,
+        int* devices, double* U, double* d, double* V, double* out_row_means, int64_t* out_info, int* out_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,8 @@ Layout (only what the path needs):
              resident on the device (csrc/ops_graph.hip)
   streaming.py nmf_streaming(): the plain MSE fit with the matrix streamed through the device one column panel at a time
              (csrc/ops_stream.hip); neither the matrix nor its transpose is resident
+  svd_streaming.py svd_streaming() / pca_streaming(): the randomized block SVD with the matrix streamed the same way
+             (csrc/ops_stream_svd.hip), from a host CSC or an .spz path
   als.py     one-process-per-GPU column-sharded ALS loop over torch.distributed (RCCL): Comm, ShardedALS, HipOps
   data.py    synthetic inputs (restatement of R/simulateNMF.R) and CSC helpers
 """
@@ -37,3 +39,4 @@ from .refine import compute_target, refine  # noqa: E402,F401
 from .classify import classify_cv, classify_embedding, classify_logistic  # noqa: E402,F401
 from .similarity import align, bipartiteMatch, cosine, cosine_knn, knn_graph  # noqa: E402,F401
 from .streaming import nmf_streaming  # noqa: E402,F401
+from .svd_streaming import pca_streaming, svd_streaming  # noqa: E402,F401

@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_cosine_sparse_ex", "rcppml_gpu_cosine_knn_sparse_ex", "rcppml_gpu_cosine_geometry", "rcppml_gpu_cosine_dense_ex", "rcppml_gpu_bipartite_match_ex",
     "rcppml_hip_stream_geometry", "rcppml_hip_stream_rhs_w", "rcppml_hip_stream_gram_accum", "rcppml_hip_stream_gram_finish",
     "rcppml_gpu_nmf_streaming_ex",
+    "rcppml_hip_stream_block_geometry", "rcppml_hip_stream_block_prod", "rcppml_gpu_svd_streaming_ex",
 ]
 
 
@@ -1836,4 +1837,45 @@ def nmf_streaming(csc, spz_path, m, n, k, W_T, H, *, panel_cols=0, max_iter=100,
         r.update(d=d, iter=it.value, converged=bool(conv.value), loss=loss.value, tol=otol.value, loss_history=hist[:it.value].copy(),
                  panels=int(info[0]), panel_cols=int(info[1]), panel_bytes_peak=int(info[2]), ops_per_iter=int(info[3]),
                  range_table_bytes=int(info[4]))
+    return r
+
+
+# ----------------------------------------------------------------------------- panel-streamed SVD (ops_stream_svd.hip)
+def stream_block_geometry(dt, l):
+    """rcppml_hip_stream_block_geometry: dict(tile_rows, waves, wave_rows, lanes, table_bytes_per_tile_column) of
+    stream_block_prod for this precision and sketch width."""
+    out = (C.c_int64 * 5)()
+    f = lib().rcppml_hip_stream_block_geometry
+    f.restype = C.c_int
+    _chk(f(C.c_int(dt), C.c_int(l), out), "stream_block_geometry")
+    return dict(zip(("tile_rows", "waves", "wave_rows", "lanes", "table_bytes_per_tile_column"), (int(v) for v in out)))
+
+
+def stream_block_prod(ctx, dt, col_ptr, row_idx, values, nrows, ncols, l, X, accumulate, Y, groups=0):
+    """rcppml_hip_stream_block_prod on device tensors: Y (l x nrows) (+)= the panel's scatter product with X (l x ncols)."""
+    f = lib().rcppml_hip_stream_block_prod
+    f.restype = C.c_int
+    _chk(f(ctx._h, C.c_int(dt), _dptr(col_ptr), _dptr(row_idx), _dptr(values), C.c_int64(nrows), C.c_int64(ncols), C.c_int(l),
+           _dptr(X), C.c_int(int(accumulate)), _dptr(Y), C.c_int(groups)), "stream_block_prod")
+
+
+def svd_streaming(csc, spz_path, m, n, k, *, center=False, seed=0, max_iter=3, precision=F64, panel_cols=0, devices=1, buffers=None):
+    """rcppml_gpu_svd_streaming_ex.  csc: (p, i, x) host arrays or None; spz_path: a path or None.  buffers: U, d, V, row_means to
+    write into (as they are), else zeroed ones.  Returns dict(status, error, U (m x k), d, V (n x k), row_means, buffers, passes,
+    panels, panel_cols, panel_bytes_peak, range_table_bytes, device_ops, power_iterations, sketch)."""
+    keep = _csc_args(*csc) if csc is not None else ()
+    head = [_np_ptr(keep[0]), _np_ptr(keep[1]), _np_ptr(keep[2]), _ci(keep[2].shape[0])] if csc is not None else [None, None, None, _ci(0)]
+    kb = max(int(k), 1)
+    b = _svd_buffers(m, n, kb, buffers)
+    info = (C.c_int64 * 8)()
+    st = C.c_int(-99)
+    lib().rcppml_gpu_svd_streaming_ex(*head, C.c_char_p(os.fsencode(spz_path)) if spz_path is not None else None, _ci(m), _ci(n), _ci(k),
+                                      _ci(int(bool(center))), _ci(seed), _ci(max_iter), _ci(precision), _ci(panel_cols), _ci(devices),
+                                      _np_ptr(b["U"]), _np_ptr(b["d"]), _np_ptr(b["V"]), _np_ptr(b["row_means"]), info, C.byref(st))
+    del keep
+    r = dict(status=st.value, error=last_error() if st.value else "", buffers=b)
+    if st.value == 0:
+        r.update(U=b["U"][:m * kb].reshape(kb, m).T, d=b["d"], V=b["V"][:n * kb].reshape(kb, n).T, row_means=b["row_means"],
+                 **dict(zip(("passes", "panels", "panel_cols", "panel_bytes_peak", "range_table_bytes", "device_ops",
+                             "power_iterations", "sketch"), (int(v) for v in info))))
     return r

@@ -26,7 +26,7 @@ template <class T, int KP> constexpr size_t lds_bytes() { return ACC_BYTES + (si
 
 // tp[b * pc + j] = the first nonzero of panel column j whose row is >= b * RW (b = 0 .. nb: wave slice boundaries; rows are
 // sorted within a column, so slice b of column j is the contiguous range tp[b * pc + j] .. tp[(b + 1) * pc + j])
-__global__ __launch_bounds__(256) void stream_tile_ptr_kernel(const int* __restrict__ cp, const int* __restrict__ ri, int64_t pc,
+static __global__ __launch_bounds__(256) void stream_tile_ptr_kernel(const int* __restrict__ cp, const int* __restrict__ ri, int64_t pc,
                                                               int64_t nb, int RW, int* __restrict__ tp) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (nb + 1) * pc) return;
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void stream_gram_finish_kernel(const T* __rest
 }
 
 // out[0] = v[0] + v[1] + ... in index order
-__global__ void stream_sum_kernel(const double* __restrict__ v, int count, double* __restrict__ out) {
+static __global__ void stream_sum_kernel(const double* __restrict__ v, int count, double* __restrict__ out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     double s = 0;
     for (int q = 0; q < count; ++q) s += v[q];

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(WG) void ks_finish_kernel(T* __restrict__ X, long l
 // it + 1 passes done and, unless the loop ends here, factorises V'V for the W-update of pass it + 1; it = -1: the seed).
 // Outputs: Ginv = (G + ridge I)^-1, nsq = diag(G) before the ridge, cs = the column sums.  Li: k x k scratch.
 // A non-positive (or NaN) pivot stops the loop before the update it would feed and leaves its code in st[KS_ERR].
-__global__ __launch_bounds__(WG) void ks_small_kernel(const double* __restrict__ PG, int nb, int k, double ridge,
+static __global__ __launch_bounds__(WG) void ks_small_kernel(const double* __restrict__ PG, int nb, int k, double ridge,
                                                       double* __restrict__ Ginv, double* __restrict__ Li, double* __restrict__ nsq,
                                                       double* __restrict__ cs, double* __restrict__ dw_out, double tol, double eps,
                                                       int* st, int it, int side, int last) {

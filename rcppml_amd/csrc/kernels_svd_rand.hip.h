@@ -171,7 +171,7 @@ __global__ __launch_bounds__(WG) void rs_prod_kernel(const int* __restrict__ p, 
 // One workgroup.  G = the records' Grams re-added in block order.  final: G -> Gout and nothing else.  Else the Cholesky factor
 // L = R' of G in LDS, a pivot accepted only above thr * (its original diagonal), and Rinv[b * l + a] = R^-1(b, a); a rejected
 // pivot leaves row and column of R^-1 zero.  Li: l x l scratch.
-__global__ __launch_bounds__(WG) void rs_chol_kernel(const double* __restrict__ P, int nb, int l, double thr, double* __restrict__ Rinv,
+static __global__ __launch_bounds__(WG) void rs_chol_kernel(const double* __restrict__ P, int nb, int l, double thr, double* __restrict__ Rinv,
                                                      double* __restrict__ Li, double* __restrict__ Gout, int final) {
     __shared__ double G[RS_LMAX * RS_LMAX];
     __shared__ double d0[RS_LMAX];
@@ -267,5 +267,9 @@ __global__ __launch_bounds__(WG) void rs_rotate_kernel(const T* __restrict__ X, 
     if (c0 < k) out[(long)c0 * len + row] = (T)q0;
     if (c1 < k) out[(long)c1 * len + row] = (T)q1;
 }
+
+// Host (defined in ops_svd.hip): the l x l stage.  G = Bt'Bt (l x l, fp64) -> d[c] = sqrt(lambda_c) descending for c < kc, and the
+// rotations the two rs_rotate_kernel launches take: wu[b * kc + c] = Vb(b, c), wv[b * kc + c] = Vb(b, c) / d[c] (0 where d = 0).
+void rs_small_stage(const std::vector<double>& G, int l, int kc, std::vector<double>& d, std::vector<double>& wu, std::vector<double>& wv);
 
 }  // namespace rsv

@@ -8,17 +8,11 @@
 //
 // Every argument is checked before the device is touched, and outputs are written only after the fit has succeeded, so a refused
 // call leaves every output buffer as it was.
-#include "entry_common.hip.h"
 #include "gram_launch.hip.h"
 #include "kernels_stream.hip.h"
-#include "spz_parse.hpp"
+#include "stream_panels.hip.h"
 
-#include <cstdio>
 #include <limits>
-
-// ops_spz.hip: whole chunks of a parsed .spz file into device arrays
-void rcppml_spz_decode_columns(rcppml_hip_ctx* c, const uint8_t* data, const rcppml_spz::SpzParsed& P, int64_t col0, int64_t col1,
-                               int* d_col_ptr, int* d_row_idx, double* d_values, int check_rows_below);
 
 namespace {
 using namespace rcppml_plugin;
@@ -127,23 +121,16 @@ size_t range_table_bytes(size_t elem, int k, int64_t m, int64_t pc) {
 }
 
 struct StreamArgs {
-    // the matrix: a host CSC (p, i, x) or a parsed .spz file (file bytes + parse)
-    const int* p = nullptr; const int* i = nullptr; const double* x = nullptr;
-    const uint8_t* file = nullptr; const rcppml_spz::SpzParsed* spz = nullptr;
+    const PanelSource* src = nullptr;        // the matrix and its panels (stream_panels.hip.h)
     std::vector<int64_t> pb;                 // panel q holds columns pb[q] .. pb[q + 1]
-    int64_t m, n, pc, max_nnz;               // pc: the widest panel's columns, max_nnz: the fullest panel's nonzeros
+    int64_t m, n, pc;                        // pc: the widest panel's columns
     int k, max_iter, norm_type, solver_mode, cd_maxit, patience, sort_model, nonneg_W, nonneg_H;
     double tol, cd_tol, L1_W, L1_H, L2_W, L2_H, ub_W, ub_H;
     double *W, *H, *d, *loss_history;
     int out_iter = 0, out_converged = 0, ops_per_iter = 0;
     double out_loss = 0, out_tol = 0;
-    const int* colptr() const { return spz ? spz->col_ptr.data() : p; }
+    const int* colptr() const { return src->colptr(); }
 };
-
-// device bytes of the panel buffer: column pointers, rows, values in T, and for fp32 the doubles they are cast from
-size_t panel_buffer_bytes(size_t elem, int64_t pc, int64_t max_nnz) {
-    return ((size_t)pc + 1) * 4 + (size_t)max_nnz * (4 + elem + (elem == 4 ? 8 : 0));
-}
 
 // the plain fit of plugin.hip (fit<T>, MSE branch) with the columns regrouped into panels; see the file comment
 template <class T>
@@ -151,24 +138,13 @@ void fit_stream(StreamArgs& P) {
     const int dt = DT<T>::id, k = P.k;
     const int64_t m = P.m, n = P.n, np = (int64_t)P.pb.size() - 1;
     const int* cp = P.colptr();
-    std::vector<int> hp;                                       // host CSC: every panel's column pointers, rebased to its first nonzero
-    if (!P.spz) {
-        hp.resize((size_t)(n + np));
-        for (int64_t q = 0; q < np; ++q)
-            for (int64_t j = P.pb[q]; j <= P.pb[q + 1]; ++j) hp[(size_t)(j + q)] = cp[j] - cp[P.pb[q]];
-    }
 
     CtxGuard g(env_device());
     rcppml_hip_ctx* c = g.c;
     hipStream_t s = g.s;
-    // one panel buffer: everything runs on one stream, so a second one would overlap nothing
-    DevBuf bp, bi, bx, bx64;
-    dalloc<int>(bp, (size_t)P.pc + 1);
-    dalloc<int>(bi, (size_t)P.max_nnz);
-    dalloc<T>(bx, (size_t)P.max_nnz);
+    PanelBuffer<T> panel(*P.src, c, s);
+    DevBuf &bp = panel.bp, &bi = panel.bi, &bx = panel.bx;
     constexpr bool f32 = std::is_same<T, float>::value;
-    if (f32) dalloc<double>(bx64, (size_t)P.max_nnz);          // the boundary's doubles, cast on the device
-    double* const x64 = f32 ? bx64.as<double>() : reinterpret_cast<double*>(bx.p);
     DevBuf dW, dH, dd, dBw, dBh, dG, dGs, dGacc, dGwt, dsums, dtr, dtrp, dloss;
     upload_cast<T>(c, P.W, (size_t)k * m, dW, s);
     upload_cast<T>(c, P.H, (size_t)k * n, dH, s);
@@ -182,21 +158,6 @@ void fit_stream(StreamArgs& P) {
     dalloc<double>(dtr, 1);
     zeros<double>(dtrp, (size_t)np, s);
     dalloc<double>(dloss, 4);
-
-    // panel q resident in the buffer: uploaded from the host CSC, or its chunks decoded on the device
-    auto load_panel = [&](int64_t q, bool first_pass) {
-        const int64_t j0 = P.pb[q], j1 = P.pb[q + 1], e0 = cp[j0], pn = cp[j1] - e0;
-        if (P.spz) {
-            rcppml_spz_decode_columns(c, P.file, *P.spz, j0, j1, bp.as<int>(), bi.as<int>(), x64, first_pass ? (int)m : 0);
-        } else {
-            HIPCHK(hipMemcpyAsync(bp.p, hp.data() + j0 + q, (size_t)(j1 - j0 + 1) * 4, hipMemcpyHostToDevice, s));
-            if (pn > 0) {
-                HIPCHK(hipMemcpyAsync(bi.p, P.i + e0, (size_t)pn * 4, hipMemcpyHostToDevice, s));
-                HIPCHK(hipMemcpyAsync(x64, P.x + e0, (size_t)pn * 8, hipMemcpyHostToDevice, s));
-            }
-        }
-        if (f32 && pn > 0) OPCHK(rcppml_hip_cast(c, RCPPML_F64, x64, RCPPML_F32, bx.p, pn));
-    };
 
     const double eps = 1e-15;
     double prev_loss = f32 ? (double)std::numeric_limits<float>::max() : std::numeric_limits<double>::max();
@@ -216,7 +177,7 @@ void fit_stream(StreamArgs& P) {
         OPCHK(rcppml_hip_gram(c, dt, dW.p, k, m, eps, P.L2_H, dG.p)); ++ops;
         for (int64_t q = 0; q < np; ++q) {
             const int64_t j0 = P.pb[q], pc = P.pb[q + 1] - j0, pn = cp[P.pb[q + 1]] - cp[j0];
-            load_panel(q, iter == 0);
+            panel.load(q, iter == 0);
             T* Hp = dH.as<T>() + (size_t)j0 * k;
             // H side: the panel's columns against the fixed Gram of W
             OPCHK(rcppml_hip_rhs(c, dt, bp.as<int>(), bi.as<int>(), bx.p, pc, dW.p, k, dBh.p));
@@ -277,17 +238,6 @@ void fit_stream(StreamArgs& P) {
     P.out_iter = iterations; P.out_converged = converged ? 1 : 0; P.out_loss = train_loss; P.out_tol = final_tol;
 }
 
-std::vector<uint8_t> read_file(const char* path) {
-    struct File { FILE* f; ~File() { if (f) std::fclose(f); } } file{std::fopen(path, "rb")};
-    if (!file.f) throw std::invalid_argument(std::string("cannot open ") + path);
-    long fsz = -1;
-    if (std::fseek(file.f, 0, SEEK_END) == 0) fsz = std::ftell(file.f);
-    if (fsz < 0 || std::fseek(file.f, 0, SEEK_SET) != 0) throw std::invalid_argument(std::string("cannot size ") + path);
-    std::vector<uint8_t> bytes((size_t)fsz);
-    if (fsz && std::fread(bytes.data(), 1, (size_t)fsz, file.f) != (size_t)fsz) throw std::invalid_argument(std::string("short read of ") + path);
-    return bytes;
-}
-
 }  // namespace
 
 extern "C" void rcppml_gpu_nmf_streaming_ex(const int* col_ptr, const int* row_idx, const double* values, int* nnz, const char* spz_path,
@@ -315,69 +265,17 @@ extern "C" void rcppml_gpu_nmf_streaming_ex(const int* col_ptr, const int* row_i
         if (*norm_type < 0 || *norm_type > 2) throw std::invalid_argument("norm_type must be 0 (L1), 1 (L2) or 2 (none)");
         StreamArgs P{};
         P.m = *m; P.n = *n; P.k = *k;
-        std::vector<uint8_t> bytes;
-        rcppml_spz::SpzParsed parsed;
-        std::vector<int64_t> chunk_start;                      // .spz: the first column of every chunk, then n
-        int64_t total_nnz = 0;
-        if (spz_path) {
-            bytes = read_file(spz_path);
-            try { parsed = rcppml_spz::parse_file(bytes.data(), bytes.size()); }
-            catch (const rcppml_spz::ParseError& e) { throw std::invalid_argument(std::string("data = an .spz path: ") + e.what); }
-            const rcppml_spz::SpzHeader& h = parsed.h;
-            if ((int64_t)h.m != P.m || (int64_t)h.n != P.n) throw std::invalid_argument("data = an .spz path: the file's shape is not m x n");
-            if (!parsed.row_perm.empty()) throw std::invalid_argument("data = an .spz path: a row-sorted file (stored row permutation) does not keep rows ascending within a column");
-            for (int64_t j = 0; j < P.n; ++j)
-                if (parsed.col_ptr[j] < 0 || parsed.col_ptr[j] > parsed.col_ptr[j + 1]) throw std::invalid_argument("data = an .spz path: column pointers not monotone");
-            if (parsed.col_ptr[0] != 0 || (uint64_t)parsed.col_ptr[P.n] != h.nnz) throw std::invalid_argument("data = an .spz path: column pointers do not span the nonzeros");
-            std::vector<rcppml_spz::SpzChunk> ch(h.num_chunks);
-            if (h.num_chunks) std::memcpy(ch.data(), bytes.data() + h.chunk_index_offset, (size_t)h.num_chunks * 48);
-            int64_t next = 0;
-            for (const auto& cdesc : ch) {
-                if ((int64_t)cdesc.col_start != next) throw std::invalid_argument("data = an .spz path: chunks are not contiguous in column order");
-                chunk_start.push_back(next);
-                next += cdesc.num_cols;
-            }
-            if (next != P.n) throw std::invalid_argument("data = an .spz path: chunks do not cover the columns");
-            chunk_start.push_back(P.n);
-            P.file = bytes.data(); P.spz = &parsed;
-            total_nnz = (int64_t)h.nnz;
-        } else {
-            if (!nnz || *nnz < 0) throw std::invalid_argument("nnz must be >= 0");
-            if (!col_ptr || (*nnz > 0 && (!row_idx || !values))) throw std::invalid_argument("null CSC array");
-            check_csc_strict(col_ptr, row_idx, *m, *n, *nnz);
-            all_finite(values, (size_t)*nnz, "the matrix");
-            P.p = col_ptr; P.i = row_idx; P.x = values;
-            total_nnz = *nnz;
-        }
+        PanelSource src;
+        if (spz_path) src.open_spz(spz_path, P.m, P.n);
+        else src.open_csc(col_ptr, row_idx, values, nnz, P.m, P.n);
         all_finite(W, (size_t)*k * *m, "W");
         all_finite(H, (size_t)*k * *n, "H");
         const size_t el = *precision == RCPPML_F32 ? 4 : 8;
         // panel_cols = 0: panels of about 64 MiB of CSC at the matrix's mean column size, in whole multiples of 256 columns, and no
         // wider than the range table of stream_rhs_w allows (2^29 cells)
         const int64_t cap = std::max<int64_t>(1, (((int64_t)1 << 29) * 4) / (int64_t)range_table_bytes(el, P.k, P.m, 1));
-        int64_t pc = *panel_cols;
-        if (pc == 0) {
-            const double col_bytes = 4.0 + 12.0 * (double)total_nnz / (double)P.n;
-            pc = std::max<int64_t>(256, (int64_t)(67108864.0 / col_bytes) / 256 * 256);
-            pc = std::min(pc, std::max<int64_t>(1, spz_path ? cap : (cap >= 256 ? cap / 256 * 256 : cap)));
-        }
-        if (spz_path && parsed.h.chunk_cols > 0) pc = (pc + parsed.h.chunk_cols - 1) / parsed.h.chunk_cols * parsed.h.chunk_cols;
-        pc = std::min(pc, P.n);
-        // the panels: pc columns each; from an .spz file whole chunks, pc rounded up to them
-        P.pb.push_back(0);
-        if (spz_path) {
-            for (size_t q = 1; q < chunk_start.size(); ++q)
-                if (q + 1 == chunk_start.size() || chunk_start[q + 1] - P.pb.back() > pc) P.pb.push_back(chunk_start[q]);
-        } else {
-            for (int64_t j = pc; j < P.n; j += pc) P.pb.push_back(j);
-            P.pb.push_back(P.n);
-        }
-        const int* cp = P.colptr();
-        P.pc = 0; P.max_nnz = 0;
-        for (size_t q = 0; q + 1 < P.pb.size(); ++q) {
-            P.pc = std::max(P.pc, P.pb[q + 1] - P.pb[q]);
-            P.max_nnz = std::max<int64_t>(P.max_nnz, cp[P.pb[q + 1]] - cp[P.pb[q]]);
-        }
+        src.plan(*panel_cols, cap);
+        P.src = &src; P.pb = src.pb; P.pc = src.pc;
         if (P.pc > cap) throw std::invalid_argument("panel_cols: the range table of the W-side kernel would exceed 2 GiB at " + std::to_string(P.pc) +
                                                     " columns per panel; use at most " + std::to_string(cap));
         P.max_iter = *max_iter; P.tol = *tol; P.norm_type = *norm_type; P.solver_mode = *solver_mode; P.cd_maxit = *cd_maxit;
@@ -385,10 +283,10 @@ extern "C" void rcppml_gpu_nmf_streaming_ex(const int* col_ptr, const int* row_i
         P.L1_W = L1[0]; P.L1_H = L1[1]; P.L2_W = L2[0]; P.L2_H = L2[1]; P.ub_W = upper_bound[0]; P.ub_H = upper_bound[1];
         P.nonneg_W = nonneg[0]; P.nonneg_H = nonneg[1];
         P.W = W; P.H = H; P.d = d; P.loss_history = loss_history;
-        const size_t panel_bytes = panel_buffer_bytes(el, P.pc, P.max_nnz), table_bytes = range_table_bytes(el, P.k, P.m, P.pc);
+        const size_t panel_bytes = src.buffer_bytes(el), table_bytes = range_table_bytes(el, P.k, P.m, P.pc);
         // factors, right-hand sides and the cast staging of the factors; the panel buffer; the range table; .spz: the decoder's scratch
         device_ready(el * (size_t)P.k * (size_t)(2 * P.m + P.n + P.pc) + 8 * (size_t)P.k * (size_t)std::max(P.m, P.n) + panel_bytes + table_bytes +
-                         (spz_path ? bytes.size() / (P.pb.size() - 1) * 2 + (size_t)P.max_nnz * 8 : 0) + ((size_t)64 << 20),
+                         src.decode_bytes() + ((size_t)64 << 20),
                      "the streamed fit");
         if (*precision == RCPPML_F32) fit_stream<float>(P);
         else fit_stream<double>(P);

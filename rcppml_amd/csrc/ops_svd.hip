@@ -950,21 +950,11 @@ template <class T> struct Engine {
         hipLaunchKernelGGL(rs_chol_kernel, dim3(1), dim3(WG), 0, s, (const double*)Pn, nbn, l, thr, Ri, Li, G, 1);
         HIPCHK(hipGetLastError());
         const std::vector<double> Gh = read<double>(G, (size_t)l * l);
-        std::vector<double> Us, lam, Vb;
-        jacobi_svd(Gh, l, Us, lam, Vb);                         // G is symmetric positive semidefinite: its SVD is its eigensystem
         const int kc = std::min(K, l);
         R.iters.assign(1, q);
         R.k_sel = kc;
-        R.d.resize(kc);
-        std::vector<double> wu((size_t)l * kc), wv((size_t)l * kc);
-        for (int c = 0; c < kc; ++c) {
-            const double sg = std::sqrt(std::max(lam[c], 0.0));
-            R.d[c] = sg;
-            for (int b = 0; b < l; ++b) {
-                wu[(size_t)b * kc + c] = Vb[(size_t)c * l + b];
-                wv[(size_t)b * kc + c] = sg > 0 ? Vb[(size_t)c * l + b] / sg : 0.0;
-            }
-        }
+        std::vector<double> wu, wv;
+        rs_small_stage(Gh, l, kc, R.d, wu, wv);
         DevBuf dwu, dwv, ou, ov;
         const double* Wu = upload<double>(dwu, wu.data(), wu.size(), s);
         const double* Wv = upload<double>(dwv, wv.data(), wv.size(), s);
@@ -1412,6 +1402,25 @@ extern "C" void rcppml_gpu_svd_krylov_dense_ex(const double* A_data, int* m, int
 // ------------------------------------------------------------------------------------------------------------ randomized entries
 // Build-defined: the randomized block SVD (svd/randomized.hpp:59-241), which the four reference entries run as Lanczos under
 // algorithm 3.
+// The l x l stage, shared with the streamed engine (ops_stream_svd.hip).  G is symmetric positive semidefinite: its SVD is its
+// eigensystem.
+void rsv::rs_small_stage(const std::vector<double>& G, int l, int kc, std::vector<double>& d, std::vector<double>& wu,
+                         std::vector<double>& wv) {
+    std::vector<double> Us, lam, Vb;
+    jacobi_svd(G, l, Us, lam, Vb);
+    d.resize(kc);
+    wu.assign((size_t)l * kc, 0.0);
+    wv.assign((size_t)l * kc, 0.0);
+    for (int c = 0; c < kc; ++c) {
+        const double sg = std::sqrt(std::max(lam[c], 0.0));
+        d[c] = sg;
+        for (int b = 0; b < l; ++b) {
+            wu[(size_t)b * kc + c] = Vb[(size_t)c * l + b];
+            wv[(size_t)b * kc + c] = sg > 0 ? Vb[(size_t)c * l + b] / sg : 0.0;
+        }
+    }
+}
+
 namespace {
 struct RsRaw {
     int* max_iter; double *L21_u, *L21_v, *angular_u, *angular_v;
