@@ -1361,6 +1361,27 @@ RCPPML_GPU_API void rcppml_gpu_svd_streaming_ex(const int* col_ptr, const int* r
         const char* spz_path, int* m, int* n, int* k, int* center, int* seed, int* max_iter, int* precision, int* panel_cols,
         int* devices, double* U, double* d, double* V, double* out_row_means, int64_t* out_info, int* out_status);
 
+/* StreamPress v2 `.spz` writer (rcppml_amd/csrc/ops_spz_write.hip, kernels_spz_write.hip.h, spz_layout.hpp).
+ * Build-defined; a Python-surface entry (st_write()): the reference plugin ABI has no writer, its st_write() encodes on the host
+ * (R/streampress.R:69).  The entropy coding runs on the device.
+ *
+ * rcppml_gpu_spz_write_ex: host CSC (col_ptr *n + 1, row_idx and values *nnz; rows strictly increasing within a column) -> the
+ *   file `path`, which rcppml_hip_spz_decode, rcppml_sp_read_gpu, the streamed fits and the reference decoder read.
+ *   *value_type: -1 "auto" (the smallest of uint8 / uint16 / uint32 when every stored value is a non-negative integer below 2^32,
+ *   -0.0 not being one; float64 otherwise), or 0 uint8, 1 uint16, 2 uint32, 3 float32 (values rounded to fp32), 6 float64.
+ *   *chunk_cols: columns per chunk, in [1, 2^31 - 1] (the reference's default is 2048).  No row sorting, no transpose section, no
+ *   obs / var tables, an empty metadata section.  A chunk without nonzeros gets a count section of zeros.
+ *   out_info (4): {bytes written, value type written, chunks, nonzeros}.  out_ms (8 doubles, may be NULL; when given, the stages
+ *   are timed with events): {upload + classify, symbolise, histogram, normalise, rANS encode, escapes, gather + download, wall
+ *   time of the call} in ms.
+ *   *out_status: 0; 2 when value type 0..2 was asked for and a stored value is not a non-negative integer that fits it; -1
+ *   otherwise: a null pointer, value type 4 or 5 (float16, quant8: lossy, not written) or an unknown one, *m or *n below 1,
+ *   *chunk_cols below 1, a malformed CSC (col_ptr, or a row that does not ascend or lies outside [0, *m)), a data section above
+ *   4 GiB (the format's stream offsets are 32-bit), not enough free device memory, no HIP device, a file that cannot be written.
+ *   The reason is in rcppml_gpu_last_error; no file is left behind. */
+RCPPML_GPU_API void rcppml_gpu_spz_write_ex(const int* col_ptr, const int* row_idx, const double* values, int* nnz, int* m, int* n,
+        const char* path, int* value_type, int* chunk_cols, int64_t* out_info, double* out_ms, int* out_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,8 @@ Layout (only what the path needs):
              (csrc/ops_stream.hip); neither the matrix nor its transpose is resident
   svd_streaming.py svd_streaming() / pca_streaming(): the randomized block SVD with the matrix streamed the same way
              (csrc/ops_stream_svd.hip), from a host CSC or an .spz path
+  streampress.py st_write() / st_read() / st_info(): StreamPress v2 `.spz` files; st_write() encodes a host CSC on the device
+             (csrc/ops_spz_write.hip: symbolise, histogram, normalise, rANS encode, escapes) into what the two streamed entries take
   als.py     one-process-per-GPU column-sharded ALS loop over torch.distributed (RCCL): Comm, ShardedALS, HipOps
   data.py    synthetic inputs (restatement of R/simulateNMF.R) and CSC helpers
 """
@@ -40,3 +42,4 @@ from .classify import classify_cv, classify_embedding, classify_logistic  # noqa
 from .similarity import align, bipartiteMatch, cosine, cosine_knn, knn_graph  # noqa: E402,F401
 from .streaming import nmf_streaming  # noqa: E402,F401
 from .svd_streaming import pca_streaming, svd_streaming  # noqa: E402,F401
+from .streampress import st_info, st_read, st_write  # noqa: E402,F401

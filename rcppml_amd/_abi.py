@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_hip_stream_geometry", "rcppml_hip_stream_rhs_w", "rcppml_hip_stream_gram_accum", "rcppml_hip_stream_gram_finish",
     "rcppml_gpu_nmf_streaming_ex",
     "rcppml_hip_stream_block_geometry", "rcppml_hip_stream_block_prod", "rcppml_gpu_svd_streaming_ex",
+    "rcppml_gpu_spz_write_ex",
 ]
 
 
@@ -1878,4 +1879,27 @@ def svd_streaming(csc, spz_path, m, n, k, *, center=False, seed=0, max_iter=3, p
         r.update(U=b["U"][:m * kb].reshape(kb, m).T, d=b["d"], V=b["V"][:n * kb].reshape(kb, n).T, row_means=b["row_means"],
                  **dict(zip(("passes", "panels", "panel_cols", "panel_bytes_peak", "range_table_bytes", "device_ops",
                              "power_iterations", "sketch"), (int(v) for v in info))))
+    return r
+
+
+# ----------------------------------------------------------------------------- .spz writer (ops_spz_write.hip)
+SPZ_VALUE_TYPES = {"uint8": 0, "uint16": 1, "uint32": 2, "fp32": 3, "fp64": 6}      # header_v2.hpp:47-55 (fp16 4, quant8 5: not written)
+SPZ_WRITE_STAGES = ("upload", "symbolise", "histogram", "normalise", "encode", "escapes", "gather", "wall")
+
+
+def spz_write(csc, m, n, path, value_type=-1, chunk_cols=2048, timed=False):
+    """rcppml_gpu_spz_write_ex.  csc: (p, i, x) host arrays; value_type: -1 auto or a header_v2 value type.  Returns dict(status, error,
+    bytes, value_type, chunks, nnz, ms (timed: stage -> ms, SPZ_WRITE_STAGES)); status 2: the values do not fit the integer type."""
+    keep = _csc_args(*csc)
+    info = (C.c_int64 * 4)()
+    ms = (C.c_double * 8)()
+    st = C.c_int(-99)
+    lib().rcppml_gpu_spz_write_ex(_np_ptr(keep[0]), _np_ptr(keep[1]), _np_ptr(keep[2]), _ci(keep[2].shape[0]), _ci(m), _ci(n),
+                                  C.c_char_p(os.fsencode(path)), _ci(value_type), _ci(chunk_cols), info, ms if timed else None, C.byref(st))
+    del keep
+    r = dict(status=st.value, error=last_error() if st.value else "")
+    if st.value == 0:
+        r.update(bytes=int(info[0]), value_type=int(info[1]), chunks=int(info[2]), nnz=int(info[3]))
+        if timed:
+            r["ms"] = dict(zip(SPZ_WRITE_STAGES, (float(v) for v in ms)))
     return r

@@ -25,7 +25,8 @@ def nmf_streaming(data, k, panel_cols=0, tol=1e-4, maxit=100, L1=(0.0, 0.0), L2=
     """A ~ w diag(d) h by alternating NNLS with the matrix streamed through the device one panel of `panel_cols` columns at a time.
 
     `data`: a scipy sparse matrix, a CSC, a 2-D array (taken as sparse), or the path of an .spz file (StreamPress v2, not
-    row-sorted), whose chunks are decoded on the device panel by panel: the matrix then never exists uncompressed, on either side.
+    row-sorted; st_write() produces one), whose chunks are decoded on the device panel by panel: the matrix then never exists
+    uncompressed, on either side.
     `panel_cols` = 0 chooses panels of about 64 MiB of CSC at the matrix's mean column size, in whole multiples of 256 columns,
     never more than n and never more than the W-side kernel's range table allows (2 GiB); a value above n means one panel.  For an
     .spz file `panel_cols` is rounded up to whole chunks.  The other arguments are nmf()'s; `seed` is None,

@@ -23,7 +23,7 @@ def svd_streaming(data, k=10, center=False, seed=None, maxit=3, precision="float
     """Randomized block SVD with the matrix streamed through the device one panel of `panel_cols` columns at a time.
 
     `data`: a scipy sparse matrix, a CSC, a 2-D array (taken as sparse), or the path of an .spz file (StreamPress v2, not
-    row-sorted), whose chunks are decoded on the device panel by panel.  `panel_cols` = 0 chooses panels of about 64 MiB of CSC in
+    row-sorted; st_write() produces one), whose chunks are decoded on the device panel by panel.  `panel_cols` = 0 chooses panels of about 64 MiB of CSC in
     whole multiples of 256 columns; for an .spz file it is rounded up to whole chunks.  k, center, seed, maxit (the power
     iterations, at most 10) and precision ("float" / "double") are svd(method = "randomized")'s; l = k + max(10, k / 5) must be at
     most 128 and at most min(m, n).  Any other svd() argument (tol, L1, L2, nonneg, upper_bound, another method, k = "auto",
