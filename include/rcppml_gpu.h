@@ -745,6 +745,24 @@ RCPPML_GPU_API void rcppml_gpu_classify_logistic_ex(const double* train, const d
         double* out_coef, int* out_aliased, int* out_iters, int* out_converged, double* out_deviance, double* out_prob,
         int* out_predictions, int* out_confusion, double* out_precision, double* out_recall, double* out_f1, int* out_support,
         double* out_auc, int* out_launches, int* out_status);
+/* Histogram random forest (rcppml_amd/csrc/ops_classify_rf.hip): the device counterpart of the reference's
+ * classify_rf (R/classifier_metrics.R:315-380, which calls the randomForest package on the CPU).  Not randomForest's algorithm: 256
+ * uniform bins per feature between the training minimum and maximum, bootstrap and candidate features from the SplitMix64 stream of
+ * *seed (>= 0; 0 is taken as 12345), Gini split search on integer class-by-bin histograms, breadth-first growth to depth 40.  All
+ * counts are integers, so the forest and the votes are bitwise repeatable.  *mtry: candidate features per node, 0 for
+ * floor(sqrt(dim)).  *tree_batch (may be NULL; 0: sized from the free device memory): trees grown together, a test switch -- the
+ * results do not depend on it.  out_votes: n_test x n_classes tree counts; out_prob = votes / *ntree; the metrics as above.
+ * Forest outputs (all NULL or all given): out_feature / out_threshold / out_left / out_class are *ntree x 2 n_train, node ids in
+ * breadth-first order (a split node: feature, threshold bin t of `bin <= t`, left child id, right = left + 1; a leaf: -1, -1, -1;
+ * every node: its majority class; -1 beyond the tree's out_n_nodes); out_lo / out_hi (dim): the bin range of each feature.
+ * out_ms (may be NULL, 43 doubles): host wall time in ms of {binning + bootstrap, prediction, levels 0 .. 40}.
+ * Refused as above, and: dim outside [1, 128], n_classes outside [2, 64], ntree outside [1, 4096], mtry outside [0, dim], a negative seed or
+ * tree_batch, n_train of 2^29 or more (node ids and work-list indices are 32-bit). */
+RCPPML_GPU_API void rcppml_gpu_classify_rf_ex(const double* train, const double* test, const int* train_labels,
+        const int* test_labels, int* n_train, int* n_test, int* dim, int* n_classes, int* ntree, int* mtry, int* seed,
+        int* tree_batch, int* out_votes, double* out_prob, int* out_predictions, int* out_confusion, double* out_precision,
+        double* out_recall, double* out_f1, int* out_support, double* out_auc, int* out_feature, int* out_threshold, int* out_left,
+        int* out_class, int* out_n_nodes, double* out_lo, double* out_hi, double* out_ms, int* out_launches, int* out_status);
 
 /* Last error text of the calling thread ("" if none). */
 RCPPML_GPU_API const char* rcppml_gpu_last_error(void);

@@ -15,7 +15,7 @@ Layout (only what the path needs):
   zi.py      nmf_zi(): zero-inflated GP / NB NMF (zi = "row" / "col") on the HIP zero-inflation path (csrc/ops_zi.hip); nmf(zi = ...)
              itself still refuses, routing it here is a later change
   classify.py classify_embedding() / classify_logistic() / classify_cv(): mirror of the R surface on the HIP classifier-evaluation
-             path (csrc/ops_classify.hip)
+             path (csrc/ops_classify.hip); classify_rf(): the histogram random forest (csrc/ops_classify_rf.hip)
   similarity.py cosine() / bipartiteMatch() / align(): mirror of the R surface on the HIP similarity path (csrc/ops_similarity.hip):
              sparse column cosines (rcppml_gpu_cosine_sparse_ex, tile geometry from rcppml_gpu_cosine_geometry), batched dense
              cosines / correlations (rcppml_gpu_cosine_dense_ex) and the host assignment solver (rcppml_gpu_bipartite_match_ex).  A
@@ -38,7 +38,7 @@ __version__ = "0.1.0"
 
 # the package attribute `refine` is the function from here on; the module's other names come with `from rcppml_amd.refine import ...`
 from .refine import compute_target, refine  # noqa: E402,F401
-from .classify import classify_cv, classify_embedding, classify_logistic  # noqa: E402,F401
+from .classify import classify_cv, classify_embedding, classify_logistic, classify_rf  # noqa: E402,F401
 from .similarity import align, bipartiteMatch, cosine, cosine_knn, knn_graph  # noqa: E402,F401
 from .streaming import nmf_streaming  # noqa: E402,F401
 from .svd_streaming import pca_streaming, svd_streaming  # noqa: E402,F401

@@ -57,7 +57,7 @@ EXPORTED_SYMBOLS = [
     "rcppml_gpu_consensus_double", "rcppml_gpu_hclust_average_double",
     "rcppml_gpu_compute_target_double", "rcppml_gpu_refine_correct_double", "rcppml_gpu_refine_wfit_double", "rcppml_gpu_refine_double",
     "rcppml_gpu_nmf_zi_double", "rcppml_gpu_zi_em_double",
-    "rcppml_gpu_classify_metrics_ex", "rcppml_gpu_classify_knn_ex", "rcppml_gpu_classify_logistic_ex",
+    "rcppml_gpu_classify_metrics_ex", "rcppml_gpu_classify_knn_ex", "rcppml_gpu_classify_logistic_ex", "rcppml_gpu_classify_rf_ex",
     "rcppml_hip_graph_assemble", "rcppml_hip_graph_layer_loss", "rcppml_gpu_factor_net_fit_ex",
     "rcppml_gpu_cosine_sparse_ex", "rcppml_gpu_cosine_knn_sparse_ex", "rcppml_gpu_cosine_geometry", "rcppml_gpu_cosine_dense_ex", "rcppml_gpu_bipartite_match_ex",
     "rcppml_hip_stream_geometry", "rcppml_hip_stream_rhs_w", "rcppml_hip_stream_gram_accum", "rcppml_hip_stream_gram_finish",
@@ -1378,6 +1378,38 @@ def classify_logistic(train, test, train_labels, test_labels, n_classes, maxit=2
     r = _classify_call("rcppml_gpu_classify_logistic_ex", head, b, order, [C.byref(launches)], nte, Cn,
                        dict(coef=(Cn, P), aliased=(Cn, P), iters=(Cn,), converged=(Cn,), deviance=(Cn,), prob=(nte, Cn)), keep)
     r["launches"] = launches.value
+    return r
+
+
+RF_LEVELS = 41                                   # depths 0 .. 40 (out_ms: binning + bootstrap, prediction, then one slot per level)
+
+
+def classify_rf(train, test, train_labels, test_labels, n_classes, ntree=500, mtry=0, seed=0, *, tree_batch=0, forest=False,
+                init=-7.0, buffers=None):
+    """rcppml_gpu_classify_rf_ex: votes (n_test x C tree counts, int32), prob = votes / ntree and the metrics of classify_metrics,
+    plus launches and ms (dict(setup, predict, levels)).  mtry 0: floor(sqrt(dim)).  forest=True adds feature, threshold, left,
+    leaf_class (ntree x 2 n_train, -1 beyond n_nodes and in a leaf's feature / threshold / left), n_nodes, lo, hi.  tree_batch: trees
+    grown together (0: sized from free device memory); a test switch, the results do not depend on it."""
+    head, keep, ntr, nte, dim = _classify_head(train, test, train_labels, test_labels, n_classes)
+    Cn, T = int(n_classes), int(ntree)
+    b = buffers
+    if b is None:
+        b = _metric_buffers(nte, Cn, init)
+        b.update(votes=np.full(max(nte, 1) * max(Cn, 1), int(init), np.int32), prob=np.full(max(nte, 1) * max(Cn, 1), init))
+        if forest:
+            cap = max(T, 1) * 2 * max(ntr, 1)
+            b.update({k: np.full(cap, int(init), np.int32) for k in ("feature", "threshold", "left", "leaf_class")})
+            b.update(n_nodes=np.full(max(T, 1), int(init), np.int32), lo=np.full(max(dim, 1), init), hi=np.full(max(dim, 1), init))
+    fkeys = ("feature", "threshold", "left", "leaf_class", "n_nodes", "lo", "hi")
+    launches, ms = C.c_int(0), np.zeros(2 + RF_LEVELS)
+    head += [_ci(T), _ci(mtry), _ci(seed), _ci(tree_batch)]
+    order = ("votes", "prob") + _METRIC_OUT + (fkeys if forest else ())
+    tail = ([] if forest else [None] * len(fkeys)) + [_np_ptr(ms), C.byref(launches)]
+    shapes = dict(votes=(nte, Cn), prob=(nte, Cn))
+    if forest:
+        shapes.update({k: (T, 2 * ntr) for k in fkeys[:4]}, n_nodes=(T,), lo=(dim,), hi=(dim,))
+    r = _classify_call("rcppml_gpu_classify_rf_ex", head, b, order, tail, nte, Cn, shapes, keep)
+    r.update(launches=launches.value, ms=dict(setup=float(ms[0]), predict=float(ms[1]), levels=ms[2:].copy()))
     return r
 
 

@@ -96,6 +96,34 @@ def classify_logistic(embedding, labels, test_fraction=0.2, test_idx=None, seed=
     return out
 
 
+def classify_rf(embedding, labels, test_fraction=0.2, test_idx=None, ntree=500, seed=None, *, mtry=None, return_forest=False):
+    """Random-forest classifier on an embedding, evaluated on held-out rows (R's classify_rf).  Returns R's fn_classifier_eval
+    fields as a dict (method "random_forest"), plus ntree, mtry, votes (n_test x C tree counts), prob (votes / ntree) and launches.
+    return_forest=True adds the node arrays feature, threshold, left, leaf_class (ntree x 2 n_train; a split node sends
+    bin <= threshold to node `left`, the rest to left + 1; -1 marks a leaf and the slots beyond n_nodes), n_nodes, lo and hi.
+
+    Deviation from R: R hands the work to the randomForest package (exact sorted thresholds, R's Mersenne Twister)
+    on the CPU.  This is a histogram forest on the device with a specification of its own: 256 uniform bins per feature between the
+    training minimum and maximum, bootstrap rows and mtry candidate features per node (default max(1, floor(sqrt(p))), as
+    randomForest) from the project's SplitMix64 stream, Gini splits on integer class counts, depth at most 40.  Every count is an
+    integer, so two runs, any tree batch and any grid give the same forest bit for bit."""
+    emb, levels, codes, train_idx, test_idx = _prepare(embedding, labels, test_fraction, test_idx, seed)
+    p = emb.shape[1]
+    ntree = int(ntree)
+    mtry = max(1, int(np.floor(np.sqrt(p)))) if mtry is None else int(mtry)
+    if ntree < 1:
+        raise ValueError("ntree must be >= 1")
+    if mtry < 1 or mtry > p:
+        raise ValueError("mtry must be in [1, ncol(embedding)]")
+    r = _abi._check(_abi.classify_rf(emb[train_idx], emb[test_idx], codes[train_idx], codes[test_idx], len(levels), ntree, mtry,
+                                     0 if seed is None else int(seed), forest=return_forest), "classify_rf")
+    out = _eval_result(r, levels, codes, train_idx, test_idx, "random_forest")
+    out.update(ntree=ntree, mtry=mtry, votes=r["votes"], prob=r["prob"], launches=r["launches"])
+    if return_forest:
+        out.update({key: r[key] for key in ("feature", "threshold", "left", "leaf_class", "n_nodes", "lo", "hi")})
+    return out
+
+
 def fold_scale(train, test):
     """R's scale() by the training columns' mean and sd (n - 1; an sd of 0 becomes 1)."""
     means = train.mean(axis=0)
